@@ -2,7 +2,7 @@
 """Headline benchmark: Neumann-Neumann Schur-PCG on the 1 M-DoF / 8-subdomain problem
 (BASELINE.json configs[2] at N=1; configs[3] sharding at N>1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one complete `pcg(S, b_schur, 0, ΠSnn)` solve (Example03:193) with the assembled
@@ -16,9 +16,12 @@ At N>1 the 8 subdomains are split across ranks (8/N each), Γ-vectors are replic
 xGMI + flags, csrc/exchange.hpp) when every rank can map its peers' arenas, RCCL all-reduces otherwise (`--exchange`);
 total work is fixed, so scaling is "strong".
 
-Extra objects on the JSON line: `roofline` for the dominant kernel (batched dense GEMV of the S-apply,
-HIP events on the library's stream) and `cpu_baseline` (the C oracle, OpenMP over the host cores,
-rank 0 at N=1 only).
+A plain run sets up, warms up, times the K solves and prints the line; `roofline`, `cpu_baseline` and
+`secondary` are null in it. `--full` adds them: `roofline` for the dominant kernel (batched dense GEMV of the
+S-apply, HIP events on the library's stream), `cpu_baseline` (the C oracle, OpenMP over the host cores, also the
+parity check of the run; rank 0 at N=1 only) and `secondary` (the other loops, config 2, set-up, config 5).
+
+`--dump-outputs DIR` writes what the last timed solve returned (x, it, res_norm) as DIR/<name>.npy in float64.
 """
 from __future__ import annotations
 
@@ -89,7 +92,7 @@ def bench_full_system(args):
     Aop = api.SparseMatrixCSC(ctx, A)
     M = api.JacobiPreconditioner(ctx, A.diagonal())
     bd = torch.from_numpy(b).cuda()
-    steps, warm = min(args.steps, 20), min(args.warmup, 2)
+    steps, warm = args.steps, args.warmup
     xs = [torch.zeros(n, dtype=torch.float64, device="cuda") for _ in range(steps + warm)]
     for w in range(warm):
         _, its, res = api.pcg(Aop, bd, xs[w], M, eps=args.eps)
@@ -99,6 +102,17 @@ def bench_full_system(args):
         _, it, res = api.pcg(Aop, bd, xs[warm + k], M, eps=args.eps)
     ctx.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x=xs[warm + steps - 1], it=it, res_norm=res)
+    out = {"metric": "full-A Jacobi-PCG iterations/sec, 250k DoF (configs[1])", "value": round(steps * (it - 1) / el, 1),
+           "unit": "iterations/s", "n_gpus": 1, "steps": steps, "warmup": warm, "ms_per_step": round(el / steps * 1e3, 3),
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": f"configs[1]: N={N}, n={n}, nnz={A.nnz}, a=0.1+1e-4xy, pcg(A,b,0,Jacobi)", "it": it,
+                      "final_relres": float(res[-1] / np.linalg.norm(b))},
+           "roofline": None, "cpu_baseline": None}
+    if not args.full:
+        OUT.emit(json.dumps(out))
+        return
     _, nb = Aop.bytes()
     e0, e1 = api.Event(ctx), api.Event(ctx)
     if args.kernel_reps <= 0:      # profiling passes (PMC): only the solves
@@ -121,15 +135,10 @@ def bench_full_system(args):
         tc = time.perf_counter() - t0
         cpu = {"value": round(nsolve * (ito - 1) / tc, 1), "unit": "iterations/s", "cores": cores, "kind": "port",
                "sample": f"{nsolve} full Jacobi-PCG solves of the same system in {tc:.1f}s (C restatement, OpenMP row-gather SpMV; not Julia)"}
-    out = {"metric": "full-A Jacobi-PCG iterations/sec, 250k DoF (configs[1])", "value": round(steps * (it - 1) / el, 1),
-           "unit": "iterations/s", "n_gpus": 1, "steps": steps, "warmup": warm, "ms_per_step": round(el / steps * 1e3, 3),
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": f"configs[1]: N={N}, n={n}, nnz={A.nnz}, a=0.1+1e-4xy, pcg(A,b,0,Jacobi)", "it": it,
-                      "final_relres": float(res[-1] / np.linalg.norm(b))},
-           "roofline": {"bound": "hbm", "kernel": "k_spmv_csr", "achieved": round(nb / us / 1e3, 1), "peak": HBM_PEAK_GBS,
-                        "unit": "GB/s", "frac": round(nb / us / 1e3 / HBM_PEAK_GBS, 4), "traffic": spmv_traffic(),
-                        "bytes_per_launch": int(nb), "us_per_launch": round(us, 3)},
-           "cpu_baseline": cpu}
+    out["roofline"] = {"bound": "hbm", "kernel": "k_spmv_csr", "achieved": round(nb / us / 1e3, 1), "peak": HBM_PEAK_GBS,
+                       "unit": "GB/s", "frac": round(nb / us / 1e3 / HBM_PEAK_GBS, 4), "traffic": spmv_traffic(),
+                       "bytes_per_launch": int(nb), "us_per_launch": round(us, 3)}
+    out["cpu_baseline"] = cpu
     OUT.emit(json.dumps(out))
 
 
@@ -475,6 +484,15 @@ class StdoutToStderr:
 OUT = None
 
 
+def dump_outputs(out_dir: str, **arrays) -> None:
+    """--dump-outputs: what the caller of the timed solve received in the last step (x on the device, `it`, the residual
+    history), one float64 DIR/<name>.npy each, so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else a
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(a, dtype=np.float64))
+
+
 def spawn_ranks(n: int) -> None:
     """Run this same command line as n rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set the way
     torch.distributed.run sets them) and wait for them. Rank 0 prints the JSON line on the inherited stdout."""
@@ -538,8 +556,15 @@ def main():
     ap.add_argument("--many-subdomains", action="store_true",
                     help="add the 160-subdomain problem (n_Γ = 9417) to `secondary`; off by default so that the kernel statistics of the "
                          "default command contain the headline's launches of k_gemv_pcg only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: `roofline` (--kernel-reps), `cpu_baseline` with the oracle's "
+                         "parity check (--no-cpu-baseline), `secondary` (--no-secondary, --config5-reals, --many-subdomains)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write x, it and res_norm of the last timed solve as DIR/<name>.npy (float64)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as fresh children, BEFORE this
@@ -765,7 +790,57 @@ def main():
     loop_its = its - 1
     value = args.steps * loop_its / elapsed
     relres = float(res[-1] / np.linalg.norm(b_host))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x=xs[args.warmup + args.steps - 1], it=it, res_norm=res)
+    short = max(2, min(5, its - 2))
+    folded = its > short + 2   # every layout runs the folded loop (sharded launches are followed by an exchange: peer stores or an RCCL all-reduce of the launch's table)
 
+    # ---------------- --full: roofline, secondary workloads and the CPU baseline (with the oracle's parity check)
+    roofline = cpu = secondary = None
+    if args.full:
+        full = full_measurements(args, rank, world, multi, api, fem, ctx, mesh, P, f, uex, S, M, b_dev, b_host, n_Γ, ndom,
+                                 its, res, short, folded, value, elapsed)
+        if full is None:
+            return
+        roofline, secondary, cpu = full
+
+    if rank == 0:
+        out = {
+            "metric": "Schur-PCG iterations/sec (NN-preconditioned, assembled local Schurs), 1M DoF",
+            "value": round(value, 1), "unit": "iterations/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": f"configs[2]: N={args.N} structured P1 mesh, {n_free} free DoF, {ndom} subdomains "
+                                   f"({args.px}x{args.py} boxes), lognormal a=exp(g) seed {args.seed}, n_Γ={n_Γ}; "
+                                   f"pcg(S, b_schur, 0, ΠSnn), eps={args.eps:g}",
+                       "subdomains_per_gpu": hi - lo,
+                       "parallelism": ("single GPU" if not multi else
+                                       f"S sharded {hi - lo} subdomain(s)/GPU; NN blocks "
+                                       + ("sharded: folded loop, two peer exchanges per iteration (the launches store into every rank's arena over xGMI and signal; "
+                                          + ("the next launch waits for the flags itself" if peer_inwait else "a one-wave kernel waits for the flags") + ", csrc/exchange.hpp)"
+                                          if args.shard_precond and peer_on else
+                                          "sharded: folded loop, an RCCL all-reduce of the launch's table behind each of the two launches" if args.shard_precond
+                                          else "replicated: folded loop, 1 exchange of the S launch's contribution table per iteration ("
+                                               + ("peer stores" if peer_on else "RCCL all-reduce") + ")")),
+                       "exchange": (("peer-inlaunch" if peer_inwait else "peer") if peer_on else "rccl") if multi else None,
+                       "layouts_measured": layout_times,
+                       "it": its, "loop_iterations_per_solve": loop_its,
+                       "final_relres": relres, "launches_per_iteration": 2 if folded else 4},
+            "roofline": roofline,
+            "cpu_baseline": cpu,
+            "secondary": secondary,
+        }
+        OUT.emit(json.dumps(out))
+    if multi:
+        dist.destroy_process_group()
+
+
+def full_measurements(args, rank, world, multi, api, fem, ctx, mesh, P, f, uex, S, M, b_dev, b_host, n_Γ, ndom,
+                      its, res, short, folded, value, elapsed):
+    """What `--full` adds to the headline run, on the same device-resident operators after the timed region:
+    (roofline, secondary, cpu_baseline); None after a profiling run's reduced line (--kernel-reps 0)."""
+    import torch
     # ---------------- roofline of the dominant kernel, HIP events on the library's stream
     # In the timed region every iteration is two launches of k_gemv_pcg (the S-apply and the NN-apply GEMV with
     # the PCG vector work folded in). Their average duration is measured live as the GPU-time difference between
@@ -776,7 +851,7 @@ def main():
     if args.kernel_reps <= 0:      # profiling runs: leave only the solves in the trace
         if rank == 0:
             OUT.emit(json.dumps({"value": round(value, 1), "ms_per_step": round(elapsed / args.steps * 1e3, 4), "it": its}))
-        return
+        return None
 
     def gpu_ms(maxit, reps=30):
         ts = []
@@ -790,8 +865,6 @@ def main():
                 ts.append(e0.elapsed_ms(e1))
         return float(np.median(ts))
 
-    short = max(2, min(5, its - 2))
-    folded = its > short + 2   # every layout runs the folded loop (sharded launches are followed by an exchange: peer stores or an RCCL all-reduce of the launch's table)
     k_us = None
     if folded:
         t_short = gpu_ms(short)
@@ -864,36 +937,7 @@ def main():
                "sample": f"{nsolve} full NN-PCG solves of the same 1M-DoF Schur system in {tc:.1f}s "
                          "(C restatement of cg.jl/EPDD.jl, OpenMP row-parallel GEMV; not Julia)"}
 
-    if rank == 0:
-        out = {
-            "metric": "Schur-PCG iterations/sec (NN-preconditioned, assembled local Schurs), 1M DoF",
-            "value": round(value, 1), "unit": "iterations/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"configs[2]: N={args.N} structured P1 mesh, {n_free} free DoF, {ndom} subdomains "
-                                   f"({args.px}x{args.py} boxes), lognormal a=exp(g) seed {args.seed}, n_Γ={n_Γ}; "
-                                   f"pcg(S, b_schur, 0, ΠSnn), eps={args.eps:g}",
-                       "subdomains_per_gpu": hi - lo,
-                       "parallelism": ("single GPU" if not multi else
-                                       f"S sharded {hi - lo} subdomain(s)/GPU; NN blocks "
-                                       + ("sharded: folded loop, two peer exchanges per iteration (the launches store into every rank's arena over xGMI and signal; "
-                                          + ("the next launch waits for the flags itself" if peer_inwait else "a one-wave kernel waits for the flags") + ", csrc/exchange.hpp)"
-                                          if args.shard_precond and peer_on else
-                                          "sharded: folded loop, an RCCL all-reduce of the launch's table behind each of the two launches" if args.shard_precond
-                                          else "replicated: folded loop, 1 exchange of the S launch's contribution table per iteration ("
-                                               + ("peer stores" if peer_on else "RCCL all-reduce") + ")")),
-                       "exchange": (("peer-inlaunch" if peer_inwait else "peer") if peer_on else "rccl") if multi else None,
-                       "layouts_measured": layout_times,
-                       "it": its, "loop_iterations_per_solve": loop_its,
-                       "final_relres": relres, "launches_per_iteration": 2 if folded else 4},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "secondary": secondary,
-        }
-        OUT.emit(json.dumps(out))
-    if multi:
-        dist.destroy_process_group()
+    return roofline, secondary, cpu
 
 
 if __name__ == "__main__":

@@ -3,8 +3,10 @@ import sys
 
 # In-process ranks (tests/test_gpu_multirank.py, test_gpu_parity.py) join their contexts by device-side flags: kernels of
 # one rank wait for kernels of another, which needs a hardware queue per rank (include/mi355schur.h, mi_ctx_loopback_init).
-# The HIP runtime reads this once, at its first call.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# The HIP runtime reads this once, at its first call. A smaller value already in the environment (the runtime's own
+# default is 4) is raised, not kept: with fewer queues than live streams the ranks' waits expire or share a queue.
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 # ... and the ranks' host<->device copies must not share an engine queue: a copy that waits for a spinning kernel would
 # block the next rank's copy in (measured at copies above the runtime's blit threshold): copies as kernels on each
 # rank's own stream. One process per GPU (the production layout) needs neither setting.

@@ -259,7 +259,7 @@ def test_bench_rehearses_its_multi_gpu_path_on_one_gpu():
     against RCCL, the timing of both layouts, the JSON contract — with ONE rank on this GPU (N = 200: seconds)."""
     import json
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--N", "200", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-secondary", "--kernel-reps", "20"]
+           "--full", "--no-cpu-baseline", "--no-secondary", "--kernel-reps", "20"]
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)

@@ -8,7 +8,7 @@ for v in default t2048 t4096; do
   if [ $v = default ]; then cp /tmp/lib_default.so julia-phd-krylov-spdes_amd/libmi355schur.so; else cp build_variants/lib_$v.so julia-phd-krylov-spdes_amd/libmi355schur.so; fi
   echo "== $v" >> $OUT/probe.log
   timeout -k 10 300 python tools/interior_probe.py 2>/dev/null | head -2 >> $OUT/probe.log
-  timeout -k 10 200 python bench.py --workload fullA --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config 2:', d['value'], d['roofline'])" >> $OUT/probe.log
+  timeout -k 10 200 python bench.py --full --workload fullA --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config 2:', d['value'], d['roofline'])" >> $OUT/probe.log
 done
 cp /tmp/lib_default.so julia-phd-krylov-spdes_amd/libmi355schur.so
 cat $OUT/probe.log
