@@ -112,6 +112,7 @@ int mi_ctx_set_exchange(mi_ctx_t ctx, int use_peer_exchange);
 #define MI_QUERY_EXCHANGES 3
 #define MI_QUERY_EXPERIMENTAL 5    /* 1: built with `make EXPERIMENTAL=1` (persistent on-chip PCG, rocBLAS/rocSOLVER set-up route) */
 #define MI_QUERY_SPECTRAL_PINV 4   /* blocks of mi_nn_pinv that went to the eigen-decomposition (rocSOLVER) so far, process-wide */
+#define MI_QUERY_FOLDED_PCG 6      /* launches of the folded PCG kernel issued (captured or direct) so far, process-wide */
 int mi_ctx_query(mi_ctx_t ctx, int what, int64_t *out);
 /* Test facility: in-process ranks. `n_ranks` contexts of ONE process (one host thread each, typically all on the same
  * device) call mi_ctx_loopback_init with the same group and then behave like ranks of a multi-GPU job: operators built
@@ -310,9 +311,12 @@ int mi_schur_matfree_interior_solutions(mi_op_t op, const double *u_gamma, const
  * mi_nn_pinv — `prepare_neumann_neumann_schur_precond(Sd, ...)` (EPDD.jl:1201-1220): ΠS_d = pinv(S_d, rtol) of the symmetric
  * blocks; rtol <= 0 means sqrt(eps(Float64)), the reference's value. LinearAlgebra.pinv drops the singular values
  * <= rtol * the largest. Three routes, tried in this order per block, all giving that result: (1) 1/||S^{-1}||_inf >
- * rtol ||S||_inf proves that nothing is dropped: the pseudo-inverse is the inverse (the Gauss-Jordan kernels of the set-up);
- * (2) floating subdomains, ||S 1||_inf <= rtol ||S||_inf: S^+ = (S + α u u')^{-1} - u u'/α, u = 1/sqrt(n), α = ||S||_inf, the
- * same kernels and the same certificate on the shifted matrix; (3) anything else (rank deficiency > 1): eigen-decomposition
+ * rtol ||S||_inf proves that nothing is dropped: the pseudo-inverse is the inverse (the Gauss-Jordan kernels of the set-up),
+ * used only if the probe residual ||v - Z S v||_inf <= 4 n eps ||Z||_inf ||S||_inf (v = ±1) shows Z accurate (routes 1, 2);
+ * (2) floating subdomains, ||S 1||_inf <= rtol max(max_i |S_ii|, ||S||_inf / sqrt(n)) (lower bounds on the largest singular
+ * value, so pinv drops an eigenvalue as well): S^+ = (S + α u u')^{-1} - u u'/α, u = 1/sqrt(n), α = ||S||_inf, the same kernels
+ * and the same certificate on the shifted matrix, plus ||S 1||_inf ||(S + α u u')^{-1}||_inf <= rtol (u close to the dropped
+ * eigenvector); (3) anything else (rank deficiency > 1, an eigenvalue near the cut-off): eigen-decomposition
  * (rocSOLVER dsyevd, bound with dlopen; singular values = |eigenvalues|). MI_QUERY_SPECTRAL_PINV counts route (3).
  * mi_dense_set_blocks — new blocks (concatenated, column-major) for an existing mi_schur_assembled / mi_nn operator on the same
  * maps: the per-realization update of S (Example07:180-199) without re-creating the operator. */

@@ -184,9 +184,9 @@ class Context:
         check(self._L.mi_ctx_set_exchange(self._h, C.c_int(int(mode))))
 
     def query(self, what: str) -> int:
-        """`mi_ctx_query`: "no_graph", "peer_exchange", "graph_replays", "exchanges", "spectral_pinv"."""
+        """`mi_ctx_query`: "no_graph", "peer_exchange", "graph_replays", "exchanges", "spectral_pinv", "experimental", "folded_pcg"."""
         out = i64(0)
-        check(self._L.mi_ctx_query(self._h, C.c_int({"no_graph": 0, "peer_exchange": 1, "graph_replays": 2, "exchanges": 3, "spectral_pinv": 4, "experimental": 5}[what]), C.byref(out)))
+        check(self._L.mi_ctx_query(self._h, C.c_int({"no_graph": 0, "peer_exchange": 1, "graph_replays": 2, "exchanges": 3, "spectral_pinv": 4, "experimental": 5, "folded_pcg": 6}[what]), C.byref(out)))
         return int(out.value)
 
     def peer_connect(self, rank: int, n_ranks: int, all_gather) -> None:

@@ -433,6 +433,7 @@ int mi_ctx_query(mi_ctx_t ctx, int what, int64_t *out) {
       case MI_QUERY_PEER_EXCHANGE: *out = ctx->use_peer() ? (ctx->peer_inwait ? 3 : ctx->peer->fine_grained ? 2 : 1) : 0; break;
       case MI_QUERY_GRAPH_REPLAYS: *out = ctx->n_replays; break;
       case MI_QUERY_SPECTRAL_PINV: *out = spectral_pinv_calls().load(); break;
+      case MI_QUERY_FOLDED_PCG: *out = folded_pcg_launches().load(); break;
       case MI_QUERY_EXPERIMENTAL:
 #ifdef MI355_EXPERIMENTAL
         *out = 1;

@@ -1,6 +1,7 @@
 // Operators (`A*x`, `mul!`) and preconditioners (`M \ r`) of the hot path, device resident.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <functional>
 #include <numeric>
@@ -28,6 +29,7 @@ inline int to_i32(int64_t v, int64_t lo, int64_t hi, const char *what) {
 
 // ------------------------------------------------------------------ base class
 constexpr int PART_ROWS = 4;   // fewest rows a streamed tile can have (4 waves x 1 row)
+inline std::atomic<long long> &folded_pcg_launches() { static std::atomic<long long> n{0}; return n; }   // k_gemv_pcg launches issued (mi_ctx_query)
 struct DenseBlockOp;
 struct Operator {
   mi_ctx_s *ctx;
@@ -559,6 +561,7 @@ struct DenseBlockOp : Operator {
   // One launch of the folded PCG pair (kernels.hpp k_gemv_pcg); PHASE 1 on the ΠS operator, 0 on S.
   void gemv_pcg(int phase, const PcgFold &f) {
     if (!ntiles) return;
+    ++folded_pcg_launches();
     const bool xchg = f.xp != nullptr || f.x_inwait != 0;   // this launch stores into the peers' arenas and / or waits for them
 #define MI_PCG4(R, P, C, V) do { if (xchg) hipLaunchKernelGGL((k_gemv_pcg<R, P, C, V, true>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, f); \
                                  else hipLaunchKernelGGL((k_gemv_pcg<R, P, C, V, false>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, f); } while (0)

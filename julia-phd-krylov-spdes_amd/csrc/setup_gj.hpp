@@ -18,6 +18,7 @@
 // depends only on the plan: it is captured once and replayed per realization on plan-owned buffers.
 #pragma once
 #include <atomic>
+#include <limits>
 
 #include "setup_dense.hpp"
 
@@ -1090,8 +1091,12 @@ inline void gj_run(mi_setup_s &P, const double *ii_val, const double *ig_val, co
 // span{u}, u = 1/sqrt(n):   S^+ = (S + α u u')^{-1} - (1/α) u u'   for any α > 0 (S + α u u' has the eigenpairs of S with
 // the zero eigenvalue replaced by α). With α = ||S||_inf the shifted matrix is as well conditioned as S on its range, the
 // SAME kernels invert it, and the same certificate on it shows that no OTHER singular value lies below the cut-off. Taken
-// when ||S 1||_inf <= rtol ||S||_inf (the constant vector is in the numerical kernel pinv would drop). Only blocks that fail
-// both tests (rank deficiency > 1, or a kernel that is not the constants) go to the spectral route (rocSOLVER dsyevd).
+// when ||S 1||_inf <= rtol max(max_i |S_ii|, ||S||_inf / sqrt(n)): both terms are lower bounds on σ_max and
+// λ_min <= u'S u <= ||S 1||_inf, so pinv drops an eigenvalue too (a test against rtol ||S||_inf alone, up to sqrt(n) σ_max,
+// would drop eigenvalues in (rtol σ_max, rtol ||S||_inf] that pinv keeps). The result is then accepted only if also
+// ||S 1||_inf ||(S + α u u')^{-1}||_inf <= rtol, which bounds the angle between u and the dropped eigenvector. Blocks that
+// fail any of these (rank deficiency > 1, a kernel that is not the constants, an eigenvalue near the cut-off) go to the
+// spectral route (rocSOLVER dsyevd).
 template <bool SIGNED>
 __global__ __launch_bounds__(256) void k_rowsum_max_t(int n, const double *__restrict__ A, double *__restrict__ out) {
   __shared__ double sm[NT / 64 + 1];
@@ -1101,6 +1106,44 @@ __global__ __launch_bounds__(256) void k_rowsum_max_t(int n, const double *__res
     for (int c = 0; c < n; ++c) s2 += SIGNED ? A[r + (size_t)c * n] : fabs(A[r + (size_t)c * n]);   // symmetric: column sums = row sums, coalesced this way
     s2 = fabs(s2);
     m = fmax(m, isfinite(s2) ? s2 : INFINITY);
+  }
+  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_down(m, o, 64));
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
+}
+// max_i |A_ii| (<= ||A||_2), one partial maximum per workgroup as k_rowsum_max_t
+__global__ __launch_bounds__(256) void k_diag_max(int n, const double *__restrict__ A, double *__restrict__ out) {
+  __shared__ double sm[NT / 64 + 1];
+  double m = 0.0;
+  for (int r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
+    const double a = fabs(A[r + (size_t)r * n]);
+    m = fmax(m, isfinite(a) ? a : INFINITY);
+  }
+  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_down(m, o, 64));
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
+}
+// Probe of the computed inverse: v_j = ±1 (fixed signs), t = (A + c) v with c added to every entry as T = A + c was formed
+// before the inversion, then out[blockIdx.x] = max_i |v_i - (Z t)_i| over this workgroup's rows (k_probe_residual).
+__device__ __forceinline__ double probe_sign(int j) { return ((unsigned)j * 2654435761u) & 0x10000u ? 1.0 : -1.0; }
+__global__ __launch_bounds__(256) void k_probe_apply(int n, const double *__restrict__ A, double c, double *__restrict__ t) {
+  for (int r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
+    double s2 = 0.0;
+    for (int j = 0; j < n; ++j) s2 += (A[r + (size_t)j * n] + c) * probe_sign(j);
+    t[r] = s2;
+  }
+}
+__global__ __launch_bounds__(256) void k_probe_residual(int n, const double *__restrict__ Z, const double *__restrict__ t,
+                                                        double *__restrict__ out) {
+  __shared__ double sm[NT / 64 + 1];
+  double m = 0.0;
+  for (int r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
+    double s2 = 0.0;
+    for (int j = 0; j < n; ++j) s2 += Z[r + (size_t)j * n] * t[j];
+    const double e = fabs(probe_sign(r) - s2);
+    m = fmax(m, isfinite(e) ? e : INFINITY);
   }
   for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_down(m, o, 64));
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
@@ -1122,15 +1165,15 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
   std::vector<GjStep> st(ndom);
   std::vector<GjDom> dm(ndom);
   size_t tot = 0;
-  std::vector<size_t> oT(ndom), o0(ndom), o1(ndom), oP(ndom), off(ndom);
-  size_t run = 0;
+  std::vector<size_t> oT(ndom), o0(ndom), o1(ndom), oP(ndom), off(ndom), ov(ndom);
+  size_t run = 0, nsum = 0;
   for (int d = 0; d < ndom; ++d) {
     const size_t n = (size_t)n_gamma_d[d], nn = std::max<size_t>(1, n * n);
-    off[d] = run; run += n * n;
+    off[d] = run; run += n * n; ov[d] = nsum; nsum += n;
     auto take = [&](size_t cnt) { const size_t o = tot; tot += (cnt + 31) / 32 * 32; return o; };
     oT[d] = take(nn); o0[d] = take(nn); o1[d] = take(nn); oP[d] = take(2 * GJ_B * GJ_B + 16);
   }
-  DevBuf<double> pool(tot + 32), norms((size_t)3 * ndom * 8);
+  DevBuf<double> pool(tot + 32), norms((size_t)5 * ndom * 8), probe(nsum + 32);
   for (int d = 0; d < ndom; ++d) {
     const int n = (int)n_gamma_d[d];
     st[d] = GjStep{}; st[d].n0 = n; st[d].nb = (n + GJ_B - 1) / GJ_B;
@@ -1139,9 +1182,10 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
   auto cdiv = [](int a, int b) { return (a + b - 1) / b; };
   DevBuf<GjStep> std_; DevBuf<GjDom> dmd;
   // One batch: T_d = S_d + shift_d (every entry) for the blocks `ds`, inverted together; norms of S_d (abs row sums), of the
-  // inverse, and of S_d 1 (signed row sums) come back to the host.
+  // inverse, of S_d 1 (signed row sums), the largest |diagonal entry| of S_d, and the probe residual ||v - Z (S_d + shift_d) v||_inf
+  // (v = ±1) come back to the host.
   auto batch = [&](const std::vector<int> &ds, const std::vector<double> &shift, std::vector<double> &nS, std::vector<double> &nZ,
-                   std::vector<double> &nS1) {
+                   std::vector<double> &nS1, std::vector<double> &nD, std::vector<double> &nR) {
     std::vector<GjStep> sb; std::vector<GjDom> db;
     int nmax = 1, nbmax = 0;
     for (size_t k = 0; k < ds.size(); ++k) {
@@ -1163,46 +1207,63 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
     for (size_t k = 0; k < ds.size(); ++k) {
       const int d = ds[k], n = (int)n_gamma_d[d];
       if (!n) continue;
-      hipLaunchKernelGGL(k_rowsum_max_t<false>, dim3(8), dim3(256), 0, s, n, Sd + off[d], norms.p + (size_t)24 * d);
-      hipLaunchKernelGGL(k_rowsum_max_t<false>, dim3(8), dim3(256), 0, s, n, dm[d].Z[st[d].nb & 1], norms.p + (size_t)24 * d + 8);
-      hipLaunchKernelGGL(k_rowsum_max_t<true>, dim3(8), dim3(256), 0, s, n, Sd + off[d], norms.p + (size_t)24 * d + 16);
+      hipLaunchKernelGGL(k_probe_apply, dim3(8), dim3(256), 0, s, n, Sd + off[d], shift[k], probe.p + ov[d]);
+      hipLaunchKernelGGL(k_probe_residual, dim3(8), dim3(256), 0, s, n, (const double *)dm[d].Z[st[d].nb & 1], (const double *)probe.p + ov[d],
+                         norms.p + (size_t)40 * d + 32);
+      hipLaunchKernelGGL(k_rowsum_max_t<false>, dim3(8), dim3(256), 0, s, n, Sd + off[d], norms.p + (size_t)40 * d);
+      hipLaunchKernelGGL(k_rowsum_max_t<false>, dim3(8), dim3(256), 0, s, n, dm[d].Z[st[d].nb & 1], norms.p + (size_t)40 * d + 8);
+      hipLaunchKernelGGL(k_rowsum_max_t<true>, dim3(8), dim3(256), 0, s, n, Sd + off[d], norms.p + (size_t)40 * d + 16);
+      hipLaunchKernelGGL(k_diag_max, dim3(8), dim3(256), 0, s, n, Sd + off[d], norms.p + (size_t)40 * d + 24);
     }
     MI_HIP(hipGetLastError());
-    std::vector<double> nh((size_t)24 * ndom);
+    std::vector<double> nh((size_t)40 * ndom);
     MI_HIP(hipMemcpyAsync(nh.data(), norms.p, sizeof(double) * nh.size(), hipMemcpyDeviceToHost, s));
     MI_HIP(hipStreamSynchronize(s));
-    nS.assign(ndom, 0.0); nZ.assign(ndom, 0.0); nS1.assign(ndom, 0.0);
+    nS.assign(ndom, 0.0); nZ.assign(ndom, 0.0); nS1.assign(ndom, 0.0); nD.assign(ndom, 0.0); nR.assign(ndom, 0.0);
     for (int d : ds)
       for (int k = 0; k < 8; ++k) {
-        nS[d] = std::max(nS[d], nh[(size_t)24 * d + k]); nZ[d] = std::max(nZ[d], nh[(size_t)24 * d + 8 + k]);
-        nS1[d] = std::max(nS1[d], nh[(size_t)24 * d + 16 + k]);
+        nS[d] = std::max(nS[d], nh[(size_t)40 * d + k]); nZ[d] = std::max(nZ[d], nh[(size_t)40 * d + 8 + k]);
+        nS1[d] = std::max(nS1[d], nh[(size_t)40 * d + 16 + k]); nD[d] = std::max(nD[d], nh[(size_t)40 * d + 24 + k]);
+        nR[d] = std::max(nR[d], nh[(size_t)40 * d + 32 + k]);
       }
   };
   std::vector<int> all;
   for (int d = 0; d < ndom; ++d) all.push_back(d);
-  std::vector<double> nS, nZ, nS1, zero(ndom, 0.0);
-  batch(all, zero, nS, nZ, nS1);
+  std::vector<double> nS, nZ, nS1, nD, nR, zero(ndom, 0.0);
+  batch(all, zero, nS, nZ, nS1, nD, nR);
+  // The certificates below test the computed inverse Z, so they say nothing about its accuracy: without pivoting the block
+  // Gauss-Jordan kernels lose accuracy much faster than κ eps beyond κ ~ 1e5 (measured: 41 % at κ = 1e8, n = 65). A good
+  // inverse has |I - Z T| <= c n eps |Z| |T| entry-wise, so ||v - Z T v||_inf <= c n eps ||Z||_inf ||T||_inf for v = ±1;
+  // a result whose probe residual exceeds that (c = PROBE_C) is not used, and the block goes to the next route.
+  constexpr double PROBE_C = 4.0;
+  const double eps = std::numeric_limits<double>::epsilon();
+  auto probe_ok = [&](int n, double nT, double nZ_, double res) { return std::isfinite(res) && res <= PROBE_C * n * eps * nT * nZ_; };
   std::vector<int> floating, slow;
   std::vector<double> shift;
   for (int d = 0; d < ndom; ++d) {
     const int n = (int)n_gamma_d[d];
     if (!n) continue;
     if (!std::isfinite(nS[d])) raise(MI_ERR_SINGULAR, "mi_nn_pinv: block %d is not finite (mi_schur_setup_run met a singular or indefinite interior block)", d);
-    const bool inv_ok = std::isfinite(nS[d]) && std::isfinite(nZ[d]) && nZ[d] > 0.0 && 1.0 / nZ[d] > rtol * nS[d];
+    const bool inv_ok = std::isfinite(nS[d]) && std::isfinite(nZ[d]) && nZ[d] > 0.0 && 1.0 / nZ[d] > rtol * nS[d] &&
+                        probe_ok(n, nS[d], nZ[d], nR[d]);
     if (inv_ok) MI_HIP(hipMemcpyAsync(Pi + off[d], dm[d].Z[st[d].nb & 1], sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, s));
-    else if (std::isfinite(nS[d]) && nS[d] > 0.0 && nS1[d] <= rtol * nS[d] && !env_int("MI355_PINV_NO_SHIFT", 0)) {
+    // (max |S_ii| and ||S||_inf / sqrt(n) are both <= σ_max: an S 1 this small means pinv drops at least one eigenvalue)
+    else if (std::isfinite(nS[d]) && nS[d] > 0.0 && nS1[d] <= rtol * std::max(nD[d], nS[d] / std::sqrt((double)n)) &&
+             !env_int("MI355_PINV_NO_SHIFT", 0)) {
       floating.push_back(d);
       shift.push_back(nS[d] / n);                  // α u u' with α = ||S||_inf, u = 1/sqrt(n): every entry + α / n
     } else slow.push_back(d);
   }
   if (!floating.empty()) {
     MI_HIP(hipStreamSynchronize(s));               // the copies out of Z above
-    std::vector<double> nS2, nZ2, nS12;
-    batch(floating, shift, nS2, nZ2, nS12);
+    std::vector<double> nS2, nZ2, nS12, nD2, nR2;
+    batch(floating, shift, nS2, nZ2, nS12, nD2, nR2);
     for (size_t k = 0; k < floating.size(); ++k) {
       const int d = floating[k], n = (int)n_gamma_d[d];
       const double alpha = shift[k] * n;
-      const bool ok = std::isfinite(nZ2[d]) && nZ2[d] > 0.0 && 1.0 / nZ2[d] > rtol * nS[d];   // every eigenvalue of S + α u u' above the cut-off
+      // every eigenvalue of S + α u u' above the cut-off, and u close enough to the eigenvector that is dropped
+      const bool ok = std::isfinite(nZ2[d]) && nZ2[d] > 0.0 && 1.0 / nZ2[d] > rtol * nS[d] && nS1[d] * nZ2[d] <= rtol &&
+                      probe_ok(n, 2.0 * nS[d], nZ2[d], nR2[d]);   // (||S + α u u'||_inf <= ||S||_inf + α = 2 ||S||_inf)
       if (ok) hipLaunchKernelGGL(k_copy_add_const, dim3(std::min(4096, cdiv(n * n, 256))), dim3(256), 0, s, (long long)n * n,
                                  (const double *)dm[d].Z[st[d].nb & 1], Pi + off[d], -1.0 / (alpha * n));   // - (1/α) u u'
       else slow.push_back(d);
