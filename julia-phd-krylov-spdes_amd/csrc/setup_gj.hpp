@@ -298,7 +298,7 @@ __device__ __forceinline__ void gj_inv4(const double (&m)[16], double (&p)[16]) 
 #ifndef GJ_STAMP
 #define GJ_STAMP(i)
 #endif
-__device__ __forceinline__ void gj_invert_block64(double *M, int LD, double *Rb) {
+__device__ __forceinline__ void gj_invert_block64(double *M, int LD, double *Rb, bool mirror) {
   constexpr int RL = 68;
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, lc = l & 15, lk = l >> 4;
 #pragma unroll 1
@@ -358,7 +358,12 @@ __device__ __forceinline__ void gj_invert_block64(double *M, int LD, double *Rb)
     __syncthreads();
     GJ_STAMP(5);
   }
-  // symmetric to the last bit (the update kernels read P as symmetric): mirror the upper triangle
+  // `mirror` (the block is the whole matrix, P the result): symmetric to the last bit, the upper triangle mirrored. NOT when
+  // P feeds further block steps: the two triangles of an unpivoted Gauss-Jordan inverse carry errors of order κ eps that
+  // cancel in the next Schur complement D - B' (P B) only as computed; with one triangle replaced by the other that
+  // complement loses up to κ² eps (|Z - T^-1| / |T^-1| = 0.41 at κ = 1e8, n = 65, instead of 7e-5; the update kernels
+  // read P[t][k] as stored, they do not assume it symmetric).
+  if (!mirror) return;
   for (int e = threadIdx.x; e < 64 * 64; e += 256) {
     const int i = e >> 6, j = e & 63;
     if (j > i) M[j * LD + i] = M[i * LD + j];
@@ -368,8 +373,9 @@ __device__ __forceinline__ void gj_invert_block64(double *M, int LD, double *Rb)
 // in-place inverse of the SPD GJ_B x GJ_B block in LDS (row stride LD; identity beyond the matrix' end), 256 threads. GJ_B = 64:
 //   [A B; B' D]^{-1} = [P + Y X', -Y; -Y', S^{-1}],  P = A^{-1},  X = P B,  S = D - B' X,  Y = X S^{-1}
 // two 32-step register inversions (the serial part) and five 32 x 32 x 32 products; `W` = 32 x LD doubles of scratch, `scr` = 64 more.
-__device__ __forceinline__ void gj_invert_block(double *M, int LD, double *W, double *scr) {
-  if (GJ_B == 64 && !MI355_GJ_INV_RECURSIVE) { gj_invert_block64(M, LD, W); return; }
+// `whole`: the block is the whole matrix (one pivot block), its inverse the result (see gj_invert_block64).
+__device__ __forceinline__ void gj_invert_block(double *M, int LD, double *W, double *scr, bool whole) {
+  if (GJ_B == 64 && !MI355_GJ_INV_RECURSIVE) { gj_invert_block64(M, LD, W, whole); return; }
   if (GJ_B == 32) {
     gj_inv32(M, LD, 0, scr);
     __syncthreads();
@@ -447,7 +453,7 @@ __global__ __launch_bounds__(256) void k_gj_pivot(int step, int kb, int ndom, co
     Mb[r * LD + c] = (r < bs && c < bs) ? A[(k0 + r) + (size_t)(k0 + c) * n] : (r == c ? 1.0 : 0.0);
   }
   __syncthreads();
-  gj_invert_block(Mb, LD, Wb, Wb + GJ_H * LD);
+  gj_invert_block(Mb, LD, Wb, Wb + GJ_H * LD, st.nb == 1);
   double *Pd = dm.P + (kb & 1) * (GJ_B * GJ_B);
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) Pd[e] = Mb[(e % GJ_B) * LD + e / GJ_B];   // column-major GJ_B x GJ_B
 }
@@ -543,7 +549,7 @@ __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom
     }
     __syncthreads();
     GJ_KSTAMP(1);
-    gj_invert_block(&R[0][0], GJ_T + 1, lds + LDS_R, lds + LDS_R + (GJ_B == 32 ? 0 : GJ_H * (GJ_T + 1)));
+    gj_invert_block(&R[0][0], GJ_T + 1, lds + LDS_R, lds + LDS_R + (GJ_B == 32 ? 0 : GJ_H * (GJ_T + 1)), st.nb == 1);
     GJ_KSTAMP(2);
     double *Pw = dm.P + (kb & 1) * (GJ_B * GJ_B);
     for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) __hip_atomic_store(&Pw[e], R[e % GJ_B][e / GJ_B], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -705,7 +711,7 @@ __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom
     }
   __syncthreads();
   static_assert(LDS_CC >= GJ_H * (GJ_T + 1) + 64 || GJ_B == 32, "scratch of the block inversion lives in the Cc buffer");
-  gj_invert_block(&R[0][0], GJ_T + 1, lds + LDS_R, lds + LDS_R + (GJ_B == 32 ? 0 : GJ_H * (GJ_T + 1)));
+  gj_invert_block(&R[0][0], GJ_T + 1, lds + LDS_R, lds + LDS_R + (GJ_B == 32 ? 0 : GJ_H * (GJ_T + 1)), false);   // (block kb + 1 >= 1)
   GJ_KSTAMP(3);   // pivot block inverted
   double *Pn = dm.P + ((kb + 1) & 1) * (GJ_B * GJ_B);
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) Pn[e] = R[e % GJ_B][e / GJ_B];
@@ -957,19 +963,22 @@ inline void gj_set_keep(mi_setup_s &P, bool on) {
   if (!P.gj) gj_build(P);
   GjState &G = *P.gj;
   if (G.keep == on) return;
+  const int nd = P.ndom;
+  // refusals first: the plan stays as it was (a plan left with `keep` set and no level storage would copy into nothing)
+  if (on && G.nmax > LV_MAX) raise(MI_ERR_BAD_ARG, "level solves: a level of %d nodes exceeds the %d the back-substitution kernel stages", G.nmax, LV_MAX);
+  for (int d = 0; on && d < nd; ++d)
+    if (P.dom[d].nlev > 0 && P.dom[d].lev_off[P.dom[d].nlev] != P.dom[d].n_i)
+      raise(MI_ERR_BAD_ARG, "level solves: subdomain %d has interior nodes that are not connected to its interface", d);
   MI_HIP(hipStreamSynchronize(P.ctx->stream));
   for (auto &g : G.graph) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
   if (G.solve_graph) { (void)hipGraphExecDestroy(G.solve_graph); G.solve_graph = nullptr; }
   G.keep = on; G.have_levels = false;
   if (!on) { G.zstore.release(); G.gstore.release(); G.ustore.release(); G.sv_in.release(); G.sv_out.release(); return; }
-  if (G.nmax > LV_MAX) raise(MI_ERR_BAD_ARG, "level solves: a level of %d nodes exceeds the %d the back-substitution kernel stages", G.nmax, LV_MAX);
-  const int nd = P.ndom;
   long long ztot = 0;
   std::vector<int> rp, rc, rs;
   for (int d = 0; d < nd; ++d) {
     const SetupDom &D = P.dom[d];
     if (D.nlev == 0) continue;
-    if (D.lev_off[D.nlev] != D.n_i) raise(MI_ERR_BAD_ARG, "level solves: subdomain %d has interior nodes that are not connected to its interface", d);
     for (int k = 0; k < D.nlev; ++k) {
       GjStep &st = G.steps_h[(size_t)(G.nsteps - 1 - k) * nd + d];
       st.zoff = ztot;
@@ -1232,7 +1241,9 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
   std::vector<double> nS, nZ, nS1, nD, nR, zero(ndom, 0.0);
   batch(all, zero, nS, nZ, nS1, nD, nR);
   // The certificates below test the computed inverse Z, so they say nothing about its accuracy: without pivoting the block
-  // Gauss-Jordan kernels lose accuracy much faster than κ eps beyond κ ~ 1e5 (measured: 41 % at κ = 1e8, n = 65). A good
+  // Gauss-Jordan kernels can lose accuracy faster than κ eps: the Schur complement of a short trailing pivot block is formed
+  // from the explicit inverse of the block before it (measured: 1e-4 at κ = 1e8, n = 65; 41 % while the pivot inverses
+  // were mirrored to symmetry, see gj_invert_block64). A good
   // inverse has |I - Z T| <= c n eps |Z| |T| entry-wise, so ||v - Z T v||_inf <= c n eps ||Z||_inf ||T||_inf for v = ±1;
   // a result whose probe residual exceeds that (c = PROBE_C) is not used, and the block goes to the next route.
   constexpr double PROBE_C = 4.0;

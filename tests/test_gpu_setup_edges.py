@@ -1,0 +1,291 @@
+"""GPU suite (-m gpu): the device Schur set-up (`mi_schur_setup_run`, setup_gj.hpp) at the level widths, coupling degrees,
+plan shapes and condition numbers the FEM meshes never produce, against the long-double reference of tests/setup_synth.py.
+
+Bar (every comparison): err / scale <= C κ_max n eps, C = 50 (the pinv tests' constant), κ_max = the subdomain's largest
+κ(T_k), n = its largest level width; for S_d err = max |S_dev - S_ref| and scale = max |A_IΓ' A_II^-1 A_IΓ|, for w_d and
+interior_solve the largest entry of the reference. Where κ_max <= 1e4 also err / scale <= 1e-12. Every ratio is printed.
+
+The Gauss-Jordan inversion without pivoting forms the Schur complement of a pivot block from that block's explicit inverse,
+so it is not backward stable: where the trailing pivot block is short (n0 = 65: one row) and κ is large, the ALGORITHM
+alone exceeds the bar (its numpy copy, setup_synth.gj_emulate: err/(κ n eps) up to ~70 at n0 = 65, κ = 1e8). The
+direct-inverse cases are therefore held to the bar OR to 4 x the error of that copy on the same matrix, whichever is
+larger: the kernels must be as accurate as the algorithm they implement. Every such case prints both."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import f_m1, u0734
+import setup_synth as ss
+
+pytestmark = pytest.mark.gpu
+
+C = 50.0
+N0S = [1, 2, 31, 32, 33, 63, 64, 65, 96, 127, 128, 129, 193, 257]
+KAPPAS = [10.0, 1e4, 1e6, 1e8]
+_REF = {}
+
+
+def ref_of(s):
+    if s.tag not in _REF:
+        _REF[s.tag] = ss.reference(s)
+    return _REF[s.tag]
+
+
+def make_setup(api, ctx, cases):
+    return api.SchurSetup(ctx, [c.A_II for c in cases], [c.A_IΓ for c in cases], [c.A_ΓΓ for c in cases])
+
+
+def run(setup, cases, values=None):
+    """-> (S_d blocks, w_d pieces) of one run with b_I; `values`: (ii, ig, gg) of another realization."""
+    b = np.concatenate([c.b_I for c in cases])
+    Sd, w = setup.run(*(values or (None, None, None)), b_I=b)
+    ng = [c.A_ΓΓ.shape[0] for c in cases]
+    return ss.split_blocks(Sd, ng), ss.split_vec(w, ng)
+
+
+def emulated(c):
+    """(S_d, w_d) relative errors of the numpy copy of the device's inversion, for a direct-inverse case (B = I)."""
+    if c.tag not in _EMU:
+        ref = ref_of(c)
+        Z = ss.gj_emulate(c.A_II.toarray())
+        _EMU[c.tag] = (np.max(np.abs(c.A_ΓΓ.toarray() - Z - ref.S)) / ref.S_scale, np.max(np.abs(Z @ c.b_I - ref.w)) / np.max(np.abs(ref.w)))
+    return _EMU[c.tag]
+
+
+_EMU = {}
+
+
+def ratio(tag, what, got, want, scale, ref, emu=None):
+    err = float(np.max(np.abs(np.asarray(got) - want))) if np.size(want) else 0.0
+    rel = err / scale if scale > 0 else err
+    unit = ref.kappa * max(ref.nmax, 1) * ss.EPS
+    r = rel / unit
+    extra = "" if emu is None else f", algorithm (numpy copy) {emu / unit:.3e}"
+    print(f"{tag}: {what} err/(κ n eps) = {r:.3e}  (κ_max {ref.kappa:.2e}, n {ref.nmax}, relative {rel:.2e}{extra})")
+    assert np.all(np.isfinite(got)), (tag, what)
+    allow = 0.0 if emu is None else 4.0 * emu
+    assert r <= C or rel <= allow, (tag, what, r)
+    if ref.kappa <= 1e4:
+        assert rel <= max(1e-12, allow), (tag, what, rel)
+    return r
+
+
+def check_case(tag, c, S, w, u=None):
+    ref = ref_of(c)
+    if c.A_II.shape[0] == 0:                                   # n_I = 0: S_d = A_ΓΓ to the bit, w_d = 0
+        assert np.array_equal(S, c.A_ΓΓ.toarray()) and not np.any(w)
+        print(f"{tag}: n_I = 0, S_d == A_ΓΓ exactly")
+        return 0.0
+    eS, ew = emulated(c) if c.tag.startswith("direct") else (None, None)
+    r = ratio(tag, "S_d", S, ref.S, ref.S_scale, ref, eS)
+    r = max(r, ratio(tag, "w_d", w, ref.w, np.max(np.abs(ref.w)), ref, ew))
+    if u is not None:
+        r = max(r, ratio(tag, "interior_solve", u, ref.u, np.max(np.abs(ref.u)), ref))
+    return r
+
+
+# ------------------------------------------------------------------ the direct-inverse family: S_d = 2 I - T^-1
+@pytest.mark.parametrize("kappa", KAPPAS)
+def test_direct_inverse_family(pkg, ctx, kappa):
+    """One level T = Q diag(geomspace(1, κ)) Q' at every width around the 32 / 64 edges, alone and in one mixed plan:
+    the pivot-block inversions, look-ahead and one-row trailing blocks exposed directly. A subdomain's S_d is bitwise the
+    same alone and in the mixed plan (subdomains are independent along grid.z)."""
+    api = pkg.api
+    cases = [ss.direct_inverse(n0, kappa) for n0 in N0S]
+    mixed = make_setup(api, ctx, cases)
+    Sm, wm = run(mixed, cases)
+    worst = 0.0
+    for k, c in enumerate(cases):
+        one = make_setup(api, ctx, [c])
+        S1, w1 = run(one, [c])
+        one.close()
+        assert np.array_equal(S1[0], Sm[k]), c.tag
+        assert np.array_equal(w1[0], wm[k]), c.tag
+        worst = max(worst, check_case(c.tag, c, Sm[k], wm[k]))
+    mixed.close()
+    print(f"direct inverse κ={kappa:g}: largest ratio {worst:.3e}")
+
+
+# ------------------------------------------------------------------ ladders
+def ladders(value_seed=None):
+    L = lambda *a, **k: ss.ladder(*a, value_seed=value_seed, **k)   # noqa: E731
+    tag = "" if value_seed is None else f" values {value_seed}"
+    return [
+        L([65, 64, 1, 33, 128, 2], degree=[1, 4, 5, 12], density=0.05, n_gamma=17, gamma_deg=3, seed=1, contrast=1e2, tag="edges A" + tag),
+        L([129, 63, 257], degree=4, density=0.01, n_gamma=300, gamma_deg=2, seed=2, tag="edges B" + tag),
+        L([6, 9, 5, 7, 8, 6, 9, 4, 6, 7, 5, 3], degree=1, n_gamma=15, seed=3, shift=0.05, tag="12 deep" + tag),
+        L([40], degree=1, density=0.1, n_gamma=16, gamma_deg=4, seed=4, tag="one level" + tag),
+        L([64, 96, 65], degree=5, density=0.02, n_gamma=1, gamma_deg=1, seed=5, contrast=10.0, tag="n_Γ 1, degree 5" + tag),
+        L([33, 200, 129], degree=12, density=0.02, n_gamma=16, gamma_deg=4, seed=6, tag="degree 12" + tag),
+        ss.empty_interior(5),
+    ]
+
+
+def test_ladders(pkg, ctx):
+    """Level widths across the 64 edges, a 12-level subdomain in the plan of a one-level one, coupling degrees 1 / 4 /
+    5 / 12 (both paths of k_gj_pick), n_Γ 1 / 15 / 16 / 17 / 300 and an n_I = 0 subdomain: S_d, w_d and, after
+    keep_levels(True), interior_solve."""
+    api = pkg.api
+    cases = ladders()
+    setup = make_setup(api, ctx, cases)
+    S, w = run(setup, cases)
+    setup.keep_levels(True)
+    Sk, wk = run(setup, cases)
+    u = ss.split_vec(setup.interior_solve(np.concatenate([c.f for c in cases])), [c.A_II.shape[0] for c in cases])
+    worst = 0.0
+    for k, c in enumerate(cases):
+        assert np.array_equal(Sk[k], S[k]) and np.array_equal(wk[k], w[k]), c.tag   # keep_levels on == off
+        worst = max(worst, check_case(c.tag, c, S[k], w[k], u[k] if c.A_II.shape[0] else None))
+    setup.close()
+    print(f"ladders: largest ratio {worst:.3e}")
+
+
+def test_interior_island_is_ignored_and_refused(pkg, ctx):
+    """An interior component that does not touch Γ cannot influence S_d or w_d; the level solves cannot reach it, so
+    keep_levels(True) is refused (MI_ERR_BAD_ARG) and the plan stays usable as it was."""
+    api = pkg.api
+    cases = [ss.ladder([33, 70, 20], degree=[1, 5], density=0.05, n_gamma=17, gamma_deg=2, seed=8, island=9, tag="island"),
+             ss.ladder([30, 10], degree=2, n_gamma=16, seed=9, tag="island's neighbour")]
+    setup = make_setup(api, ctx, cases)
+    S, w = run(setup, cases)
+    for k, c in enumerate(cases):
+        check_case(c.tag, c, S[k], w[k])
+    with pytest.raises(pkg._lib.MiError) as e:
+        setup.keep_levels(True)
+    assert e.value.code == -1                                                  # MI_ERR_BAD_ARG
+    S2, w2 = run(setup, cases)
+    for k in range(len(cases)):
+        assert np.array_equal(S2[k], S[k]) and np.array_equal(w2[k], w[k])
+    setup.close()
+
+
+def test_level_solve_limit(pkg, ctx):
+    """LV_MAX = 2048: a level of exactly 2048 nodes (sparse inside the level) solves; one of 2049 is refused."""
+    api = pkg.api
+    c = ss.ladder([64, 2048], degree=1, density=0.002, n_gamma=40, gamma_deg=2, seed=10, tag="level 2048")
+    setup = make_setup(api, ctx, [c])
+    setup.keep_levels(True)
+    S, w = run(setup, [c])
+    u = setup.interior_solve(c.f)
+    check_case(c.tag, c, S[0], w[0], u)
+    setup.close()
+    c2 = ss.ladder([64, 2049], degree=1, density=0.002, n_gamma=40, gamma_deg=2, seed=10, tag="level 2049")
+    setup = make_setup(api, ctx, [c2])
+    with pytest.raises(pkg._lib.MiError) as e:
+        setup.keep_levels(True)
+    assert e.value.code == -1
+    setup.close()
+
+
+# ------------------------------------------------------------------ variants: bitwise equal to the default run
+def test_variants_bitwise(pkg, ctx, monkeypatch):
+    """MI355_SETUP_NO_GRAPH=1 (plain launches) and a plan run with values B after values A give the bits of the default
+    (graph) run of a fresh plan with B: no stale ping-pong buffer, pivot half or ready flag survives a run."""
+    api = pkg.api
+    A = ladders() + [ss.direct_inverse(65, 1e4), ss.direct_inverse(129, 1e6)]
+    B = ladders(value_seed=1234) + [ss.direct_inverse(65, 1e4, seed=3), ss.direct_inverse(129, 1e6, seed=4)]
+    for c in B[-2:]:
+        c.tag += " (other Q)"
+    fresh = make_setup(api, ctx, B)
+    SB, wB = run(fresh, B)
+    fresh.close()
+    reused = make_setup(api, ctx, A)
+    run(reused, A)
+    vals = (np.concatenate([c.A_II.data for c in B]), np.concatenate([c.A_IΓ.data for c in B]),
+            np.concatenate([c.A_ΓΓ.data for c in B]))
+    SR, wR = run(reused, B, vals)
+    monkeypatch.setenv("MI355_SETUP_NO_GRAPH", "1")
+    SN, wN = run(reused, B, vals)
+    nograph = make_setup(api, ctx, B)
+    SN2, wN2 = run(nograph, B)
+    nograph.close()
+    reused.close()
+    for k, c in enumerate(B):
+        for S_, w_ in ((SR, wR), (SN, wN), (SN2, wN2)):
+            assert np.array_equal(S_[k], SB[k]) and np.array_equal(w_[k], wB[k]), c.tag
+        check_case(c.tag, c, SB[k], wB[k])
+
+
+# ------------------------------------------------------------------ head-of-launch pivots (child process)
+CHILD = r"""
+import sys, numpy as np
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import __graft_entry__ as g
+from test_gpu_setup_edges import head_cases
+api = g.load_package().api
+ctx = api.Context(0)
+cases = head_cases()
+setup = api.SchurSetup(ctx, [c.A_II for c in cases], [c.A_IΓ for c in cases], [c.A_ΓΓ for c in cases])
+Sd, w = setup.run(b_I=np.concatenate([c.b_I for c in cases]))
+np.savez({out!r}, Sd=Sd, w=w)
+"""
+
+
+def head_cases():
+    return ladders()[:-1] + [ss.direct_inverse(n0, k) for n0 in (33, 64, 65, 129, 257) for k in (1e4, 1e8)]
+
+
+def test_head_of_launch_pivots(pkg, ctx, tmp_path):
+    """MI355_GJ_HEAD_MAXN (read once per process) in a child process: the pivot block inverted at the head of each update
+    launch, the other tiles waiting for its flag. Same bar; bitwise equality with the look-ahead form is reported, not
+    required. A non-finite result would be the bounded wait giving up (a finding, not something to retry)."""
+    api = pkg.api
+    cases = head_cases()
+    out = tmp_path / "head.npz"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, MI355_GJ_HEAD_MAXN=str(1 << 30))
+    code = CHILD.format(root=root, tests=os.path.join(root, "tests"), out=str(out))
+    p = subprocess.run([sys.executable, "-c", code], env=env, timeout=300, capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    got = np.load(out)
+    ng = [c.A_ΓΓ.shape[0] for c in cases]
+    Sh, wh = ss.split_blocks(got["Sd"], ng), ss.split_vec(got["w"], ng)
+    setup = make_setup(api, ctx, cases)
+    S, w = run(setup, cases)
+    setup.close()
+    same = 0
+    worst = 0.0
+    for k, c in enumerate(cases):
+        worst = max(worst, check_case("HEAD " + c.tag, c, Sh[k], wh[k]))
+        same += bool(np.array_equal(Sh[k], S[k]) and np.array_equal(wh[k], w[k]))
+    print(f"head-of-launch pivots: largest ratio {worst:.3e}; bitwise equal to look-ahead in {same} of {len(cases)} subdomains")
+
+
+# ------------------------------------------------------------------ FEM at high contrast
+def _two_valued(points, contrast=1e6):
+    x, y = points
+    inc = np.zeros(x.shape, dtype=bool)
+    for cx, cy, r in ((0.3, 0.3, 0.12), (0.7, 0.55, 0.15), (0.35, 0.75, 0.1), (0.62, 0.2, 0.08)):
+        inc |= (x - cx) ** 2 + (y - cy) ** 2 <= r * r
+    return np.where(inc, contrast, 1.0)
+
+
+@pytest.mark.parametrize("coef", ["lognormal sig2=4", "inclusions 1e6"])
+def test_fem_high_contrast(pkg, ctx, fem, coef):
+    """fem.build_schur_problem(50, 3, 3) with a lognormal coefficient of variance 4 and with a two-valued field of
+    contrast 1e6 (inclusions): S_d, w_d and interior_solve of every subdomain to the κ bar."""
+    api = pkg.api
+    mesh = fem.get_mesh(50)
+    if coef.startswith("lognormal"):
+        kl = fem.synthetic_kl(mesh.points, sig2=4.0)
+        _, g = fem.draw(kl, np.random.default_rng(5))
+        a = np.exp(g)
+    else:
+        a = _two_valued(mesh.points)
+    P = fem.build_schur_problem(50, 3, 3, a, f_m1, u0734)
+    rng = np.random.default_rng(6)
+    cases = []
+    for d in range(P.sub.ndom):
+        lv = [len(l) for l in ss.bfs_levels(P.A_IIdd[d], P.A_IΓdd[d])]
+        cases.append(ss.Synth(P.A_IIdd[d], P.A_IΓdd[d], P.A_ΓΓdd[d], np.asarray(P.b_Id[d], dtype=np.float64),
+                              rng.standard_normal(P.A_IIdd[d].shape[0]), lv, f"FEM {coef} d={d}"))
+    setup = make_setup(api, ctx, cases)
+    setup.keep_levels(True)
+    S, w = run(setup, cases)
+    u = ss.split_vec(setup.interior_solve(np.concatenate([c.f for c in cases])), [c.A_II.shape[0] for c in cases])
+    setup.close()
+    worst = max(check_case(c.tag, c, S[k], w[k], u[k]) for k, c in enumerate(cases))
+    print(f"FEM {coef}: largest ratio {worst:.3e}, largest κ(T_k) {max(ref_of(c).kappa for c in cases):.3e}")

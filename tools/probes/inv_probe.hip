@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void k_probe(const double *A, double *out, lon
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) Mb[(e % GJ_B) * LD + e / GJ_B] = A[e];
   __syncthreads();
   long long t3 = wall_clock64();
-  gj_invert_block(Mb, LD, Wb, Wb + GJ_H * LD);
+  gj_invert_block(Mb, LD, Wb, Wb + GJ_H * LD, true);
   long long t4 = wall_clock64();
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) out[e] = Mb[(e % GJ_B) * LD + e / GJ_B];
   if (threadIdx.x == 0) { stamps[0] = t1 - t0; stamps[1] = t2 - t1; stamps[2] = t4 - t3; }
