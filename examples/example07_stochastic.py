@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Example07_PcgSchurStochasticEllipticPde.jl (lines 56-285) on the MI355X drop-in — BASELINE config 5.
+"""Example07_PcgSchurStochasticEllipticPde.jl (lines 56-285; with --gg also the second loop, 290-424) on the MI355X
+drop-in — BASELINE config 5.
 
 For every realization ξ_t of the lognormal coefficient: rebuild the local blocks, b_schur, the assembled
 S_d and NN_t on the host (as the reference does), then on the GPU
@@ -13,7 +14,12 @@ S_d and NN_t on the host (as the reference does), then on the GPU
                                                         eigdefpcg with the W the previous solve returned
                                                         (Example09_..._Functions.jl:345, 364; nvec = 1.25 ndom,
                                                         spdim = 3 ndom), the chain being per rank
-and record the iteration counts. Realizations are independent: under torch.distributed.run each rank takes
+and record the iteration counts. With --gg, also the second loop's solves preconditioned by the interface block itself
+    pcg(S, b_schur, 0, A_ΓΓ_0)        (Example07:412)   A_ΓΓ of the ξ = 0 operator
+    pcg(S, b_schur, 0, A_ΓΓ_t)        (Example07:416)   A_ΓΓ of this realization
+with `M \\ r` by the device sparse direct solve (api.SparseDirectPreconditioner, refilled per realization by set_values:
+from `prepare_global_schur` on the host, or with --device-setup from the device assembly through fem.gamma_gather_map).
+Realizations are independent: under torch.distributed.run each rank takes
 realizations rank, rank+world, ... on its own GPU (replicas only, no collective in the solve).
 
 With --device-assembly the element loop of `prepare_local_schurs` (Example07:162-171, redone per realization by the
@@ -28,6 +34,7 @@ import os
 import sys
 
 import numpy as np
+import scipy.sparse as sp
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as graft  # noqa: E402
@@ -46,6 +53,7 @@ def main():
                     help="with --device-assembly: S_d, the condensed rhs and NN_t on the device too (mi_schur_setup_run, mi_nn_pinv, "
                          "mi_dense_set_blocks): nothing of a realization's set-up runs on the host")
     ap.add_argument("--recycle", action="store_true")
+    ap.add_argument("--gg", action="store_true", help="also pcg(S, b_schur, 0, A_ΓΓ_0) and pcg(S, b_schur, 0, A_ΓΓ_t) (Example07:412, 416)")
     args = ap.parse_args()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     pkg = graft.load_package()
@@ -78,7 +86,16 @@ def main():
         setup = api.SchurSetup(ctx, P0.A_IIdd, P0.A_IΓdd, P0.A_ΓΓdd)
         S_dev = api.LocalSchurs(ctx, P0.Sd, sub.gather_idx, sub.node_Γ_cnt)
         NN_dev = api.NeumannNeumannSchurPreconditioner(ctx, P0.ΠSd, sub.gather_idx, sub.node_Γ_cnt)
-    iters_0, iters_t, iters_def, iters_rec = [], [], [], []
+    M_gg0 = M_ggt = gmap = None
+    if args.gg:   # Example07:290-300: A_ΓΓ_0 of the ξ = 0 operator; A_ΓΓ_t on the same pattern, refilled per realization
+        A_gg0 = sp.csc_matrix(fem.prepare_global_schur(mesh.cells, mesh.points, P0.epart, sub, np.exp(0 * gs[0]), f, uexact)[2])
+        A_gg0.sort_indices()
+        M_gg0 = api.SparseDirectPreconditioner(ctx, A_gg0)
+        M_ggt = api.SparseDirectPreconditioner(ctx, A_gg0)
+        if args.device_setup:
+            gmap = fem.gamma_gather_map(plan.patterns["ΓΓ"], sub.gather_idx, n_Γ, offsets=[o for o, _ in plan.layout["ΓΓ"]])
+            assert np.array_equal(gmap.indptr, A_gg0.indptr) and np.array_equal(gmap.indices, A_gg0.indices)
+    iters_0, iters_t, iters_def, iters_rec, iters_gg0, iters_ggt = [], [], [], [], [], []
     W_rec, nvec, spdim = None, int(1.25 * ndom), 3 * ndom
     for ireal in range(rank, args.nreals, world):
         if setup is not None:
@@ -94,6 +111,8 @@ def main():
                 b_schur[sub.gather_idx[d]] -= wh[off:off + sub.n_Γd[d]]
                 off += sub.n_Γd[d]
             S, ΠSnn_t = S_dev, NN_dev
+            if M_ggt is not None:
+                M_ggt.set_values(gmap.values(vals))                                                    # A_ΓΓ_t = Σ_d R_d' A_ΓΓdd R_d
         else:
             blocks = plan.blocks(dev_plan.run(np.exp(gs[ireal]))) if plan else None                   # :162-171 on the GPU
             P = fem.build_schur_problem(args.N, args.px, args.py, np.exp(gs[ireal]), f, uexact, mesh=mesh,
@@ -101,6 +120,10 @@ def main():
             S = api.LocalSchurs(ctx, P.Sd, sub.gather_idx, sub.node_Γ_cnt)
             ΠSnn_t = api.NeumannNeumannSchurPreconditioner(ctx, P.ΠSd, sub.gather_idx, sub.node_Γ_cnt)
             b_schur = P.b_schur
+            if M_ggt is not None:
+                A_ggt = sp.csc_matrix(fem.prepare_global_schur(mesh.cells, mesh.points, P0.epart, sub, np.exp(gs[ireal]), f, uexact)[2])
+                A_ggt.sort_indices()
+                M_ggt.set_values(A_ggt.data)
         x0 = np.zeros(n_Γ)
         iters_0.append(api.pcg(S, b_schur, x0, ΠSnn_0)[1])                                            # :273
         iters_t.append(api.pcg(S, b_schur, x0, ΠSnn_t)[1])                                            # :277
@@ -117,11 +140,18 @@ def main():
             except (api.BoundsError, api.SingularException) as e:          # Example09:355-375: status = -1
                 rec = f"  recycling stopped: {type(e).__name__}"
                 W_rec = None
+        gg = ""
+        if M_gg0 is not None:
+            iters_gg0.append(api.pcg(S, b_schur, x0, M_gg0)[1])                                       # :412
+            iters_ggt.append(api.pcg(S, b_schur, x0, M_ggt)[1])                                       # :416
+            gg = f"  pcg(A_GG_0) it={iters_gg0[-1]}  pcg(A_GG_t) it={iters_ggt[-1]}"
         print(f"[rank {rank}] realization {ireal}: pcg(NN_0) it={iters_0[-1]}  pcg(NN_t) it={iters_t[-1]}  "
-              f"defpcg(W_0, NN_0) it={iters_def[-1]}{rec}", flush=True)
+              f"defpcg(W_0, NN_0) it={iters_def[-1]}{rec}{gg}", flush=True)
     if args.out:                                                                                       # :281-285 npz of iteration counts
-        np.savez(args.out.format(rank=rank), iters_0=iters_0, iters_t=iters_t, iters_def=iters_def, iters_rec=iters_rec)
-    print(f"[rank {rank}] mean its: NN_0 {np.mean(iters_0):.1f}  NN_t {np.mean(iters_t):.1f}  def {np.mean(iters_def):.1f}")
+        np.savez(args.out.format(rank=rank), iters_0=iters_0, iters_t=iters_t, iters_def=iters_def, iters_rec=iters_rec,
+                 iters_gg0=iters_gg0, iters_ggt=iters_ggt)                                          # (:423-424: io.save_pcg_iters(..., precond="A_GG"))
+    print(f"[rank {rank}] mean its: NN_0 {np.mean(iters_0):.1f}  NN_t {np.mean(iters_t):.1f}  def {np.mean(iters_def):.1f}"
+          + (f"  A_GG_0 {np.mean(iters_gg0):.1f}  A_GG_t {np.mean(iters_ggt):.1f}" if iters_gg0 else ""))
 
 
 if __name__ == "__main__":

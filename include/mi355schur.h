@@ -142,6 +142,25 @@ int mi_csr_create(mi_ctx_t ctx, int64_t n_rows, int64_t n_cols, const int64_t *r
  * (Example01's AMG preconditioner is out of scope; Jacobi / none stand in). */
 int mi_diag_create(mi_ctx_t ctx, int64_t n, const double *dinv, mi_op_t *op);
 
+/* mi_spd_direct_create — `M \ r` for a sparse SPD `M::SparseMatrixCSC{Float64,Int64}`: RecyclingKrylovSolvers' pcg applies
+ * its preconditioner as `z .= M \ r` (cg.jl:85, 100), a sparse Cholesky solve per call in Julia; Example07:412/416 pass
+ * the interface block itself, `pcg(S, b_schur, zeros(S.N), A_ΓΓ)`. Exact, by one level of nested dissection for an
+ * interface-like graph: pieces of at most 64 nodes grown breadth-first, a separator Σ from a greedy vertex cover of the
+ * edges between pieces, dense inverses of the pieces' diagonal blocks and of the Schur complement s of Σ, all formed on the
+ * device (no atomics: bitwise reproducible). The apply is two launches and is captured into the solvers' graphs.
+ *   create    : colptr (n + 1), rowval, nzval (nnz) of the CSC matrix, HOST arrays, `index_base`-based indices. The pattern
+ *               must be structurally symmetric without duplicates. |Σ| above 2048 (s^-1 would exceed 32 MB: the graph is not
+ *               interface-like) is MI_ERR_BAD_ARG naming both numbers. Recursive dissection is not provided.
+ *   set_values: new nzval on the same pattern (a new realization, Example07:416), host or device pointer per the context's
+ *               pointer mode; only the numeric phase runs again. Synchronous.
+ *   Both return MI_ERR_SINGULAR when a pivot is not positive (M not positive definite) or the certificate of s^-1 fails
+ *   (||v - s^-1 s v||_inf > 4 |Σ| eps ||s^-1||_inf ||s||_inf, v = ±1); set_values then keeps the previous factor.
+ * mi_spd_direct_stats — the number of pieces and |Σ| (either pointer may be NULL). */
+int mi_spd_direct_create(mi_ctx_t ctx, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval,
+                         int index_base, mi_op_t *op);
+int mi_spd_direct_set_values(mi_op_t op, const double *nzval);
+int mi_spd_direct_stats(mi_op_t op, int64_t *pieces, int64_t *separator);
+
 /* mi_schur_assembled_create — `apply_local_schurs(Sd, ind_Γd_Γ2l, node_Γ_cnt, x)`, EPDD.jl:761-785:
  * Sx = Σ_d R_d' S_d R_d x with dense local Schur complements.
  *   Sd[d]          n_gamma_d[d]^2 doubles, column-major (Julia `Array(Sd[d])`)

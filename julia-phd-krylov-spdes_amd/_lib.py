@@ -46,6 +46,9 @@ SIGNATURES = {
     "mi_ctx_allreduce_sum": [vp, vp, i64],
     "mi_csr_create": [vp, i64, i64, i64p, i64p, f64p, C.c_int, C.POINTER(vp)],
     "mi_diag_create": [vp, i64, f64p, C.POINTER(vp)],
+    "mi_spd_direct_create": [vp, i64, i64p, i64p, f64p, C.c_int, C.POINTER(vp)],
+    "mi_spd_direct_set_values": [vp, vp],
+    "mi_spd_direct_stats": [vp, i64p, i64p],
     "mi_schur_assembled_create": [vp, i64, i64, i64p, i64pp, f64pp, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_nn_create": [vp, i64, i64, i64p, i64pp, f64pp, i64p, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_schur_matfree_create": [vp, i64, i64, i64p, i64p, i64pp, i64pp, i64pp, f64pp, i64pp, i64pp, f64pp,

@@ -393,6 +393,44 @@ def JacobiPreconditioner(ctx: Context, diag) -> Operator:
     return Operator(ctx, h)
 
 
+class SparseDirectPreconditioner(Operator):
+    """`M \\ r` for a sparse SPD `M::SparseMatrixCSC` (cg.jl:85, 100): Example07:412/416 `pcg(S, b_schur, 0, A_ΓΓ)`.
+    Exact, factored on the device by one level of nested dissection (`mi_spd_direct_create`). `A` is a scipy sparse matrix
+    or a (colptr, rowval, nzval, n) tuple of CSC arrays; the pattern must be structurally symmetric. `.stats` =
+    (pieces, |Σ|)."""
+
+    def __init__(self, ctx: Context, A, index_base: int = 0):
+        if isinstance(A, tuple):
+            ptr, idx, val, n = A
+            ptr, idx, val = _i64(ptr), _i64(idx), _f64(val)
+        else:
+            A = sp.csc_matrix(A)
+            A.sum_duplicates()
+            A.sort_indices()
+            n = A.shape[0]
+            if A.shape[0] != A.shape[1]:
+                raise ValueError("square matrix expected")
+            ptr, idx, val = _i64(A.indptr), _i64(A.indices), _f64(A.data)
+        h = vp()
+        check(ctx._L.mi_spd_direct_create(ctx._h, i64(n), ptr.ctypes.data_as(i64p), idx.ctypes.data_as(i64p),
+                                          val.ctypes.data_as(f64p), C.c_int(index_base), C.byref(h)))
+        super().__init__(ctx, h)
+        self.nnz = int(val.size)
+
+    def set_values(self, nzval) -> None:
+        """New values on the pattern of construction (CSC order): numpy array or torch CUDA tensor (`mi_spd_direct_set_values`)."""
+        self.ctx._mode_for(nzval)
+        k, p = self.ctx._ptr(nzval, self.nnz)
+        self.ctx._order((k,), after=False)         # values made by torch kernels are complete before the factorisation reads them
+        check(self.ctx._L.mi_spd_direct_set_values(self._h, p))   # synchronous
+
+    @property
+    def stats(self):
+        a, b = i64(), i64()
+        check(self.ctx._L.mi_spd_direct_stats(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+
 def _dom_slice(ctx: Context, ndom: int, dom_slice):
     if dom_slice is None:
         return shard_domains(ndom, ctx.rank, ctx.n_ranks)

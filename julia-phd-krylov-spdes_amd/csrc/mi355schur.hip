@@ -6,6 +6,7 @@
 
 #include "eig_solvers.hpp"
 #include "setup_gj.hpp"
+#include "spd_direct.hpp"
 
 namespace mi {
 
@@ -515,6 +516,34 @@ int mi_csr_create(mi_ctx_t ctx, int64_t n_rows, int64_t n_cols, const int64_t *r
 int mi_diag_create(mi_ctx_t ctx, int64_t n, const double *dinv, mi_op_t *op) {
   if (n < 0 || n >= INT32_MAX) return fail(MI_ERR_BAD_ARG, "bad n");
   MI_NEW_OP(ctx, op, new DiagOp(ctx, n, dinv));
+}
+
+static SpdDirectOp *as_spd_direct(mi_op_t op) {
+  return op && op->impl ? dynamic_cast<SpdDirectOp *>(op->impl.get()) : nullptr;
+}
+int mi_spd_direct_create(mi_ctx_t ctx, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval,
+                         int index_base, mi_op_t *op) {
+  if (!nzval) return fail(MI_ERR_BAD_ARG, "mi_spd_direct_create: nzval is NULL");
+  MI_NEW_OP(ctx, op, new SpdDirectOp(ctx, n, colptr, rowval, nzval, index_base));
+}
+int mi_spd_direct_set_values(mi_op_t op, const double *nzval) {
+  SpdDirectOp *d = as_spd_direct(op);
+  if (!d || !nzval) return fail(MI_ERR_BAD_ARG, "mi_spd_direct_set_values: not a sparse direct preconditioner, or NULL nzval");
+  mi_ctx_s *c = d->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    DevBuf<double> st;
+    In vi(c, nzval, (size_t)d->nnz(), st);
+    d->factor(vi.dev);   // synchronous: a singular matrix is reported here
+    return MI_OK;
+  });
+}
+int mi_spd_direct_stats(mi_op_t op, int64_t *pieces, int64_t *separator) {
+  SpdDirectOp *d = as_spd_direct(op);
+  if (!d) return fail(MI_ERR_BAD_ARG, "mi_spd_direct_stats: not a sparse direct preconditioner");
+  if (pieces) *pieces = d->pl.n_pieces();
+  if (separator) *separator = d->pl.n_sigma();
+  return MI_OK;
 }
 
 int mi_schur_assembled_create(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d,

@@ -481,6 +481,78 @@ def prepare_global_schur(cells, points, epart, sub: Subdomains, coeff: Coeff, f,
 
 
 @dataclass
+class GammaGatherMap:
+    """A_ΓΓ = Σ_d R_d' A_ΓΓdd R_d as a gather: the CSC pattern of the global block (symmetric, so also its CSR arrays) and,
+    for every stored entry e, the flat indices `src[e, :]` of its local contributions in ascending subdomain order (padding
+    points past the end, at an appended zero). `values(v)` sums them in that fixed order — numpy or torch CUDA alike, no
+    scatter-add — so device-assembled values (`api.AssemblyPlan.run`) refresh A_ΓΓ_t without the host (Example07:416).
+    The sum is grouped by subdomain, `prepare_global_schur` groups by element: the two agree to rounding, not bit for bit."""
+    n: int
+    indptr: np.ndarray
+    indices: np.ndarray
+    src: np.ndarray        # (nnz, width) int64
+    n_src: int             # length of the flat value array the indices point into
+
+    def values(self, v):
+        if type(v).__module__.startswith("torch"):
+            import torch
+            src = getattr(self, "_src_t", None)
+            if src is None or src.device != v.device:
+                src = self._src_t = torch.as_tensor(self.src, device=v.device)
+            ext = torch.cat([v[:self.n_src], v.new_zeros(1)])
+            out = ext[src[:, 0]]
+            for c in range(1, src.shape[1]):
+                out = out + ext[src[:, c]]
+            return out
+        ext = np.concatenate([np.asarray(v, dtype=np.float64)[:self.n_src], [0.0]])
+        out = ext[self.src[:, 0]]
+        for c in range(1, self.src.shape[1]):
+            out = out + ext[self.src[:, c]]
+        return out
+
+    def matrix(self, v) -> sp.csc_matrix:
+        return sp.csc_matrix((np.asarray(self.values(v)), self.indices, self.indptr), shape=(self.n, self.n))
+
+
+def gamma_gather_map(patterns, gather_idx, n_Γ: int, offsets=None) -> GammaGatherMap:
+    """`patterns`: per subdomain A_ΓΓdd (scipy, Γ_d-local, symmetric) or its (indptr, indices, shape); `offsets`: where each
+    subdomain's nzval starts in the flat value array (default: the blocks back to back; `AssemblyPlan.layout["ΓΓ"]` offsets
+    make `values` read the output of an assembly run directly)."""
+    rows, cols, flat, dom = [], [], [], []
+    off = 0
+    n_src = 0
+    for d, pat in enumerate(patterns):
+        if sp.issparse(pat):
+            m = sp.csr_matrix(pat)
+            indptr, indices = m.indptr, m.indices
+        else:
+            indptr, indices = pat[0], pat[1]
+        o = off if offsets is None else int(offsets[d])
+        nnz = int(indptr[-1])
+        r = np.repeat(np.arange(len(indptr) - 1), np.diff(indptr))
+        g = np.asarray(gather_idx[d], dtype=np.int64)
+        rows.append(g[r]); cols.append(g[np.asarray(indices, dtype=np.int64)])
+        flat.append(o + np.arange(nnz, dtype=np.int64)); dom.append(np.full(nnz, d, dtype=np.int64))
+        off += nnz
+        n_src = max(n_src, o + nnz)
+    rows, cols, flat, dom = (np.concatenate(a) for a in (rows, cols, flat, dom))
+    order = np.lexsort((flat, dom, rows, cols))                 # CSC order: column, row; then subdomain
+    rows, cols, flat = rows[order], cols[order], flat[order]
+    new = np.ones(rows.size, dtype=bool)
+    new[1:] = (rows[1:] != rows[:-1]) | (cols[1:] != cols[:-1])
+    entry = np.cumsum(new) - 1
+    nE = int(entry[-1]) + 1 if entry.size else 0
+    first = np.flatnonzero(new)
+    rank = np.arange(rows.size) - first[entry]
+    width = int(rank.max()) + 1 if rank.size else 1
+    src = np.full((nE, width), n_src, dtype=np.int64)
+    src[entry, rank] = flat
+    indptr = np.zeros(n_Γ + 1, dtype=np.int64)
+    np.add.at(indptr, cols[first] + 1, 1)
+    return GammaGatherMap(n_Γ, np.cumsum(indptr), rows[first].astype(np.int64), src, n_src)
+
+
+@dataclass
 class AssemblyPlan:
     """The index half of `prepare_local_schurs` (EPDD.jl:389-546) for a FIXED mesh, partition, `f` and `uexact`: what
     Example07's realization loop (:162-171) recomputes for every coefficient draw although only `a` changes.

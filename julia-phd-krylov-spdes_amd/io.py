@@ -80,8 +80,10 @@ def load_partition(tentative_nnode: int, ndom: int, data_dir: str = "data"):
     return np.load(pe).astype(np.int64).ravel(), np.load(pn).astype(np.int64).ravel()
 
 
-def save_pcg_iters(iters, root_fname: str, ndom: int, tag: str, nreals: int, data_dir: str = "data") -> str:
-    """Example07:284-285: `data/$root_fname.neumann-neumann_ndom$ndom_$tag.pcg-iters.nreals$nreals.npz`."""
-    path = os.path.join(data_dir, f"{root_fname}.neumann-neumann_ndom{ndom}_{tag}.pcg-iters.nreals{nreals}.npz")
+def save_pcg_iters(iters, root_fname: str, ndom: int, tag: str, nreals: int, data_dir: str = "data",
+                   precond: str = "neumann-neumann") -> str:
+    """Example07:284-285: `data/$root_fname.neumann-neumann_ndom$ndom_$tag.pcg-iters.nreals$nreals.npz`;
+    `precond="A_GG"`: Example07:423-424, `data/$root_fname.A_GG_ndom$ndom_$tag.pcg-iters.nreals$nreals.npz`."""
+    path = os.path.join(data_dir, f"{root_fname}.{precond}_ndom{ndom}_{tag}.pcg-iters.nreals{nreals}.npz")
     _write(path, np.asarray(iters, dtype=np.int64))
     return path

@@ -32,7 +32,8 @@ import Fem: apply_local_schur, apply_local_schurs, apply_global_schur, apply_neu
 export MiContext, MiOperator, MiPrecond,
        LocalSchurs, LocalSchur, MatrixFreeLocalSchurs, GlobalSchur,
        AssemblyPlan, assemble!, set_values!, SchurSetup, set_blocks!, interior_precond!, interior_iterations,
-       keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!
+       keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!,
+       SparseDirectPreconditioner, spd_direct_stats
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -466,5 +467,43 @@ function initsolve(A::MiOperator, M, b::Vector{Float64}, x::Vector{Float64}, W::
 end
 initcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, W::Matrix{Float64}; maxit=0) = initsolve(A, nothing, b, x, W, maxit)
 initpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiOperator, W::Matrix{Float64}; maxit=0) = initsolve(A, M, b, x, W, maxit)
+
+# ---------------------------------------------------------------- sparse direct `M \ r` (Example07:412/416)
+"""`SparseDirectPreconditioner(ctx, A)`: `M \\ r` for a sparse SPD `A::SparseMatrixCSC` — RecyclingKrylovSolvers' pcg applies
+its `M` as `z .= M \\ r` (cg.jl:85, 100), and Example07:412/416 pass the interface block `A_ΓΓ` itself — by the device
+sparse direct solve (`mi_spd_direct_create`: one level of nested dissection, dense inverses of small pieces)."""
+function SparseDirectPreconditioner(ctx::MiContext, A::SparseMatrixCSC{Float64,Int})
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  cp, rv = Vector{Int64}(A.colptr), Vector{Int64}(A.rowval)
+  check(ccall((:mi_spd_direct_create, lib), Cint,
+              (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+              ctx.h, A.n, cp, rv, A.nzval, 1, r))
+  wrap(ctx, r)
+end
+"""`set_values!(M, A)`: the values of `A` (same pattern as at creation) — a new realization's A_ΓΓ (Example07:416)."""
+set_values!(M::MiOperator, A::SparseMatrixCSC{Float64,Int}) =
+  check(ccall((:mi_spd_direct_set_values, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), M.h, A.nzval))
+function spd_direct_stats(M::MiOperator)
+  p, s = Ref{Int64}(0), Ref{Int64}(0)
+  check(ccall((:mi_spd_direct_stats, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), M.h, p, s))
+  (p[], s[])
+end
+
+# `pcg(S, b_schur, zeros(S.N), A_ΓΓ)` as Example07:412/416 write it: the device factor is cached per matrix object, refilled
+# (set_values!) when its values changed since the last call and rebuilt when its pattern or the context did.
+const spd_factors = WeakKeyDict{SparseMatrixCSC{Float64,Int},Any}()
+function spd_factor(ctx::MiContext, M::SparseMatrixCSC{Float64,Int})
+  c = get(spd_factors, M, nothing)
+  if c === nothing || c.op.ctx !== ctx || c.colptr != M.colptr || c.rowval != M.rowval
+    c = (op=SparseDirectPreconditioner(ctx, M), colptr=copy(M.colptr), rowval=copy(M.rowval), nzval=copy(M.nzval))
+    spd_factors[M] = c
+  elseif c.nzval != M.nzval
+    set_values!(c.op, M)
+    copyto!(c.nzval, M.nzval)
+  end
+  c.op
+end
+pcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::SparseMatrixCSC{Float64,Int}; maxit=0) =
+  solve(:pcg, A, spd_factor(A.ctx, M), b, x, nothing, maxit)
 
 end # module
