@@ -53,6 +53,9 @@ def main():
                     help="with --device-assembly: S_d, the condensed rhs and NN_t on the device too (mi_schur_setup_run, mi_nn_pinv, "
                          "mi_dense_set_blocks): nothing of a realization's set-up runs on the host")
     ap.add_argument("--recycle", action="store_true")
+    ap.add_argument("--nn-f32", action="store_true",
+                    help="run the two solves of Example07:273-277 also with fp32-STORED Neumann-Neumann blocks (storage=\"f32\": "
+                         "half the preconditioner's bytes, all arithmetic fp64) and print both count vectors side by side")
     ap.add_argument("--gg", action="store_true", help="also pcg(S, b_schur, 0, A_ΓΓ_0) and pcg(S, b_schur, 0, A_ΓΓ_t) (Example07:412, 416)")
     args = ap.parse_args()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -86,6 +89,12 @@ def main():
         setup = api.SchurSetup(ctx, P0.A_IIdd, P0.A_IΓdd, P0.A_ΓΓdd)
         S_dev = api.LocalSchurs(ctx, P0.Sd, sub.gather_idx, sub.node_Γ_cnt)
         NN_dev = api.NeumannNeumannSchurPreconditioner(ctx, P0.ΠSd, sub.gather_idx, sub.node_Γ_cnt)
+    ΠSnn_0_f32 = NN_dev_f32 = None
+    if args.nn_f32:
+        ΠSnn_0_f32 = api.NeumannNeumannSchurPreconditioner(ctx, P0.ΠSd, sub.gather_idx, sub.node_Γ_cnt, storage="f32")
+        if args.device_setup:
+            NN_dev_f32 = api.NeumannNeumannSchurPreconditioner(ctx, P0.ΠSd, sub.gather_idx, sub.node_Γ_cnt, storage="f32")
+    iters_0_f32, iters_t_f32 = [], []
     M_gg0 = M_ggt = gmap = None
     if args.gg:   # Example07:290-300: A_ΓΓ_0 of the ξ = 0 operator; A_ΓΓ_t on the same pattern, refilled per realization
         A_gg0 = sp.csc_matrix(fem.prepare_global_schur(mesh.cells, mesh.points, P0.epart, sub, np.exp(0 * gs[0]), f, uexact)[2])
@@ -104,13 +113,16 @@ def main():
             ii, ig, gg, bI, bΓ = dev_plan.block_values(vals)
             Sd, w = setup.run(ii, ig, gg, bI)                                                          # :180-187
             S_dev.set_blocks(Sd)
-            NN_dev.set_blocks(api.nn_pinv(ctx, sub.n_Γd, Sd))                                          # :190-199
+            Πd = api.nn_pinv(ctx, sub.n_Γd, Sd)                                                        # :190-199
+            NN_dev.set_blocks(Πd)
+            if NN_dev_f32 is not None:
+                NN_dev_f32.set_blocks(Πd)                                                              # (rounded to fp32 on the way in)
             ctx.synchronize()
             b_schur, wh, off = bΓ.cpu().numpy().copy(), w.cpu().numpy(), 0
             for d in range(ndom):                                                                      # get_schur_rhs, EPDD.jl:853-861
                 b_schur[sub.gather_idx[d]] -= wh[off:off + sub.n_Γd[d]]
                 off += sub.n_Γd[d]
-            S, ΠSnn_t = S_dev, NN_dev
+            S, ΠSnn_t, ΠSnn_t_f32 = S_dev, NN_dev, NN_dev_f32
             if M_ggt is not None:
                 M_ggt.set_values(gmap.values(vals))                                                    # A_ΓΓ_t = Σ_d R_d' A_ΓΓdd R_d
         else:
@@ -119,6 +131,8 @@ def main():
                                         partition=(P0.epart, None), blocks=blocks, sub=sub)      # :162-199
             S = api.LocalSchurs(ctx, P.Sd, sub.gather_idx, sub.node_Γ_cnt)
             ΠSnn_t = api.NeumannNeumannSchurPreconditioner(ctx, P.ΠSd, sub.gather_idx, sub.node_Γ_cnt)
+            ΠSnn_t_f32 = (api.NeumannNeumannSchurPreconditioner(ctx, P.ΠSd, sub.gather_idx, sub.node_Γ_cnt, storage="f32")
+                          if args.nn_f32 else None)
             b_schur = P.b_schur
             if M_ggt is not None:
                 A_ggt = sp.csc_matrix(fem.prepare_global_schur(mesh.cells, mesh.points, P0.epart, sub, np.exp(gs[ireal]), f, uexact)[2])
@@ -128,6 +142,13 @@ def main():
         iters_0.append(api.pcg(S, b_schur, x0, ΠSnn_0)[1])                                            # :273
         iters_t.append(api.pcg(S, b_schur, x0, ΠSnn_t)[1])                                            # :277
         iters_def.append(api.defpcg(S, b_schur, x0, W_0, ΠSnn_0)[1])
+        f32 = ""
+        if args.nn_f32:
+            iters_0_f32.append(api.pcg(S, b_schur, x0, ΠSnn_0_f32)[1])
+            iters_t_f32.append(api.pcg(S, b_schur, x0, ΠSnn_t_f32)[1])
+            f32 = f"  fp32-stored: pcg(NN_0) it={iters_0_f32[-1]}  pcg(NN_t) it={iters_t_f32[-1]}"
+            if ΠSnn_t_f32 is not NN_dev_f32:
+                ΠSnn_t_f32.close()                       # host route: one operator per realization
         rec = ""
         if args.recycle:
             try:
@@ -146,10 +167,16 @@ def main():
             iters_ggt.append(api.pcg(S, b_schur, x0, M_ggt)[1])                                       # :416
             gg = f"  pcg(A_GG_0) it={iters_gg0[-1]}  pcg(A_GG_t) it={iters_ggt[-1]}"
         print(f"[rank {rank}] realization {ireal}: pcg(NN_0) it={iters_0[-1]}  pcg(NN_t) it={iters_t[-1]}  "
-              f"defpcg(W_0, NN_0) it={iters_def[-1]}{rec}{gg}", flush=True)
+              f"defpcg(W_0, NN_0) it={iters_def[-1]}{f32}{rec}{gg}", flush=True)
     if args.out:                                                                                       # :281-285 npz of iteration counts
         np.savez(args.out.format(rank=rank), iters_0=iters_0, iters_t=iters_t, iters_def=iters_def, iters_rec=iters_rec,
                  iters_gg0=iters_gg0, iters_ggt=iters_ggt)                                          # (:423-424: io.save_pcg_iters(..., precond="A_GG"))
+    if args.nn_f32:
+        for tag, i64_, i32_ in (("NN_0", iters_0, iters_0_f32), ("NN_t", iters_t, iters_t_f32)):
+            print(f"nn-f32 {tag}: fp64 [{' '.join(map(str, i64_))}] fp32 [{' '.join(map(str, i32_))}]")
+            if args.out:
+                pkg.io.save_pcg_iters(i32_, f"example07_N{args.N}_rank{rank}", ndom, tag, len(i32_),
+                                      data_dir=os.path.dirname(args.out.format(rank=rank)) or ".", precond="neumann-neumann-f32")
     print(f"[rank {rank}] mean its: NN_0 {np.mean(iters_0):.1f}  NN_t {np.mean(iters_t):.1f}  def {np.mean(iters_def):.1f}"
           + (f"  A_GG_0 {np.mean(iters_gg0):.1f}  A_GG_t {np.mean(iters_ggt):.1f}" if iters_gg0 else ""))
 

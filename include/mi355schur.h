@@ -185,6 +185,27 @@ int mi_nn_create(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, const int64_t *n_g
                  const int64_t *const *gather_idx, const double *const *PiSd, const int64_t *node_gamma_cnt,
                  int index_base, int64_t dom_begin, int64_t dom_end, mi_op_t *op);
 
+/* mi_nn_create_stored — the same operator (EPDD.jl:1111-1137, applied as EPDD.jl:1361-1403) with the ΠS_d blocks HELD in
+ * `storage`: MI_STORE_F64 (what mi_nn_create does) or MI_STORE_F32. PiSd[d] is fp64 column-major either way; with
+ * MI_STORE_F32 every entry is rounded once to fp32 (nearest even, subnormals kept: a C `(float)` cast) and the apply is
+ * the fp64 apply of the blocks double(float(ΠS_d)) up to summation order — operand r / cnt, products, sums, scaling
+ * and everything the solvers do stay fp64, half the bytes are streamed. Rounding a symmetric block element-wise keeps it
+ * symmetric, and PCG asks nothing of M but to be symmetric positive definite.
+ * Precedent: the reference's low-precision preconditioner wrappers Cholesky32 / Cholesky16
+ * (MyPreconditioners/CholPreconditioners.jl:32-56). Deliberately NOT their semantics: those also round r and solve in
+ * fp32; here fp32 is a storage format only.
+ * A block entry that is not finite or exceeds FLT_MAX in magnitude is MI_ERR_BAD_ARG (the message names the block), as
+ * is an unknown `storage`. mi_dense_set_blocks keeps taking fp64 blocks and converts on the way (host pointers are
+ * checked like at creation; device pointers are converted asynchronously, unchecked). S_d has no fp32 form. */
+#define MI_STORE_F64 0
+#define MI_STORE_F32 1
+int mi_nn_create_stored(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d,
+                        const int64_t *const *gather_idx, const double *const *PiSd, const int64_t *node_gamma_cnt,
+                        int index_base, int64_t dom_begin, int64_t dom_end, int storage, mi_op_t *op);
+/* Storage kind of an operator's dense blocks: MI_STORE_F32 for an fp32-stored Neumann-Neumann operator, MI_STORE_F64 for
+ * every other operator. */
+int mi_op_storage(mi_op_t op, int *storage);
+
 /* mi_schur_matfree_create — `apply_local_schurs(A_IIdd, A_IΓdd, A_ΓΓdd, ind_Γd_Γ2l, node_Γ_cnt, x)`,
  * EPDD.jl:711-747 (per subdomain apply_local_schur, EPDD.jl:639-654):
  * S_d x_d = A_ΓΓdd x_d − A_IΓdd' (A_IIdd^{-1} (A_IΓdd x_d)). The three sparse products run on the
@@ -243,7 +264,8 @@ int mi_schur_interior_iterations(mi_op_t op, int64_t *iterations);
 int mi_op_size(mi_op_t op, int64_t *n);
 /* y = A*x (operator) or y = M \ x (preconditioner); x and y must not alias. */
 int mi_op_apply(mi_op_t op, const double *x, double *y);
-/* Algorithmic bytes of one apply (SURVEY.md §8d formulas) and of its dominant kernel alone. */
+/* Algorithmic bytes of one apply (SURVEY.md §8d formulas) and of its dominant kernel alone; dense blocks count in the
+ * format they are stored in (fp32-stored Neumann-Neumann: Σ_d 4 n_Γd² + 20 n_Γd for the kernel). */
 int mi_op_bytes(mi_op_t op, int64_t *bytes_apply, int64_t *bytes_dominant_kernel);
 /* Diagnostic: launch only the dominant kernel of the apply `reps` times (x as in mi_op_apply). */
 int mi_op_apply_dominant(mi_op_t op, const double *x, int reps);

@@ -51,6 +51,8 @@ SIGNATURES = {
     "mi_spd_direct_stats": [vp, i64p, i64p],
     "mi_schur_assembled_create": [vp, i64, i64, i64p, i64pp, f64pp, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_nn_create": [vp, i64, i64, i64p, i64pp, f64pp, i64p, C.c_int, i64, i64, C.POINTER(vp)],
+    "mi_nn_create_stored": [vp, i64, i64, i64p, i64pp, f64pp, i64p, C.c_int, i64, i64, C.c_int, C.POINTER(vp)],
+    "mi_op_storage": [vp, C.POINTER(C.c_int)],
     "mi_schur_matfree_create": [vp, i64, i64, i64p, i64p, i64pp, i64pp, i64pp, f64pp, i64pp, i64pp, f64pp,
                                 INTERIOR_SOLVE_FN, vp, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_schur_matfree_device_create": [vp, i64, i64, i64p, i64p, i64pp, i64pp, i64pp, f64pp, i64pp, i64pp, f64pp,

@@ -475,10 +475,19 @@ class LocalSchurs(Operator):
 
 class NeumannNeumannSchurPreconditioner(Operator):
     """`NeumannNeumannSchurPreconditioner(ΠSd, ind_Γd_Γ2l, node_Γ_cnt)` (EPDD.jl:1111-1137); used by the
-    solvers through `Πnn \\ r` (EPDD.jl:1389-1392) = `apply_neumann_neumann_schur` (EPDD.jl:1361-1386)."""
+    solvers through `Πnn \\ r` (EPDD.jl:1389-1392) = `apply_neumann_neumann_schur` (EPDD.jl:1361-1386).
+
+    `storage="f32"` (or `numpy.float32`) holds the blocks as fp32 on the device: the apply is the fp64 apply of
+    `ΠSd.astype(float32).astype(float64)`, half the bytes streamed; everything else stays fp64 (`mi_nn_create_stored`)."""
+
+    _STORAGE = {"f64": 0, "f32": 1}
 
     def __init__(self, ctx: Context, ΠSd: Sequence, ind_Γd_Γ2l: Sequence, node_Γ_cnt, index_base: int = 0,
-                 dom_slice=None):
+                 dom_slice=None, storage="f64"):
+        if isinstance(storage, (type, np.dtype)):
+            storage = {np.dtype(np.float64): "f64", np.dtype(np.float32): "f32"}.get(np.dtype(storage), storage)
+        if storage not in self._STORAGE:
+            raise ValueError(f"storage must be 'f64', 'f32', numpy.float64 or numpy.float32, not {storage!r}")
         ndom = len(ΠSd)
         cnt = _i64(node_Γ_cnt)
         lo, hi = _dom_slice(ctx, ndom, dom_slice)
@@ -486,11 +495,18 @@ class NeumannNeumannSchurPreconditioner(Operator):
         nd = _i64([a.size for a in g])
         P = _blocks(ΠSd, lo, hi)
         h = vp()
-        check(ctx._L.mi_nn_create(ctx._h, i64(ndom), i64(cnt.size), nd.ctypes.data_as(i64p), _ptrs(g, i64p),
-                                  _ptrs(P, f64p), cnt.ctypes.data_as(i64p), C.c_int(index_base), i64(lo), i64(hi),
-                                  C.byref(h)))
+        check(ctx._L.mi_nn_create_stored(ctx._h, i64(ndom), i64(cnt.size), nd.ctypes.data_as(i64p), _ptrs(g, i64p),
+                                         _ptrs(P, f64p), cnt.ctypes.data_as(i64p), C.c_int(index_base), i64(lo), i64(hi),
+                                         C.c_int(self._STORAGE[storage]), C.byref(h)))
         super().__init__(ctx, h)
         self.dom_slice = (lo, hi)
+
+    @property
+    def storage(self) -> str:
+        """"f64" or "f32": the format the blocks are held in on the device (`mi_op_storage`)."""
+        s = C.c_int()
+        check(self.ctx._L.mi_op_storage(self._h, C.byref(s)))
+        return "f32" if s.value == 1 else "f64"
 
 
 def _wrap_interior(solvers: Sequence[Callable]):

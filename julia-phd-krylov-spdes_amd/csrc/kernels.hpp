@@ -857,7 +857,7 @@ struct GemvTile {
                       // (active: the WAVES*RPW streamed rows; inactive: up to one row per thread)
 };
 struct DenseMeta {
-  const double *M;        // all blocks of this rank, row-major, padded
+  const void *M;          // all blocks of this rank, row-major, padded: doubles, or floats for fp32-stored blocks (GemvRows<RPW, MT>)
   const GemvTile *tiles;  // [ntiles]
   const int *gidx;        // [nloc] Γ index of every local row/column
   const double *cnt;      // [nloc] node_Γ_cnt as double (NN only)
@@ -871,18 +871,40 @@ constexpr int GEMV_PANEL = 2048;  // doubles of x_d staged per pass (16 KiB LDS)
 #define MI355_GEMV_GU 4        // 16-byte loads per lane and row in one group (2 and 8 measured slower, profiles/)
 #endif
 constexpr int GU = MI355_GEMV_GU;
+#ifndef MI355_GEMV_GU_F32
+// ... of the fp32-stored blocks. 2, not 4: a group then covers 512 columns like the fp64 group, and its operand (4 doubles
+// per load from LDS) and widened floats fit. With 4 the default PHASE 1 launch k_gemv_pcg<2,1,2,16,false,float> sat at the
+// 128-VGPR cap of a 1024-thread workgroup with 16 VGPRs spilled (60 B/lane of scratch) and k_gemv_batched<2,true,16,float>
+// took 125 VGPRs (4 waves/SIMD); with 2: 109 VGPRs, no scratch (fp64 twin: 102) and 62 VGPRs, 8 waves/SIMD (fp64: 78, 6).
+#define MI355_GEMV_GU_F32 2
+#endif
 // Default-policy loads on purpose: the 136 MB working set of a PCG iteration is re-read from the Infinity
 // Cache every iteration; non-temporal loads made the stand-alone GEMV 3 % faster and the solve 4 % slower.
-__device__ __forceinline__ double2 gemv_ld(const double *p) { return *reinterpret_cast<const double2 *>(p); }
-template <int RPW>
-__device__ __forceinline__ void gemv_load_group(double2 (&mv)[RPW][GU], const double *const (&rowp)[RPW], int col0,
+// Storage type MT of a block: double (two columns per 16-byte load, 128 columns per wave load) or float (four columns per
+// load, 256 per wave load: the fp32-stored Neumann-Neumann blocks, MI_STORE_F32). A float is widened in registers
+// (v_cvt_f64_f32, exact) and multiplied against the same fp64 LDS copy of x_d: fp32 is a storage format, every product and
+// sum stays fp64. Per row the accumulation order is fixed by (lane, load, column), whatever the tiling.
+template <typename MT> struct GemvElem;
+template <> struct GemvElem<double> {
+  using Vec = double2; static constexpr int CPL = 2; static constexpr int G = GU;
+  static __device__ __forceinline__ double2 zero() { return make_double2(0.0, 0.0); }
+};
+template <> struct GemvElem<float> {
+  using Vec = float4; static constexpr int CPL = 4; static constexpr int G = MI355_GEMV_GU_F32;
+  static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+};
+template <typename MT> constexpr int gemv_wave_cols() { return 64 * GemvElem<MT>::CPL; }   // columns of one wave load
+template <typename MT>
+__device__ __forceinline__ typename GemvElem<MT>::Vec gemv_ld(const MT *p) { return *reinterpret_cast<const typename GemvElem<MT>::Vec *>(p); }
+template <int RPW, typename MT>
+__device__ __forceinline__ void gemv_load_group(typename GemvElem<MT>::Vec (&mv)[RPW][GemvElem<MT>::G], const MT *const (&rowp)[RPW], int col0,
                                                 int cb, int pw, int lane) {
 #pragma unroll
-  for (int u = 0; u < GU; ++u) {
-    const int c = cb + u * 128 + lane * 2;
+  for (int u = 0; u < GemvElem<MT>::G; ++u) {
+    const int c = cb + u * gemv_wave_cols<MT>() + lane * GemvElem<MT>::CPL;
 #pragma unroll
     for (int k = 0; k < RPW; ++k)
-      mv[k][u] = (c < pw) ? gemv_ld(rowp[k] + col0 + c) : make_double2(0.0, 0.0);
+      mv[k][u] = (c < pw) ? gemv_ld<MT>(rowp[k] + col0 + c) : GemvElem<MT>::zero();
   }
 }
 template <int RPW>
@@ -899,33 +921,52 @@ __device__ __forceinline__ void gemv_fma_group(double (&acc)[RPW], const double2
     }
   }
 }
+template <int RPW>
+__device__ __forceinline__ void gemv_fma_group(double (&acc)[RPW], const float4 (&mv)[RPW][GemvElem<float>::G], const double *xs, int cb,
+                                               int pw, int lane) {
+#pragma unroll
+  for (int u = 0; u < GemvElem<float>::G; ++u) {
+    const int c = cb + u * 256 + lane * 4;   // (pw is a multiple of 32: c < pw covers c + 3)
+    const double2 xa = (c < pw) ? *reinterpret_cast<const double2 *>(&xs[c]) : make_double2(0.0, 0.0);
+    const double2 xb = (c < pw) ? *reinterpret_cast<const double2 *>(&xs[c + 2]) : make_double2(0.0, 0.0);
+#pragma unroll
+    for (int k = 0; k < RPW; ++k) {
+      acc[k] += (double)mv[k][u].x * xa.x;
+      acc[k] += (double)mv[k][u].y * xa.y;
+      acc[k] += (double)mv[k][u].z * xb.x;
+      acc[k] += (double)mv[k][u].w * xb.y;
+    }
+  }
+}
 // Row streamer of one tile: RPW rows per wave, 16 B per lane and row per load, groups of 4 loads.
 // `begin` issues the first group of matrix loads (so the stream is in flight while the caller
 // stages the column values into LDS), `panel` consumes one staged panel, `finish` reduces.
-template <int RPW>
+template <int RPW, typename MT = double>
 struct GemvRows {
-  const double *rowp[RPW];
+  using Vec = typename GemvElem<MT>::Vec;
+  static constexpr int GROUP_COLS = gemv_wave_cols<MT>() * GemvElem<MT>::G;
+  const MT *rowp[RPW];
   double acc[RPW];
-  double2 buf[RPW][GU];
+  Vec buf[RPW][GemvElem<MT>::G];
   int lane, ld;
   __device__ __forceinline__ void begin(const DenseMeta &m, const GemvTile &t) {
     lane = threadIdx.x & 63;
     ld = t.ld;
     const int row_base = t.row0 + (threadIdx.x >> 6) * RPW;
-    const double *Md = m.M + t.mat_off;
+    const MT *Md = static_cast<const MT *>(m.M) + t.mat_off;   // (mat_off and ld count elements of the storage type)
 #pragma unroll
     for (int k = 0; k < RPW; ++k) {
       const int r = min(row_base + k, t.n - 1);  // clamp: tail rows re-read a valid row, result dropped
       rowp[k] = Md + (long long)r * ld;
       acc[k] = 0.0;
     }
-    gemv_load_group<RPW>(buf, rowp, 0, 0, min(GEMV_PANEL, ld), lane);
+    gemv_load_group<RPW, MT>(buf, rowp, 0, 0, min(GEMV_PANEL, ld), lane);
   }
   // xs holds columns [c0, c0 + pw) of the operand; for c0 > 0 the first group is loaded here
   __device__ __forceinline__ void panel(const double *xs, int c0, int pw) {
-    if (c0) gemv_load_group<RPW>(buf, rowp, c0, 0, pw, lane);
-    for (int cb = 0; cb < pw; cb += 128 * GU) {
-      if (cb) gemv_load_group<RPW>(buf, rowp, c0, cb, pw, lane);
+    if (c0) gemv_load_group<RPW, MT>(buf, rowp, c0, 0, pw, lane);
+    for (int cb = 0; cb < pw; cb += GROUP_COLS) {
+      if (cb) gemv_load_group<RPW, MT>(buf, rowp, c0, cb, pw, lane);
       gemv_fma_group<RPW>(acc, buf, xs, cb, pw, lane);
     }
   }
@@ -935,7 +976,7 @@ struct GemvRows {
   }
 };
 
-template <int RPW, bool SCALE, int WAVES>
+template <int RPW, bool SCALE, int WAVES, typename MT = double>
 __global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(DenseMeta m, const double *__restrict__ x,
                                                              double *__restrict__ yslots, const int *done,
                                                              const int *zero_x) {
@@ -955,7 +996,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(DenseMeta m, const 
         if (row_base + k < n) yslots[m.out_pos[off + row_base + k]] = 0.0;
     return;
   }
-  GemvRows<RPW> rows;
+  GemvRows<RPW, MT> rows;
 #if !MI355_OPERAND_FIRST
   rows.begin(m, t);
 #endif
@@ -1029,7 +1070,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_multi(DenseMeta m, const do
   double acc[RPW][KV];
 #pragma unroll
   for (int k = 0; k < RPW; ++k) {
-    rowp[k] = m.M + t.mat_off + (long long)min(row_base + k, n - 1) * t.ld;
+    rowp[k] = static_cast<const double *>(m.M) + t.mat_off + (long long)min(row_base + k, n - 1) * t.ld;   // (fp64 storage only)
 #pragma unroll
     for (int v = 0; v < KV; ++v) acc[k][v] = 0.0;
   }
@@ -1053,7 +1094,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_multi(DenseMeta m, const do
     __syncthreads();
     double2 buf[RPW][GU];
     for (int cb = 0; cb < pw; cb += 128 * GU) {
-      gemv_load_group<RPW>(buf, rowp, c0, cb, pw, lane);
+      gemv_load_group<RPW, double>(buf, rowp, c0, cb, pw, lane);
 #pragma unroll
       for (int u = 0; u < GU; ++u) {
         const int c = cb + u * 128 + lane * 2;
@@ -1184,10 +1225,10 @@ __device__ __forceinline__ double slot_sum(const double *slots, int g, int W) {
   return s;
 }
 
-// FOLD_CPT = columns per thread staged in registers: the launch needs max n_Γd <= FOLD_CPT * 256 (<= GEMV_PANEL)
 // FOLD_CPT = columns per thread staged in registers: the launch needs max n_Γd <= FOLD_CPT * 64 * WAVES (<= GEMV_PANEL)
 // XCHG = false compiles every peer-exchange branch out: the single-GPU launches are the kernel they were before.
-template <int RPW, int PHASE, int FOLD_CPT, int WAVES, bool XCHG>
+// MT = float: the blocks of this launch are stored as fp32 (PHASE 1, XCHG = false only: the Neumann-Neumann launch).
+template <int RPW, int PHASE, int FOLD_CPT, int WAVES, bool XCHG, typename MT = double>
 __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f) {
   constexpr int NTH = 64 * WAVES, NR = WAVES * RPW;  // threads and rows per workgroup
   SolverState *st = f.st;
@@ -1204,7 +1245,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
   asm volatile("" ::"s"(t.mat_off), "s"(t.n), "s"(t.ld), "s"(t.loc_off), "s"(t.row0), "s"(t.active), "s"(t.nrows), "s"(it0),
                "s"(it_nxt0), "s"(maxit), "s"(cap), "s"(tol), "s"(rTz0), "s"(old), "s"(done0), "s"(xe), "s"(xo));
   if (done0) return;
-  GemvRows<RPW> rows;
+  GemvRows<RPW, MT> rows;
   if (x_inwait && f.in_stride) {
     // the tables this launch reads are complete when every rank's flag in the own arena has reached the exchange number
     if (t.active) rows.begin(m, t);      // (the matrix does not depend on them: its first loads travel while the flags are polled)

@@ -555,8 +555,22 @@ int mi_schur_assembled_create(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, const
 int mi_nn_create(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d, const int64_t *const *gather_idx,
                  const double *const *PiSd, const int64_t *node_gamma_cnt, int index_base, int64_t dom_begin,
                  int64_t dom_end, mi_op_t *op) {
+  return mi_nn_create_stored(ctx, ndom, n_gamma, n_gamma_d, gather_idx, PiSd, node_gamma_cnt, index_base, dom_begin, dom_end,
+                             MI_STORE_F64, op);
+}
+int mi_nn_create_stored(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d, const int64_t *const *gather_idx,
+                        const double *const *PiSd, const int64_t *node_gamma_cnt, int index_base, int64_t dom_begin,
+                        int64_t dom_end, int storage, mi_op_t *op) {
+  if (op) *op = nullptr;
+  if (storage != MI_STORE_F64 && storage != MI_STORE_F32) return fail(MI_ERR_BAD_ARG, "mi_nn_create_stored: unknown storage %d", storage);
   if (!node_gamma_cnt) return fail(MI_ERR_BAD_ARG, "node_gamma_cnt is NULL");
-  MI_NEW_OP(ctx, op, new DenseBlockOp(ctx, ndom, n_gamma, n_gamma_d, gather_idx, PiSd, node_gamma_cnt, index_base, dom_begin, dom_end));
+  MI_NEW_OP(ctx, op, new DenseBlockOp(ctx, ndom, n_gamma, n_gamma_d, gather_idx, PiSd, node_gamma_cnt, index_base, dom_begin, dom_end, storage));
+}
+int mi_op_storage(mi_op_t op, int *storage) {
+  if (!op || !op->impl || !storage) return fail(MI_ERR_BAD_ARG, "mi_op_storage: NULL argument");
+  DenseBlockOp *d = op->impl->as_dense();
+  *storage = d ? d->storage : MI_STORE_F64;
+  return MI_OK;
 }
 
 int mi_schur_matfree_create(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d, const int64_t *n_i,
@@ -1094,6 +1108,15 @@ int mi_dense_set_blocks(mi_op_t op, const double *blocks) {
     c->use();
     size_t tot = 0;
     for (int dl = 0; dl < dop->maps.ndl; ++dl) if (dop->owned_h[dl]) tot += (size_t)dop->maps.nd[dl] * dop->maps.nd[dl];
+    if (dop->f32() && c->ptr_mode != MI_PTR_DEVICE) {   // as at creation: nothing fp32 cannot hold goes in silently
+      size_t e = 0;
+      for (int dl = 0; dl < dop->maps.ndl; ++dl) {
+        if (!dop->owned_h[dl]) continue;
+        const size_t nk = (size_t)dop->maps.nd[dl] * dop->maps.nd[dl];
+        DenseBlockOp::check_f32_range(blocks + e, nk, dl);
+        e += nk;
+      }
+    }
     DevBuf<double> st;
     In bi(c, blocks, tot, st);
     dop->set_blocks(bi.dev);

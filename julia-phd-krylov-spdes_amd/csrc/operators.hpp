@@ -2,6 +2,8 @@
 #pragma once
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
+#include <cmath>
 #include <cstdlib>
 #include <functional>
 #include <numeric>
@@ -327,10 +329,19 @@ struct LocalMaps {
 struct DenseBlockOp : Operator {
   LocalMaps maps;
   bool scale;  // true: Neumann-Neumann (gather r/cnt, result /cnt)
+  int storage;  // MI_STORE_F64 / MI_STORE_F32: element type the blocks are held and streamed in (fp32: Neumann-Neumann only)
+  bool f32() const { return storage == MI_STORE_F32; }
+  // fp32 storage refuses what a float cannot hold (creation, and set_blocks from host pointers); `block`: subdomain number
+  static void check_f32_range(const double *src, size_t ne, long long block) {
+    for (size_t e = 0; e < ne; ++e)
+      if (!(std::fabs(src[e]) <= (double)FLT_MAX))
+        raise(MI_ERR_BAD_ARG, "fp32 storage: block %lld holds %g at entry %zu (not finite, or beyond FLT_MAX)", block, src[e], e);
+  }
   int rpw, waves, ntiles = 0, max_nd = 0, max_ld = 0;  // rows per wave, waves per workgroup (4, 8 or 16)
   bool reduce_over_ranks = false;          // this rank holds only a slice of the subdomains and a communicator exists
   bool full_maps = false;                  // ... and is built on the maps of all subdomains (inactive tiles for the others)
   DevBuf<double> M, cnt, yslots;
+  DevBuf<float> M32;          // the blocks when storage == MI_STORE_F32 (M stays empty)
   DevBuf<double> yslots_all;  // multi-GPU: all-reduced copy of the contribution slots (every rank's subdomains)
   // folded PCG launches: [nloc*W] local-order contributions followed by the per-tile partials of the first dot, in ONE
   // buffer (`fold_pack`; `fold_pack_all` = its sum over ranks when the launch is sharded); second partial array; [4*nloc]
@@ -377,9 +388,14 @@ struct DenseBlockOp : Operator {
   DenseMeta meta{};
 
   DenseBlockOp(mi_ctx_s *c, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d, const int64_t *const *gather_idx,
-               const double *const *blocks, const int64_t *node_cnt, int base, int64_t d0, int64_t d1)
-      : Operator(c, n_gamma), scale(node_cnt != nullptr) {
+               const double *const *blocks, const int64_t *node_cnt, int base, int64_t d0, int64_t d1,
+               int storage_ = MI_STORE_F64)
+      : Operator(c, n_gamma), scale(node_cnt != nullptr), storage(storage_) {
     if (!blocks) raise(MI_ERR_BAD_ARG, "dense blocks pointer is NULL");
+    if (storage != MI_STORE_F64 && storage != MI_STORE_F32) raise(MI_ERR_BAD_ARG, "dense blocks: unknown storage %d", storage);
+    // the operator S stays in working precision: only a preconditioner may be held in fewer bits (PCG needs M symmetric
+    // positive definite, nothing more)
+    if (f32() && !scale) raise(MI_ERR_BAD_ARG, "fp32 storage is for the Neumann-Neumann blocks only: S_d stays fp64");
     // A slice of the subdomains (multi-GPU) is built on the maps of ALL subdomains whenever their gather lists are given
     // (index arrays every rank has): tiles of the other ranks' blocks exist but are inactive. The slot tables of the
     // ranks are then disjoint by construction, and the folded PCG launches can run sharded (solvers.hpp).
@@ -417,10 +433,14 @@ struct DenseBlockOp : Operator {
     auto owned = [&](int dl) { return m0 + dl >= d0 && m0 + dl < d1; };
     for (int dl = 0; dl < maps.ndl; ++dl) {
       const int n_d = maps.nd[dl];
-      int l = (n_d + 15) / 16 * 16;
+      // rows padded to whole 128-byte lines: 16 doubles / 32 floats
+      const int line = f32() ? 32 : 16;
+      int l = (n_d + line - 1) / line * line;
       // A row stride that is a multiple of 2 KiB puts every row of a tile on the same HBM channels: measured 27 % slower
-      // at n_Γd = 1024 (profiles/r01_gemv_variant_sweep.txt). One extra 128-byte line per row breaks the pattern.
-      if (l % 256 == 0 && l != GEMV_PANEL) l += 16;
+      // at n_Γd = 1024 (profiles/r01_gemv_variant_sweep.txt). One extra 128-byte line per row breaks the pattern. The
+      // pattern is one of bytes: 256 doubles, 512 floats. (l == GEMV_PANEL keeps its stride in both formats: the operand
+      // panel of the folded launches holds no more columns.)
+      if (l % (16 * line) == 0 && l != GEMV_PANEL) l += line;
       const bool own = owned(dl);
       if (own && n_d && !blocks[m0 + dl]) raise(MI_ERR_BAD_ARG, "dense block %d is NULL", dl);
       moff.push_back(own ? tot : 0); ldv.push_back(l);
@@ -439,7 +459,7 @@ struct DenseBlockOp : Operator {
       if (sharded_parts) part_total += (n_d + PART_ROWS - 1) / PART_ROWS;
       if (own) {
         tot += (long long)n_d * l;
-        alg_bytes += 8ll * n_d * n_d + 16ll * n_d + 4ll * n_d;
+        alg_bytes += (f32() ? 4ll : 8ll) * n_d * n_d + 16ll * n_d + 4ll * n_d;
       }
     }
     ntiles = (int)tv.size();
@@ -448,14 +468,32 @@ struct DenseBlockOp : Operator {
     for (int dl = 0; dl < maps.ndl; ++dl) owned_h.push_back(owned(dl) ? 1 : 0);
     // (+ one zeroed panel behind the last block: the persistent kernel reads whole 128-double groups of a row without
     // clamping, so a read may run past a row's end — into the next row, or into this tail — and meets a zero operand there)
-    M.alloc((size_t)tot + GEMV_PANEL);
-    memset_sync(M.p + tot, 0, sizeof(double) * GEMV_PANEL);
+    if (f32()) {
+      // Refuse before anything is stored: a block entry that fp32 cannot hold would sit in the preconditioner as a silent inf.
+      for (int dl = 0; dl < maps.ndl; ++dl) {
+        if (!owned(dl)) continue;
+        check_f32_range(blocks[m0 + dl], (size_t)maps.nd[dl] * maps.nd[dl], (long long)(m0 + dl));
+      }
+      M32.alloc((size_t)tot + GEMV_PANEL);
+      memset_sync(M32.p + tot, 0, sizeof(float) * GEMV_PANEL);
+    } else {
+      M.alloc((size_t)tot + GEMV_PANEL);
+      memset_sync(M.p + tot, 0, sizeof(double) * GEMV_PANEL);
+    }
     // column-major (Julia) -> padded row-major, one block at a time
     for (int dl = 0; dl < maps.ndl; ++dl) {
       if (!owned(dl)) continue;
       const int n_d = maps.nd[dl], l = ldv[dl];
-      std::vector<double> rowm((size_t)n_d * l, 0.0);
       const double *src = blocks[m0 + dl];
+      if (f32()) {   // (float) rounds to nearest even and keeps subnormals, as numpy.astype(float32) does
+        std::vector<float> rowm((size_t)n_d * l, 0.0f);
+        for (int j = 0; j < n_d; ++j)
+          for (int i = 0; i < n_d; ++i) rowm[(size_t)i * l + j] = (float)src[(size_t)i + (size_t)j * n_d];
+        if (!rowm.empty())
+          memcpy_sync(M32.p + moff[dl], rowm.data(), rowm.size() * sizeof(float), hipMemcpyHostToDevice);
+        continue;
+      }
+      std::vector<double> rowm((size_t)n_d * l, 0.0);
       for (int j = 0; j < n_d; ++j)
         for (int i = 0; i < n_d; ++i) rowm[(size_t)i * l + j] = src[(size_t)i + (size_t)j * n_d];
       if (!rowm.empty())
@@ -515,16 +553,21 @@ struct DenseBlockOp : Operator {
     }
     fold_vec.alloc((size_t)maps.nloc * 4 + 4); fold_vec.zero(c->stream);
     MI_HIP(hipStreamSynchronize(c->stream));
-    meta = DenseMeta{M.p, tiles.p, maps.gidx.p, scale ? cnt.p : nullptr, maps.out_pos.p};
+    meta = DenseMeta{f32() ? static_cast<const void *>(M32.p) : static_cast<const void *>(M.p), tiles.p, maps.gidx.p, scale ? cnt.p : nullptr, maps.out_pos.p};
   }
   void gemv(const double *x, const int *done) {
     if (!ntiles) return;
     const int *zx = zero_hint;
 #define MI_GEMV(R, S, V) hipLaunchKernelGGL((k_gemv_batched<R, S, V>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, x, yslots.p, done, zx)
 #define MI_GEMV_R(S, V) do { if (rpw == 1) MI_GEMV(1, S, V); else if (rpw == 2) MI_GEMV(2, S, V); else MI_GEMV(4, S, V); } while (0)
-    if (waves == 16)     { if (scale) MI_GEMV_R(true, 16); else MI_GEMV_R(false, 16); }
+#define MI_GEMV32(R, V) hipLaunchKernelGGL((k_gemv_batched<R, true, V, float>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, x, yslots.p, done, zx)
+#define MI_GEMV32_R(V) do { if (rpw == 1) MI_GEMV32(1, V); else if (rpw == 2) MI_GEMV32(2, V); else MI_GEMV32(4, V); } while (0)
+    if (f32())           { if (waves == 16) MI_GEMV32_R(16); else if (waves == 8) MI_GEMV32_R(8); else MI_GEMV32_R(4); }
+    else if (waves == 16) { if (scale) MI_GEMV_R(true, 16); else MI_GEMV_R(false, 16); }
     else if (waves == 8) { if (scale) MI_GEMV_R(true, 8); else MI_GEMV_R(false, 8); }
     else                 { if (scale) MI_GEMV_R(true, 4); else MI_GEMV_R(false, 4); }
+#undef MI_GEMV32_R
+#undef MI_GEMV32
 #undef MI_GEMV_R
 #undef MI_GEMV
     MI_HIP(hipGetLastError());
@@ -544,7 +587,8 @@ struct DenseBlockOp : Operator {
   static constexpr int KV = 4;  // columns per pass of apply_multi (4 x 16 KiB of LDS for the operand panels)
   DevBuf<double> yslots_multi;
   void apply_multi(const double *X, int64_t ldx, int k, double *Y, int64_t ldy) override {
-    if (reduce_over_ranks || !ntiles || env_int("MI355_NO_MULTI", 0)) { Operator::apply_multi(X, ldx, k, Y, ldy); return; }
+    // (fp32-stored blocks: column by column — k_gemv_multi streams doubles)
+    if (reduce_over_ranks || !ntiles || f32() || env_int("MI355_NO_MULTI", 0)) { Operator::apply_multi(X, ldx, k, Y, ldy); return; }
     const long long stride = (long long)n * maps.slot_width + 4;
     if (yslots_multi.n < (size_t)(stride * KV)) { yslots_multi.alloc((size_t)(stride * KV)); yslots_multi.zero(ctx->stream); }
     for (int v0 = 0; v0 < k; v0 += KV) {
@@ -563,9 +607,12 @@ struct DenseBlockOp : Operator {
     if (!ntiles) return;
     ++folded_pcg_launches();
     const bool xchg = f.xp != nullptr || f.x_inwait != 0;   // this launch stores into the peers' arenas and / or waits for them
+    // fp32-stored blocks have the ΠS launch without peer exchange only (Krylov's fold decision keeps everything else away)
+    if (f32() && (phase != 1 || xchg)) raise(MI_ERR_BAD_ARG, "folded PCG launch: no fp32 kernel for phase %d%s", phase, xchg ? " with peer exchange" : "");
 #define MI_PCG4(R, P, C, V) do { if (xchg) hipLaunchKernelGGL((k_gemv_pcg<R, P, C, V, true>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, f); \
                                  else hipLaunchKernelGGL((k_gemv_pcg<R, P, C, V, false>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, f); } while (0)
-#define MI_PCG3(R, C, V) do { if (phase) MI_PCG4(R, 1, C, V); else MI_PCG4(R, 0, C, V); } while (0)
+#define MI_PCG32(R, C, V) hipLaunchKernelGGL((k_gemv_pcg<R, 1, C, V, false, float>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, f)
+#define MI_PCG3(R, C, V) do { if (f32()) MI_PCG32(R, C, V); else if (phase) MI_PCG4(R, 1, C, V); else MI_PCG4(R, 0, C, V); } while (0)
 #define MI_PCG2(R, V) do { const int c = (max_ld + 64 * V - 1) / (64 * V); \
                            if (c <= 2) MI_PCG3(R, 2, V); else if (c == 3) MI_PCG3(R, 3, V); else if (c == 4) MI_PCG3(R, 4, V); \
                            else if (c == 5) MI_PCG3(R, 5, V); else if (c == 6) MI_PCG3(R, 6, V); else MI_PCG3(R, 8, V); } while (0)
@@ -574,6 +621,7 @@ struct DenseBlockOp : Operator {
 #undef MI_PCG
 #undef MI_PCG2
 #undef MI_PCG3
+#undef MI_PCG32
 #undef MI_PCG4
     MI_HIP(hipGetLastError());
   }
@@ -598,11 +646,13 @@ struct DenseBlockOp : Operator {
 };
 
 // M[moff + i*ld + j] = src[i + j*n] (column-major block -> padded row-major block)
-__global__ __launch_bounds__(NT) void k_block_to_rowmajor(int n, int ld, const double *__restrict__ src, double *__restrict__ dstm) {
+// MT = float: rounded to nearest even on the way (v_cvt_f32_f64; subnormals kept, as the host's (float) cast keeps them)
+template <typename MT>
+__global__ __launch_bounds__(NT) void k_block_to_rowmajor(int n, int ld, const double *__restrict__ src, MT *__restrict__ dstm) {
   const long long tot = (long long)n * n;
   for (long long e = blockIdx.x * (long long)NT + threadIdx.x; e < tot; e += (long long)gridDim.x * NT) {
     const int j = (int)(e % n), i = (int)(e / n);   // consecutive threads: consecutive j of one row -> coalesced stores
-    dstm[(long long)i * ld + j] = src[i + (long long)j * n];
+    dstm[(long long)i * ld + j] = (MT)src[i + (long long)j * n];
   }
 }
 inline void DenseBlockOp::set_blocks(const double *src) {
@@ -610,8 +660,9 @@ inline void DenseBlockOp::set_blocks(const double *src) {
   for (int dl = 0; dl < maps.ndl; ++dl) {
     const int n_d = maps.nd[dl];
     if (!owned_h[dl] || n_d == 0) continue;
-    hipLaunchKernelGGL(k_block_to_rowmajor, dim3((int)std::max<long long>(1, std::min<long long>(((long long)n_d * n_d + NT - 1) / NT, 4096))),
-                       dim3(NT), 0, ctx->stream, n_d, ld_h[dl], src + off, M.p + moff_h[dl]);
+    const dim3 grid((int)std::max<long long>(1, std::min<long long>(((long long)n_d * n_d + NT - 1) / NT, 4096)));
+    if (f32()) hipLaunchKernelGGL(k_block_to_rowmajor<float>, grid, dim3(NT), 0, ctx->stream, n_d, ld_h[dl], src + off, M32.p + moff_h[dl]);
+    else hipLaunchKernelGGL(k_block_to_rowmajor<double>, grid, dim3(NT), 0, ctx->stream, n_d, ld_h[dl], src + off, M.p + moff_h[dl]);
     off += (size_t)n_d * n_d;
   }
   MI_HIP(hipGetLastError());

@@ -308,7 +308,11 @@ struct Krylov {
       // ... or sharded as well (both on the maps of all subdomains): then the ΠS launch is followed by an exchange too
       fold = Ad && Md && (!Ad->reduce_over_ranks || (Ad->full_maps && nvec == 0)) &&
              (!Md->reduce_over_ranks || (Md->full_maps && Md->fold_p1_off && nvec == 0 && !env_int("MI355_NO_FOLD_SHARDED_NN", 0))) &&
-             !Ad->scale && Md->scale && Ad->same_maps(*Md) && Ad->ntiles > 0 && Ad->max_ld <= GEMV_PANEL && Ad->maps.slot_width <= 4 &&
+             !Ad->scale && Md->scale && Ad->same_maps(*Md) && Ad->ntiles > 0 && Ad->max_ld <= GEMV_PANEL && Md->max_ld <= GEMV_PANEL &&
+             Ad->maps.slot_width <= 4 &&
+             // fp32-stored ΠS: folded when it is a local operator (one GPU, or replicated beside a sharded S); a SHARDED
+             // fp32 ΠS takes the unfolded loop (plain applies + all-reduce) — its launch has no peer-exchange form
+             !(Md->f32() && Md->reduce_over_ranks) &&
              (Ad->max_ld + 64 * Ad->waves - 1) / (64 * Ad->waves) <= 8 && (Md->max_ld + 64 * Md->waves - 1) / (64 * Md->waves) <= 8;
     }
     const double *dv = nullptr;
@@ -321,7 +325,7 @@ struct Krylov {
 #ifndef MI355_EXPERIMENTAL
     return nullptr;
 #else
-    if (!fold || nvec > 0 || eig.tag || ctx->has_comm() || Ad->reduce_over_ranks || !env_int("MI355_RESIDENT", 0) || env_int("MI355_NO_RESIDENT", 0)) return nullptr;
+    if (!fold || Md->f32() || nvec > 0 || eig.tag || ctx->has_comm() || Ad->reduce_over_ranks || !env_int("MI355_RESIDENT", 0) || env_int("MI355_NO_RESIDENT", 0)) return nullptr;
     auto &slot = ws.resident[{A, M}];
     if (!slot) slot.reset(new ResidentPlan(ctx, *Ad, *Md));
     return slot->usable ? slot.get() : nullptr;
@@ -329,7 +333,8 @@ struct Krylov {
   }
   // peer exchange with the waits inside the launches: every sharded operator of the loop stores into the arenas itself
   bool inwait() const {
-    return fold && ctx->peer_inwait && ctx->use_peer() && (Ad->reduce_over_ranks || Md->reduce_over_ranks) &&
+    // (an fp32-stored ΠS launch cannot wait inside itself: the one-wave wait kernel runs behind the S launch instead)
+    return fold && !Md->f32() && ctx->peer_inwait && ctx->use_peer() && (Ad->reduce_over_ranks || Md->reduce_over_ranks) &&
            (!Ad->reduce_over_ranks || (Ad->xt_on() && Ad->xt_direct)) && (!Md->reduce_over_ranks || (Md->xt_on() && Md->xt_direct));
   }
   PcgFold fold_args(int phase) const {

@@ -117,18 +117,30 @@ end
 
 """`NeumannNeumannSchurPreconditioner(ctx, ΠSd, ind_Γd_Γ2l, node_Γ_cnt)`: a method added to the constructor of Fem's
 own struct (EPDD.jl:1111-1137; its fields are `ΠSd`, `ind_Γd_Γ2l`, `node_Γ_cnt`): with a `MiContext` in front the blocks
-go to the device and a `MiOperator` comes back, usable wherever the reference uses `Πnn \\ r` / `ldiv!` (:1389-1403)."""
+go to the device and a `MiOperator` comes back, usable wherever the reference uses `Πnn \\ r` / `ldiv!` (:1389-1403).
+`storage=Float32` holds the blocks as fp32 on the device (rounded once; the apply and the solvers stay fp64, half the
+bytes are streamed) — storage only, unlike `Cholesky32` of MyPreconditioners/CholPreconditioners.jl:32-56, which also
+solves in fp32."""
 function NeumannNeumannSchurPreconditioner(ctx::MiContext, ΠSd::Vector{Matrix{Float64}},
                                            ind_Γd_Γ2l::Vector{Dict{Int,Int}}, node_Γ_cnt::Vector{Int};
-                                           dom_range=(0, length(ΠSd)))
+                                           dom_range=(0, length(ΠSd)), storage::Type=Float64)
+  storage === Float64 || storage === Float32 || error("storage must be Float64 or Float32")
+  st = storage === Float32 ? 1 : 0   # MI_STORE_F32 / MI_STORE_F64
   ndom = length(ΠSd); g = flatten_maps(ind_Γd_Γ2l); nd = Int64[length(x) for x in g]
   cnt = Vector{Int64}(node_Γ_cnt)
   r = Ref{Ptr{Cvoid}}(C_NULL)
   GC.@preserve g ΠSd cnt begin
-    check(ccall((:mi_nn_create, lib), Cint,
-                (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Ptr{Int64}}, Ptr{Ptr{Float64}}, Ptr{Int64}, Cint, Int64, Int64, Ref{Ptr{Cvoid}}),
-                ctx.h, ndom, length(cnt), nd, ptrs(g), Ptr{Float64}[pointer(b) for b in ΠSd], cnt, 1,
-                dom_range[1], dom_range[2], r))
+    if st == 0
+      check(ccall((:mi_nn_create, lib), Cint,
+                  (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Ptr{Int64}}, Ptr{Ptr{Float64}}, Ptr{Int64}, Cint, Int64, Int64, Ref{Ptr{Cvoid}}),
+                  ctx.h, ndom, length(cnt), nd, ptrs(g), Ptr{Float64}[pointer(b) for b in ΠSd], cnt, 1,
+                  dom_range[1], dom_range[2], r))
+    else
+      check(ccall((:mi_nn_create_stored, lib), Cint,
+                  (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Ptr{Int64}}, Ptr{Ptr{Float64}}, Ptr{Int64}, Cint, Int64, Int64, Cint, Ref{Ptr{Cvoid}}),
+                  ctx.h, ndom, length(cnt), nd, ptrs(g), Ptr{Float64}[pointer(b) for b in ΠSd], cnt, 1,
+                  dom_range[1], dom_range[2], st, r))
+    end
   end
   wrap(ctx, r)
 end
