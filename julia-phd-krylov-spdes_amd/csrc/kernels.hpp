@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "exchange_dev.hpp"
+#include "spmv_blocks.hpp"
 
 namespace mi {
 
@@ -177,14 +178,7 @@ __global__ __launch_bounds__(NT) void k_diag_apply(int n, const double *__restri
 // `y[rowval[k]] += nzval[k]*x[j]`, j ascending), so y is bit-identical to it.
 // Row blocks are dealt to XCDs in contiguous ranges (blockIdx % 8 selects the range) so that each
 // XCD's L2 caches one slice of x instead of all of it.
-#ifndef MI355_SPMV_TILE
-#define MI355_SPMV_TILE 1024   // 512..4096 swept on MI355X at 250k DoF: 1024 gives the shortest launch (profiles/)
-#endif
-constexpr int SPMV_TILE = MI355_SPMV_TILE;
-
-struct SpmvBlock {  // one record per row block: rows [r0, r1), non-zeros [k0, k1)
-  int r0, r1, k0, k1;
-};
+// SPMV_TILE, the block record SpmvBlock and the partition of the rows into blocks: spmv_blocks.hpp (host code, no HIP).
 
 template <int MODE, bool DOT>  // MODE 0: y = A x, 1: y = yin - A x;  DOT: also part[b] = Σ_{rows of block b} w[r]*y[r]
 __global__ __launch_bounds__(NT) void k_spmv_csr(int nblocks, const SpmvBlock *__restrict__ blk,

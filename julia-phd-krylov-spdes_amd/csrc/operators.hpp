@@ -131,34 +131,16 @@ struct CsrDev {
   DevBuf<int> xcd_row;  // [9] first row of the row blocks that run on XCD x (x = blockIdx & 7); [8] = n_rows
   DevBuf<double> val;
   std::vector<SpmvBlock> blocks_h;
+  std::vector<int> xcd_row_h;
   // `breaks` (ascending row indices): a row block never crosses one of them (per-subdomain partial sums)
   void upload(const HostCsr &h, hipStream_t s, const std::vector<int> *breaks = nullptr) {
     n_rows = h.n_rows; n_cols = h.n_cols; nnz = h.nnz();
-    // Greedy row blocks of <= SPMV_TILE non-zeros (a longer row stands alone). A block prefers to start at
-    // an even non-zero offset (paired loads in the kernel): if the greedy end lands on an odd offset, give
-    // back up to three rows to reach an even one.
-    std::vector<SpmvBlock> blocks;
-    int r = 0;
-    size_t nb = 0;
-    while (r < n_rows) {
-      while (breaks && nb < breaks->size() && (*breaks)[nb] <= r) ++nb;
-      const int limit = (breaks && nb < breaks->size()) ? std::min((*breaks)[nb], n_rows) : n_rows;
-      int e = r + 1;
-      while (e < limit && h.rowptr[e + 1] - h.rowptr[r] <= SPMV_TILE) ++e;
-      if (e < limit && (h.rowptr[e] & 1))
-        for (int back = 1; back <= 3 && e - back > r; ++back)
-          if ((h.rowptr[e - back] & 1) == 0) { e -= back; break; }
-      blocks.push_back(SpmvBlock{r, e, h.rowptr[r], h.rowptr[e]});
-      r = e;
-    }
+    // greedy row blocks and the rows whose blocks run on XCD x (spmv_blocks.hpp)
+    const std::vector<SpmvBlock> blocks = spmv_row_blocks(n_rows, h.rowptr.data(), breaks);
     nblocks = (int)blocks.size();
     blocks_h = blocks;
-    {  // rows whose blocks run on XCD x (k_spmv_csr deals block b = (blockIdx & 7) * per + (blockIdx >> 3))
-      const int per = (nblocks + 7) >> 3;
-      std::vector<int> xr(9, n_rows);
-      for (int x = 0; x < 8; ++x) xr[x] = x * per < nblocks ? blocks[(size_t)x * per].r0 : n_rows;
-      xcd_row.upload(xr, s);
-    }
+    xcd_row_h = spmv_xcd_rows(blocks, n_rows);
+    xcd_row.upload(xcd_row_h, s);
     std::vector<int> rp = h.rowptr;
     if (rp.empty()) rp.push_back(0);
     rowptr.upload(rp, s); col.upload(h.col, s); val.upload(h.val, s); blk.upload(blocks, s);
@@ -755,9 +737,7 @@ struct InteriorCg {
   // then into runs of <= `rows_per` rows; workgroup k works on XCD k & 7, so the pieces are interleaved per XCD.
   void build_fold(const HostCsr &a, const std::vector<int> &b0, const std::vector<int> &b1) {
     hipStream_t s = ctx->stream;
-    const int per = (A.nblocks + 7) >> 3;
-    std::vector<int> xr(9, n);
-    for (int x = 0; x < 8; ++x) xr[x] = x * per < A.nblocks ? A.blocks_h[(size_t)x * per].r0 : n;
+    const std::vector<int> &xr = A.xcd_row_h;
     const int target = std::max(256, env_int("MI355_ICG_PIECES", 512));   // about this many pieces in all
     const int rows_per = std::max(NT, (n + target - 1) / target);
     std::vector<std::vector<IcgPiece>> per_xcd(8);
@@ -873,8 +853,10 @@ struct InteriorCg {
       graph_x = x;
     }
     const long long max_replays = (long long)n / chunk + 2;  // maxiter = size(A, 2)
+    long long replays = 0;
+    bool all = false;
     for (long long l = 0; l <= max_replays; ++l) {
-      bool all = true;
+      all = true;
       if (folded) {
         MI_HIP(hipMemcpyAsync(dst_host, dst.p, sizeof(IcgDomState) * ndl, hipMemcpyDeviceToHost, s));   // cur[]
         MI_HIP(hipStreamSynchronize(s));
@@ -886,8 +868,16 @@ struct InteriorCg {
       }
       if (all) break;
       MI_HIP(hipGraphLaunch(graph, s));
-      total_iterations += chunk;
+      ++replays;
     }
+    // k_icg_spmv meets the stop rule one launch after the iteration that reached it, so the 2-launch form may replay once
+    // more than its iterations fill: count the replays the slowest subdomain's own iterations needed, like the 3-launch form
+    if (folded && all) {
+      long long it_max = 0;
+      for (int d = 0; d < ndl; ++d) it_max = std::max<long long>(it_max, dst_host[d].it);
+      replays = std::min(replays, (it_max + chunk - 1) / chunk);
+    }
+    total_iterations += replays * chunk;
   }
 };
 
