@@ -628,6 +628,7 @@ int mi_op_apply(mi_op_t op, const double *x, double *y) {
     mi_ctx_s *c = op->impl->ctx;
     c->use();
     const size_t n = (size_t)op->impl->n;
+    if (n == 0) return MI_OK;   // an empty operator: nothing to copy or launch (its staging buffers were never allocated)
     if (c->ptr_mode == MI_PTR_DEVICE) {
       op->impl->apply(x, y, nullptr);
       return MI_OK;

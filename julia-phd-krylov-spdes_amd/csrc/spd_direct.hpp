@@ -252,11 +252,12 @@ struct SpdDirectOp : Operator {
     dinv.alloc((size_t)pl.d_total); G.alloc((size_t)pl.b_total); ZT.alloc((size_t)ns * ns);
     y.alloc((size_t)pl.piece_ptr.back()); slotv.alloc((size_t)pl.sig_idx.size()); sink.alloc((size_t)n + 1);
     flag.alloc(2);
-    const size_t lds = sd_lds_bytes(std::max(P, std::min(ns, spd::P_MAX)));
-    if (lds > 65536) {
-      MI_HIP(hipFuncSetAttribute((const void *)k_sd_factor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      MI_HIP(hipFuncSetAttribute((const void *)k_sd_invert, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    // The attribute belongs to the function, not to this operator, and the last value set holds: with it set to this
+    // operator's own need, the set_values of another live operator that needs more would launch above it. Both kernels
+    // are therefore always allowed the most any operator can ask for (P or |Σ| = P_MAX: 132 KiB of the 160 KiB).
+    const int lds = (int)sd_lds_bytes(spd::P_MAX);
+    MI_HIP(hipFuncSetAttribute((const void *)k_sd_factor, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    MI_HIP(hipFuncSetAttribute((const void *)k_sd_invert, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     if (nzval) {
       DevBuf<double> v;
       v.upload(nzval, (size_t)nnz, s);

@@ -2,7 +2,8 @@
 // Usage: spd_direct_check P SIGMA_MAX FILE...   FILE: "n nnz" then colptr (n + 1) and rowval (nnz), 0-based, whitespace
 // separated. For every file it checks that each node is in exactly one piece or in Σ, that no edge joins two different
 // pieces, that pieces have at most P nodes, that Σ_i, the slots and the entry destinations are consistent, and that a
-// second run gives the identical plan. Prints one JSON line per file (with the node -> piece map, -1 = Σ);
+// second run gives the identical plan. Prints one JSON line per file (pieces, |Σ|, orphans, single-node pieces, pieces
+// without a Σ neighbour, and the node -> piece map, -1 = Σ);
 // exit code 0 when every check holds.
 #include <cstdio>
 #include <cstdlib>
@@ -88,8 +89,14 @@ int main(int argc, char **argv) {
         if (a.dst[k] >= 0 && (a.dst[k] >= a.work_total() || !d.insert(a.dst[k]).second)) { why.push_back("destinations"); break; }
     }
     if (!why.empty()) ++bad;
-    std::printf("{\"file\": \"%s\", \"status\": %d, \"n\": %lld, \"pieces\": %d, \"sigma\": %d, \"orphans\": %d, \"ok\": %s, \"why\": \"%s\", \"piece_of\": [",
-                argv[f], st, n, a.n_pieces(), a.n_sigma(), (int)a.orphan.size(), why.empty() ? "true" : "false",
+    int singles = 0, isolated = 0;   // pieces of one node; pieces without a Σ neighbour
+    for (int i = 0; i < a.n_pieces(); ++i) {
+      singles += a.piece_ptr[i + 1] - a.piece_ptr[i] == 1;
+      if (st == OK) isolated += a.sig_ptr[i + 1] == a.sig_ptr[i];
+    }
+    std::printf("{\"file\": \"%s\", \"status\": %d, \"n\": %lld, \"pieces\": %d, \"sigma\": %d, \"orphans\": %d, \"singles\": %d, "
+                "\"isolated\": %d, \"ok\": %s, \"why\": \"%s\", \"piece_of\": [",
+                argv[f], st, n, a.n_pieces(), a.n_sigma(), (int)a.orphan.size(), singles, isolated, why.empty() ? "true" : "false",
                 why.empty() ? "" : why[0].c_str());
     for (int v = 0; v < n; ++v) std::printf(v ? ", %d" : "%d", a.piece_of[v]);
     std::printf("]}\n");

@@ -5,7 +5,8 @@ Not a conftest: test modules import it. Everything here runs on the host.
   ladder(...)         A_IIdd, A_IΓdd, A_ΓΓdd of one subdomain whose breadth-first levels from Γ have exactly the requested
                       widths, coupling degrees, in-level density and Γ couplings (SPD by diagonal dominance).
   direct_inverse(...) one level T = Q diag(λ) Q', B = I, A_ΓΓ = 2 ‖T^-1‖ I: S_d = A_ΓΓ - T^-1 shows the Gauss-Jordan inverse.
-  reference(...)      S_d, w_d and A_II^-1 f from SuperLU refined with long-double residuals, and κ(T_k) of every level.
+  refined_solve(...)  A^-1 R from SuperLU refined with long-double residuals (also the reference of tests/spd_graphs.py).
+  reference(...)      S_d, w_d and A_II^-1 f from refined_solve, and κ(T_k) of every level.
   gj_emulate(...)     numpy copy of the device's blocked Gauss-Jordan inversion (64-wide pivot blocks inverted by 4 x 4
                       block steps with gj_inv4's arithmetic), to tell the algorithm's rounding from a kernel's.
 """
@@ -143,7 +144,7 @@ def empty_interior(n_gamma=5, seed=3):
                  np.zeros(0), np.zeros(0), [], "n_I = 0")
 
 
-def _refined_solve(A, R, max_it=8):
+def refined_solve(A, R, max_it=8):
     """A^-1 R (R dense, columns) by SuperLU in float64, refined with residuals in long double until the correction is below
     1e-18 relative (or stops shrinking). Returns long-double columns."""
     lu = spla.splu(sp.csc_matrix(A), permc_spec="MMD_AT_PLUS_A", diag_pivot_thresh=1.0)
@@ -196,7 +197,7 @@ def reference(s: Synth) -> Ref:
     if nI == 0:
         return Ref(Gd.copy(), 0.0, np.zeros(nG), np.zeros(0), 1.0, 0, [])
     B = s.A_IΓ.toarray()
-    X = _refined_solve(s.A_II, np.column_stack([B, s.b_I, s.f]))
+    X = refined_solve(s.A_II, np.column_stack([B, s.b_I, s.f]))
     Bl = B.astype(np.longdouble)
     BX = Bl.T @ X[:, :nG]
     S = Gd.astype(np.longdouble) - BX
