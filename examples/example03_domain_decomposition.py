@@ -6,7 +6,10 @@ device library. Mesh/partition are the structured substitutes (no Triangle / MET
 interior solves of the set-up are direct, the least-dominant eigenvectors come from a dense `eigh`
 on the host instead of KrylovKit (Example03:209).
 
-    python examples/example03_domain_decomposition.py [--N 100 --px 2 --py 2]
+    python examples/example03_domain_decomposition.py [--N 100 --px 2 --py 2] [--lorasc]
+
+`--lorasc` adds Example03:245-256: `prepare_lorasc_precond` (host, dense generalized eigenpairs of (S, A_ΓΓ)) and
+`pcg(A, b, zeros, ΠA_lorasc)` with the device LORASC preconditioner.
 """
 import argparse
 import os
@@ -26,6 +29,7 @@ def main():
     ap.add_argument("--N", type=int, default=100)      # tentative_nnode = N*N (Example03:16: 40_000)
     ap.add_argument("--px", type=int, default=2)
     ap.add_argument("--py", type=int, default=2)       # ndom = px*py (Example03:19: 20)
+    ap.add_argument("--lorasc", action="store_true", help="also run the LORASC leg, Example03:245-256")
     args = ap.parse_args()
     pkg = graft.load_package()
     fem, api = pkg.fem, pkg.api
@@ -68,6 +72,21 @@ def main():
     for tag, ϕ in (("ld", V[:, :nev]), ("md", V[:, -nev:])):
         u_Γ, it, _ = api.defpcg(S_local_mat, b_schur, np.zeros(n_Γ), np.asfortranarray(ϕ), ΠSnn_local_mat)  # :214, :224
         print(f"{tag}-def-neumann-neumann-pcg: n = {S_local_mat.N}, ndom = {ndom}, nev = {nev} ({tag}), iter = {it}")
+
+    if args.lorasc:
+        t = time.time()
+        E, Σ = fem.prepare_lorasc_precond(Sdense, A_ΓΓ)                                                # Example03:246-252
+        setup = api.SchurSetup(ctx, P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd)                                      # cholesky(A_IId), EPDD.jl:1535-1537
+        setup.keep_levels()
+        setup.run()
+        chol_A_ΓΓ = api.SparseDirectPreconditioner(ctx, A_ΓΓ)                                         # cholesky(A_ΓΓ), EPDD.jl:1525
+        ΠA_lorasc = api.LorascPreconditioner(ctx, A_IΓd, (sub, P.dinds), setup, chol_A_ΓΓ, E)
+        print(f"prepare_lorasc_precond ... {time.time() - t:.2f} seconds, nev = {E.shape[1]}")
+        A_dev = api.SparseMatrixCSC(ctx, A)
+        u, it, _ = api.pcg(A_dev, b, np.zeros(b.size), ΠA_lorasc)                                      # Example03:255
+        print(f"lorasc-pcg: n = {A.shape[0]}, ndom = {ndom}, iter = {it}")                             # :256
+        e = fem.append_bc(P.dinds, u, mesh.points, uexact) - u_no_dd
+        print(f"extrema(u_lorasc - u_no_dd) = ({e.min():.3e}, {e.max():.3e})")
 
 
 if __name__ == "__main__":

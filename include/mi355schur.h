@@ -382,6 +382,40 @@ int mi_schur_setup_keep_levels(mi_setup_t plan, int on);
 int mi_schur_setup_interior_solve(mi_setup_t plan, const double *f, double *u);
 int mi_schur_matfree_interior_levels(mi_op_t op, mi_setup_t plan);
 int mi_schur_setup_destroy(mi_setup_t plan);
+
+/* mi_lorasc_create — the reference's `LorascPreconditioner` (EPDD.jl:1406-1428) with `apply_lorasc` (EPDD.jl:1908-1976) as
+ * its apply: the M of `pcg(A, b, zeros, ΠA_lorasc)` and `defpcg(A, b, zeros, ϕ, ΠA_lorasc)` on the FULL system
+ * (Example03:245-268; Examples 06, 09, 17), n = Σ n_i + n_gamma. With x indexed like the rows of A
+ * (`not_dirichlet_inds_g2l`):
+ *     y_Id = A_IId \ x_Id;  z_Γ = x_Γ - Σ_d A_IΓd' y_Id  (d ascending)         (EPDD.jl:1935-1942)
+ *     x_Γ  = A_ΓΓ \ z_Γ                                                        (EPDD.jl:1950, the Cholesky branch)
+ *     x_Γ += Σ_k coef[k] (E[:,k]' z_Γ) E[:,k]                (k ascending)      (EPDD.jl:1954-1957)
+ *     u_Id = y_Id - A_IId \ (A_IΓd x_Γ);  u_Γ = x_Γ                             (EPDD.jl:1959-1973)
+ * Both solves are exact and already on the device: `interior` is a set-up plan with mi_schur_setup_keep_levels(plan, 1) and
+ * a run after it (all A_IId at once), `a_gg_solver` a mi_spd_direct operator of size n_gamma. The operator borrows both:
+ * while it is alive, mi_schur_setup_destroy(interior), mi_schur_setup_keep_levels(interior, 0) and
+ * mi_op_destroy(a_gg_solver) return MI_ERR_BAD_ARG and change nothing. A later mi_schur_setup_run /
+ * mi_spd_direct_set_values moves them, and with them this operator, to a new realization. The apply is plain launches (two
+ * level solves, the A_ΓΓ solve, five small kernels), no atomics, fixed summation orders: bitwise reproducible, captured into
+ * the solvers' graphs.
+ *   create: HOST arrays, `index_base`-based. n_i[d] as in the plan; pos_I[d][i] / pos_gamma[g]: the row of A of interior
+ *           node i of subdomain d / of Γ node g (together a permutation of the n rows); ig_*[d]: the CSC arrays of A_IΓd,
+ *           n_i[d] x n_gamma with Γ-GLOBAL columns (`prepare_global_schur`, EPDD.jl:212-369); E: n_gamma x nev, column-major
+ *           (NULL with nev = 0); nev <= 1024.
+ *   coef:   NULL means ones — the reference AS WRITTEN: its loop `for (k, σ) in enumerate(Πlorasc.Σ)` (EPDD.jl:1954) never
+ *           uses σ, although prepare_lorasc_precond stores Σ[k] = (ε - σ_k)/σ_k (EPDD.jl:1596) beside A_ΓΓ-orthonormal
+ *           E[k]. The correction of Grigori, Nataf and Yousef is coef = Σ.
+ *   mi_lorasc_set_values: the concatenated CSC nzval of all A_IΓd for a new realization (host or device pointer per the
+ *           context's pointer mode); mi_lorasc_set_correction: new nev, E, coef (same pointer rule; coef NULL: ones).
+ * MI_ERR_BAD_ARG with a message: maps that are no permutation, an n_i that differs from the plan's, a plan without kept
+ * levels, an a_gg_solver that is no sparse direct operator of size n_gamma, indices out of range, nev above 1024, a context
+ * that is one rank of several (the operator is replicated only). The AMG/CG branch of EPDD.jl:1946 is not provided. */
+int mi_lorasc_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma, const int64_t *n_i,
+                     const int64_t *const *pos_I, const int64_t *pos_gamma, const int64_t *const *ig_colptr,
+                     const int64_t *const *ig_rowval, const double *const *ig_nzval, mi_setup_t interior,
+                     mi_op_t a_gg_solver, int64_t nev, const double *E, const double *coef, int index_base, mi_op_t *op);
+int mi_lorasc_set_values(mi_op_t op, const double *ig_val);
+int mi_lorasc_set_correction(mi_op_t op, int64_t nev, const double *E, const double *coef);
 int mi_nn_pinv(mi_ctx_t ctx, int64_t ndom, const int64_t *n_gamma_d, const double *Sd, double rtol, double *PiSd);
 int mi_dense_set_blocks(mi_op_t op, const double *blocks);
 

@@ -95,6 +95,10 @@ SIGNATURES = {
     "mi_schur_setup_create": [vp, i64, i64p, i64p, i64pp, i64pp, i64pp, i64pp, i64pp, i64pp, C.c_int, C.POINTER(vp)],
     "mi_schur_setup_run": [vp, vp, vp, vp, vp, vp, vp],
     "mi_schur_setup_destroy": [vp],
+    "mi_lorasc_create": [vp, i64, i64, i64, i64p, i64pp, i64p, i64pp, i64pp, f64pp, vp, vp, i64, f64p, f64p, C.c_int,
+                         C.POINTER(vp)],
+    "mi_lorasc_set_values": [vp, vp],
+    "mi_lorasc_set_correction": [vp, i64, vp, vp],
     "mi_nn_pinv": [vp, i64, i64p, vp, C.c_double, vp],
     "mi_dense_set_blocks": [vp, vp],
     "mi_schur_matfree_rhs": [vp, vp, vp, vp],

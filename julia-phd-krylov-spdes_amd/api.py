@@ -431,6 +431,89 @@ class SparseDirectPreconditioner(Operator):
         return int(a.value), int(b.value)
 
 
+class LorascPreconditioner(Operator):
+    """The reference's `LorascPreconditioner` with `apply_lorasc` as its apply (EPDD.jl:1406-1428, 1908-1976): `M` of
+    `pcg(A, b, zeros, ΠA_lorasc)` and `defpcg(A, b, zeros, ϕ, ΠA_lorasc)` on the full system (Example03:245-268), on the
+    device (`mi_lorasc_create`).
+
+    `A_IΓd`: the blocks of `prepare_global_schur` (Γ-global columns). `sub_or_maps`: where the unknowns sit in the rows of
+    `A` — `(pos_I, pos_Γ)` (per subdomain the row of every interior node, and the row of every Γ node), or `(sub, dinds)`,
+    or anything with `.sub` and `.dinds` (a `fem.SchurProblem`). `setup`: a `SchurSetup` of the same subdomains with
+    `keep_levels()` and a `run()` after it (the exact `A_IId \\ f`); `A_ΓΓ_solver`: a `SparseDirectPreconditioner` of A_ΓΓ.
+    Both are kept alive by this object and cannot be closed before it. `E` (n_Γ x nev) and `coef` (nev) are the low-rank
+    correction x_Γ += Σ_k coef_k (E_k' z_Γ) E_k; `coef=None` is ones — the reference as written, whose loop never uses the
+    Σ that `prepare_lorasc_precond` stores (EPDD.jl:1954-1957, 1596); pass `coef=Σ` for the correction of the paper."""
+
+    def __init__(self, ctx: Context, A_IΓd, sub_or_maps, setup: "SchurSetup", A_ΓΓ_solver: "SparseDirectPreconditioner",
+                 E=None, coef=None, index_base: int = 0):
+        pos_I, pos_Γ = _lorasc_maps(sub_or_maps)
+        ndom = len(A_IΓd)
+        if len(pos_I) != ndom:
+            raise ValueError("one interior map per subdomain expected")
+        n_i = _i64([len(p) for p in pos_I])
+        pI = [_i64(p) + index_base for p in pos_I]
+        pΓ = _i64(pos_Γ) + index_base
+        n_Γ = int(pΓ.size)
+        igp, igi, igv = _csc_parts(A_IΓd, 0, ndom, index_base)
+        nev, Ea, ca = _lorasc_correction(n_Γ, E, coef)
+        h = vp()
+        check(ctx._L.mi_lorasc_create(
+            ctx._h, i64(ndom), i64(int(n_i.sum()) + n_Γ), i64(n_Γ), n_i.ctypes.data_as(i64p), _ptrs(pI, i64p),
+            pΓ.ctypes.data_as(i64p), _ptrs(igp, i64p), _ptrs(igi, i64p), _ptrs(igv, f64p), setup._h, A_ΓΓ_solver._h, i64(nev),
+            Ea.ctypes.data_as(f64p) if nev else None, ca.ctypes.data_as(f64p) if ca is not None else None,
+            C.c_int(index_base), C.byref(h)))
+        super().__init__(ctx, h, keep=(setup, A_ΓΓ_solver))
+        self.setup, self.A_ΓΓ_solver = setup, A_ΓΓ_solver
+        self.n_Γ, self.nev, self.nnz = n_Γ, nev, int(sum(v.size for v in igv))
+
+    def set_values(self, ig_val) -> None:
+        """The concatenated CSC `nzval` of all A_IΓd of a new realization: numpy array or torch CUDA tensor
+        (`mi_lorasc_set_values`). The interior and A_ΓΓ factors move with `setup.run(...)` / `A_ΓΓ_solver.set_values(...)`."""
+        self.ctx._mode_for(ig_val)
+        k, p = self.ctx._ptr(ig_val, self.nnz)
+        self.ctx._order((k,), after=False)
+        check(self.ctx._L.mi_lorasc_set_values(self._h, p))
+
+    def set_correction(self, E=None, coef=None) -> None:
+        """A new low-rank correction (`mi_lorasc_set_correction`); `E=None` removes it."""
+        nev, Ea, ca = _lorasc_correction(self.n_Γ, E, coef)
+        self.ctx._mode_for(Ea)
+        check(self.ctx._L.mi_lorasc_set_correction(self._h, i64(nev), vp(Ea.ctypes.data) if nev else None,
+                                                   vp(ca.ctypes.data) if ca is not None else None))
+        self.nev = nev
+
+    def close(self) -> None:
+        super().close()                 # before the plan and the A_ΓΓ solver it borrows
+        self._keep = ()
+
+
+def _lorasc_maps(sub_or_maps):
+    if hasattr(sub_or_maps, "sub") and hasattr(sub_or_maps, "dinds"):
+        sub_or_maps = (sub_or_maps.sub, sub_or_maps.dinds)
+    a, b = sub_or_maps
+    if hasattr(a, "node_Id") and hasattr(b, "not_dirichlet_g2l"):
+        g2l = b.not_dirichlet_g2l
+        return [g2l[nodes] for nodes in a.node_Id], g2l[a.node_Γ]
+    return list(a), b
+
+
+def _lorasc_correction(n_Γ: int, E, coef):
+    if E is None:
+        return 0, np.empty(0), None
+    Ea = np.asarray(E, dtype=np.float64)
+    Ea = Ea.reshape(n_Γ, -1) if Ea.ndim == 1 else Ea
+    if Ea.shape[0] != n_Γ:
+        raise ValueError(f"E has {Ea.shape[0]} rows, n_Γ is {n_Γ}")
+    nev = int(Ea.shape[1])
+    Ea = np.ascontiguousarray(Ea.T).ravel()          # column-major n_Γ x nev
+    ca = None
+    if coef is not None and nev:
+        ca = _f64(coef).ravel()
+        if ca.size != nev:
+            raise ValueError(f"coef has {ca.size} entries for {nev} vectors")
+    return nev, Ea, ca
+
+
 def _dom_slice(ctx: Context, ndom: int, dom_slice):
     if dom_slice is None:
         return shard_domains(ndom, ctx.rank, ctx.n_ranks)
@@ -902,6 +985,10 @@ def apply_global_schur(S: GlobalSchur, x):
 
 def apply_neumann_neumann_schur(Πnn: NeumannNeumannSchurPreconditioner, r):
     return Πnn.apply(r)
+
+
+def apply_lorasc(Πlorasc: LorascPreconditioner, x):
+    return Πlorasc.apply(x)
 
 
 # ------------------------------------------------------------------ solvers

@@ -7,6 +7,7 @@
 #include "eig_solvers.hpp"
 #include "setup_gj.hpp"
 #include "spd_direct.hpp"
+#include "lorasc.hpp"
 
 namespace mi {
 
@@ -546,6 +547,43 @@ int mi_spd_direct_stats(mi_op_t op, int64_t *pieces, int64_t *separator) {
   return MI_OK;
 }
 
+
+static LorascOp *as_lorasc(mi_op_t op) { return op && op->impl ? dynamic_cast<LorascOp *>(op->impl.get()) : nullptr; }
+int mi_lorasc_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma, const int64_t *n_i, const int64_t *const *pos_I,
+                     const int64_t *pos_gamma, const int64_t *const *ig_colptr, const int64_t *const *ig_rowval,
+                     const double *const *ig_nzval, mi_setup_t interior, mi_op_t a_gg_solver, int64_t nev, const double *E,
+                     const double *coef, int index_base, mi_op_t *op) {
+  MI_NEW_OP(ctx, op, new LorascOp(ctx, ndom, n, n_gamma, n_i, pos_I, pos_gamma, ig_colptr, ig_rowval, ig_nzval, interior, a_gg_solver,
+                                  nev, E, coef, index_base));
+}
+int mi_lorasc_set_values(mi_op_t op, const double *ig_val) {
+  LorascOp *l = as_lorasc(op);
+  if (!l || !ig_val) return fail(MI_ERR_BAD_ARG, "mi_lorasc_set_values: not a LORASC preconditioner, or NULL ig_val");
+  mi_ctx_s *c = l->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    DevBuf<double> st;
+    In vi(c, ig_val, (size_t)l->nnz, st);
+    l->set_values(vi.dev);
+    MI_HIP(hipStreamSynchronize(c->stream));   // the staging buffer goes out of scope
+    return MI_OK;
+  });
+}
+int mi_lorasc_set_correction(mi_op_t op, int64_t nev, const double *E, const double *coef) {
+  LorascOp *l = as_lorasc(op);
+  if (!l) return fail(MI_ERR_BAD_ARG, "mi_lorasc_set_correction: not a LORASC preconditioner");
+  mi_ctx_s *c = l->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    LorascOp::check_nev(nev, E, "mi_lorasc_set_correction");
+    MI_HIP(hipStreamSynchronize(c->stream));
+    for (auto &kv : c->workspaces) kv.second->drop_graphs_of(l);   // nev and the address of E are launch arguments of captured applies
+    if (c->ptr_mode == MI_PTR_DEVICE) l->set_correction_dev(nev, E, coef);
+    else l->set_correction_host(nev, E, coef, "mi_lorasc_set_correction");
+    return MI_OK;
+  });
+}
+
 int mi_schur_assembled_create(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d,
                               const int64_t *const *gather_idx, const double *const *Sd, int index_base,
                               int64_t dom_begin, int64_t dom_end, mi_op_t *op) {
@@ -730,6 +768,7 @@ int mi_op_time_dominant(mi_op_t op, const double *x, int reps, double *us_per_la
 
 int mi_op_destroy(mi_op_t op) {
   if (!op) return MI_OK;
+  if (op->bound > 0) return fail(MI_ERR_BAD_ARG, "mi_op_destroy: %d live LORASC operator(s) use this operator; destroy them first", op->bound);
   return guarded([&]() -> int {
     if (op->impl) {
       mi_ctx_s *c = op->impl->ctx;
@@ -1032,6 +1071,7 @@ int mi_schur_setup_run(mi_setup_t plan, const double *ii_val, const double *ig_v
 }
 int mi_schur_setup_keep_levels(mi_setup_t plan, int on) {
   if (!plan) return fail(MI_ERR_BAD_ARG, "plan is NULL");
+  if (!on && plan->bound > 0) return fail(MI_ERR_BAD_ARG, "mi_schur_setup_keep_levels: %d live LORASC operator(s) solve with the kept levels", plan->bound);
   return guarded([&]() -> int {
     plan->ctx->use();
 #ifdef MI355_EXPERIMENTAL
@@ -1076,6 +1116,7 @@ int mi_schur_matfree_interior_levels(mi_op_t op, mi_setup_t plan) {
 }
 int mi_schur_setup_destroy(mi_setup_t plan) {
   if (!plan) return MI_OK;
+  if (plan->bound > 0) return fail(MI_ERR_BAD_ARG, "mi_schur_setup_destroy: %d live LORASC operator(s) use this plan; destroy them first", plan->bound);
   return guarded([&]() -> int {
     plan->ctx->use();
     (void)hipStreamSynchronize(plan->ctx->stream);

@@ -1147,4 +1147,5 @@ struct GlobalSchurOp : Operator {
 struct mi_op_s {
   std::unique_ptr<mi::Operator> impl;
   mi::DevBuf<double> hx, hy;  // staging for host-pointer mode
+  int bound = 0;              // operators that borrow this one (lorasc.hpp): mi_op_destroy is refused while > 0
 };

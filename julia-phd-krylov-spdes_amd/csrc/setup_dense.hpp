@@ -146,6 +146,7 @@ struct mi_setup_s {
   std::vector<int> c_ptr_h, c_row_h, c_src_h;
   mi::DevBuf<int> c_ptr, c_row, c_src;
   std::unique_ptr<mi::GjState> gj;
+  int bound = 0;                         // operators that borrow this plan (lorasc.hpp): mi_schur_setup_destroy is refused while > 0
   ~mi_setup_s();
   void release_lanes() {
     for (auto &l : lanes) {

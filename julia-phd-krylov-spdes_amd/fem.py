@@ -840,6 +840,45 @@ def prepare_neumann_neumann_schur_precond(Sd: Sequence[np.ndarray]):
     return out
 
 
+def prepare_lorasc_precond(S, A_ΓΓ, nvec: int = 25, ε: float = 0.01):
+    """The low-rank correction of `prepare_lorasc_precond`, its `low_rank_correction = :exact` branch (EPDD.jl:1541-1617),
+    on the host: the `nvec` least dominant generalized eigenpairs S e = σ A_ΓΓ e by a dense `scipy.linalg.eigh(S, A_ΓΓ)`
+    in place of `KrylovKit.geneigsolve(..., nvec, :SR, isposdef=true)` (:1546-1549) — both leave `E' A_ΓΓ E = I`.
+    `S` is the dense Schur complement or a callable x -> S x. Returns `(E[:, :nev], Σ[:nev])`.
+
+    The selection (:1587-1610): pairs in ascending σ; the leading ones with σ < ε are counted as nev and their Σ[k]
+    becomes (ε - σ)/σ, the count stops at the first σ >= ε; nev == 0 -> nev = nvec (with untransformed Σ), as the
+    reference falls back; nev == nvec is kept (the reference only warns). ε <= 0 gives no correction (:1612-1615)."""
+    A = A_ΓΓ.toarray() if sp.issparse(A_ΓΓ) else np.asarray(A_ΓΓ, dtype=np.float64)
+    n = A.shape[0]
+    if ε <= 0:
+        return np.empty((n, 0)), np.empty(0)
+    if callable(S):
+        S = np.column_stack([S(e) for e in np.eye(n)])
+    S = np.asarray(S, dtype=np.float64)
+    nvec = min(int(nvec), n)
+    import scipy.linalg as sla
+    Σ, E = sla.eigh((S + S.T) / 2, (A + A.T) / 2, subset_by_index=[0, nvec - 1])
+    order = np.argsort(Σ, kind="stable")
+    Σ, E = Σ[order].copy(), E[:, order]
+    nev = 0
+    for k in range(nvec):
+        if Σ[k] < ε:
+            Σ[k] = (ε - Σ[k]) / Σ[k]
+            nev += 1
+        else:
+            break
+    if nev == 0:
+        nev = nvec
+    return np.asfortranarray(E[:, :nev]), Σ[:nev]
+
+
+def lorasc_maps(sub: Subdomains, dinds: DirichletInds):
+    """Rows of A (`not_dirichlet_inds_g2l`, EPDD.jl:1924, 1930) of every subdomain's interior nodes and of the Γ nodes."""
+    g2l = dinds.not_dirichlet_g2l
+    return [g2l[nodes] for nodes in sub.node_Id], g2l[sub.node_Γ]
+
+
 def get_schur_rhs(b_Id, A_IId, A_IΓd, b_Γ, gather_idx=None, solvers=None):
     """`get_schur_rhs` (EPDD.jl:798-821 global columns; :835-864 local columns + scatter)."""
     b = np.array(b_Γ, dtype=np.float64, copy=True)

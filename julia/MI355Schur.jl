@@ -26,14 +26,15 @@ import RecyclingKrylovSolvers: cg, pcg, defcg, defpcg, eigcg, eigpcg, eigdefcg, 
 import Fem
 import Fem: apply_local_schur, apply_local_schurs, apply_global_schur, apply_neumann_neumann_schur,
             get_schur_rhs, get_subdomain_solutions, NeumannNeumannSchurPreconditioner,
-            assemble_local_schurs, prepare_neumann_neumann_schur_precond
+            assemble_local_schurs, prepare_neumann_neumann_schur_precond,
+            LorascPreconditioner, prepare_lorasc_precond, apply_lorasc
 
 # new names only (none of them is exported by Fem or RecyclingKrylovSolvers)
 export MiContext, MiOperator, MiPrecond,
        LocalSchurs, LocalSchur, MatrixFreeLocalSchurs, GlobalSchur,
        AssemblyPlan, assemble!, set_values!, SchurSetup, set_blocks!, interior_precond!, interior_iterations,
        keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!,
-       SparseDirectPreconditioner, spd_direct_stats
+       SparseDirectPreconditioner, spd_direct_stats, MiLorasc, set_correction!
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -517,5 +518,83 @@ function spd_factor(ctx::MiContext, M::SparseMatrixCSC{Float64,Int})
 end
 pcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::SparseMatrixCSC{Float64,Int}; maxit=0) =
   solve(:pcg, A, spd_factor(A.ctx, M), b, x, nothing, maxit)
+
+# ---------------------------------------------------------------- LORASC (Example03:245-268)
+"""`MiLorasc`: the device form of Fem's `LorascPreconditioner` (EPDD.jl:1406-1428). `op` applies `apply_lorasc`
+(EPDD.jl:1908-1976) on the device; `plan` (the exact `A_IId \\ f` by level solves, in place of `chol_A_IId`) and `A_ΓΓ`
+(the sparse direct factor, in place of `chol_A_ΓΓ`) are borrowed by `op` and therefore kept in fields: the library
+refuses to destroy them while `op` lives."""
+mutable struct MiLorasc
+  op::MiOperator
+  plan::SchurSetup
+  A_ΓΓ::MiOperator
+  n_Γ::Int
+end
+
+function lorasc_maps(ind_Id_g2l::Vector{Dict{Int,Int}}, ind_Γ_g2l::Dict{Int,Int}, not_dirichlet_inds_g2l::Dict{Int,Int})
+  pI = [Vector{Int64}(undef, length(m)) for m in ind_Id_g2l]
+  for (d, m) in enumerate(ind_Id_g2l), (node, i) in m
+    pI[d][i] = not_dirichlet_inds_g2l[node]                  # EPDD.jl:1924
+  end
+  pΓ = Vector{Int64}(undef, length(ind_Γ_g2l))
+  for (node, g) in ind_Γ_g2l
+    pΓ[g] = not_dirichlet_inds_g2l[node]                     # EPDD.jl:1930
+  end
+  pI, pΓ
+end
+
+"""`LorascPreconditioner(ctx, A_IΓd, ind_Id_g2l, ind_Γ_g2l, not_dirichlet_inds_g2l, plan, A_ΓΓ_solver[, E, coef])`: a method
+added to the constructor of Fem's struct. `plan` is a `SchurSetup` of the same subdomains after `keep_levels!` and an
+`assemble_local_schurs(plan, …)`; `A_ΓΓ_solver = SparseDirectPreconditioner(ctx, A_ΓΓ)`; `E` the vectors of the low-rank
+correction as columns. `coef === nothing` applies them as the reference does — its loop never uses the Σ it stores
+(EPDD.jl:1954-1957, 1596); `coef = Σ` is the correction of the paper."""
+function LorascPreconditioner(ctx::MiContext, A_IΓd::Vector{SparseMatrixCSC{Float64,Int}}, ind_Id_g2l::Vector{Dict{Int,Int}},
+                              ind_Γ_g2l::Dict{Int,Int}, not_dirichlet_inds_g2l::Dict{Int,Int}, plan::SchurSetup,
+                              A_ΓΓ_solver::MiOperator, E::Matrix{Float64}=Matrix{Float64}(undef, length(ind_Γ_g2l), 0), coef=nothing)
+  ndom = length(A_IΓd); n_Γ = length(ind_Γ_g2l)
+  pI, pΓ = lorasc_maps(ind_Id_g2l, ind_Γ_g2l, not_dirichlet_inds_g2l)
+  ni = Int64[length(p) for p in pI]
+  igp, igi, igv = csc_parts(A_IΓd)
+  cf = coef === nothing ? C_NULL : Vector{Float64}(coef)
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  GC.@preserve pI igp igi igv begin
+    check(ccall((:mi_lorasc_create, lib), Cint,
+                (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Ptr{Int64}}, Ptr{Int64}, Ptr{Ptr{Int64}}, Ptr{Ptr{Int64}},
+                 Ptr{Ptr{Float64}}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+                ctx.h, ndom, sum(ni) + n_Γ, n_Γ, ni, ptrs(pI), pΓ, ptrs(igp), ptrs(igi), ptrs(igv), plan.h, A_ΓΓ_solver.h,
+                size(E, 2), E, cf, 1, r))
+  end
+  MiLorasc(wrap(ctx, r), plan, A_ΓΓ_solver, n_Γ)
+end
+
+"""`prepare_lorasc_precond(ctx, S, A_IId, A_IΓd, A_ΓΓ, ind_Id_g2l, ind_Γ_g2l, not_dirichlet_inds_g2l, A_IIdd, A_IΓdd, A_ΓΓdd;
+nvec, ε)`: Example03:246-252 with the factorizations on the device. The eigenpairs come from the reference's own host
+method with `compute_A_ΓΓ_chol`'s work skipped where it can be (its `E`, `Σ` fields are taken over as they are); the local
+blocks of `prepare_local_schurs` are needed for the level elimination that stands in for `cholesky(A_IId[idom])`."""
+function prepare_lorasc_precond(ctx::MiContext, S, A_IId, A_IΓd, A_ΓΓ::SparseMatrixCSC{Float64,Int}, ind_Id_g2l, ind_Γ_g2l,
+                                not_dirichlet_inds_g2l, A_IIdd, A_IΓdd, A_ΓΓdd; nvec=25, ε=.01, verbose=true)
+  Π = prepare_lorasc_precond(S, A_IId, A_IΓd, A_ΓΓ, ind_Id_g2l, ind_Γ_g2l, not_dirichlet_inds_g2l; nvec=nvec, ε=ε, verbose=verbose)
+  plan = SchurSetup(ctx, A_IIdd, A_IΓdd, A_ΓΓdd)
+  keep_levels!(plan)
+  assemble_local_schurs(plan, A_IIdd, A_IΓdd, A_ΓΓdd)
+  E = isempty(Π.Σ) ? Matrix{Float64}(undef, A_ΓΓ.n, 0) : reduce(hcat, Π.E[1:length(Π.Σ)])
+  LorascPreconditioner(ctx, A_IΓd, ind_Id_g2l, ind_Γ_g2l, not_dirichlet_inds_g2l, plan, SparseDirectPreconditioner(ctx, A_ΓΓ), E)
+end
+
+apply_lorasc(Π::MiLorasc, x::Vector{Float64}) = Π.op * x                                 # EPDD.jl:1908-1976
+\(Π::MiLorasc, x::Vector{Float64}) = apply_lorasc(Π, x)                                  # EPDD.jl:1980-1982
+ldiv!(z::Vector{Float64}, Π::MiLorasc, r::Vector{Float64}) = mul!(z, Π.op, r)            # EPDD.jl:1984-1988
+ldiv!(Π::MiLorasc, r::Vector{Float64}) = (r .= apply_lorasc(Π, copy(r)))                 # EPDD.jl:1990-1993
+"""New values of all A_IΓd (same patterns) for a new realization; the interior and A_ΓΓ factors move with
+`assemble_local_schurs(Π.plan, …)` and `set_values!(Π.A_ΓΓ, A_ΓΓ)`."""
+set_values!(Π::MiLorasc, A_IΓd::Vector{SparseMatrixCSC{Float64,Int}}) =
+  check(ccall((:mi_lorasc_set_values, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), Π.op.h, reduce(vcat, [A.nzval for A in A_IΓd])))
+"""A new low-rank correction: the columns of `E`, applied with `coef` (`nothing`: ones, the reference as written)."""
+set_correction!(Π::MiLorasc, E::Matrix{Float64}, coef=nothing) =
+  check(ccall((:mi_lorasc_set_correction, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}),
+              Π.op.h, size(E, 2), E, coef === nothing ? C_NULL : Vector{Float64}(coef)))
+pcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiLorasc; maxit=0) = solve(:pcg, A, M.op, b, x, nothing, maxit)   # Example03:255
+defpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, W::Matrix{Float64}, M::MiLorasc; maxit=0) =
+  solve(:defpcg, A, M.op, b, x, W, maxit)                                                                                        # Example03:262, 268
 
 end # module
