@@ -6,10 +6,18 @@ device library. Mesh/partition are the structured substitutes (no Triangle / MET
 interior solves of the set-up are direct, the least-dominant eigenvectors come from a dense `eigh`
 on the host instead of KrylovKit (Example03:209).
 
-    python examples/example03_domain_decomposition.py [--N 100 --px 2 --py 2] [--lorasc]
+    python examples/example03_domain_decomposition.py [--N 100 --px 2 --py 2] [--lorasc] [--nn-induced {reference,assembled}]
 
 `--lorasc` adds Example03:245-256: `prepare_lorasc_precond` (host, dense generalized eigenpairs of (S, A_ΓΓ)) and
 `pcg(A, b, zeros, ΠA_lorasc)` with the device LORASC preconditioner.
+
+`--nn-induced` adds Example03:300-319: `prepare_neumann_neumann_induced_precond`, then `defpcg(A, b, ϕ, M=ΠA_induced_nn)`
+with the least dominant eigenvectors of A and `pcg(A, b, M=ΠA_induced_nn)` on the full system. `reference` is the
+preconditioner as the reference applies it (EPDD.jl:2411: neither symmetric nor positive definite, "only seems to work with
+deflation"), `assembled` its symmetric positive definite form. ϕ is `lowest_eigvecs(A, ndom + 10)`: where the cut at
+ndom + 10 falls inside a repeated eigenvalue (the x <-> y symmetry of a square box partition gives pairs), the whole
+eigenspace is taken, so that the deflation space, and with it the printed `iter`, does not depend on the basis the
+eigensolver happens to return inside that eigenspace.
 """
 import argparse
 import os
@@ -24,13 +32,32 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as graft  # noqa: E402
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=100)      # tentative_nnode = N*N (Example03:16: 40_000)
     ap.add_argument("--px", type=int, default=2)
     ap.add_argument("--py", type=int, default=2)       # ndom = px*py (Example03:19: 20)
     ap.add_argument("--lorasc", action="store_true", help="also run the LORASC leg, Example03:245-256")
-    args = ap.parse_args()
+    ap.add_argument("--nn-induced", choices=("reference", "assembled"), default=None,
+                    help="also run the Neumann-Neumann induced leg, Example03:300-319, with this coupling (EPDD.jl:2411)")
+    return ap.parse_args(argv)
+
+
+def lowest_eigvecs(A, nev, extra=6, rtol=1e-8):
+    """The eigenvectors of the `nev` smallest eigenvalues of the SPD matrix A (Arpack.eigs(A, nev, :SM), Example03:311),
+    by shift-invert Lanczos at 0. An eigenvalue equal (to `rtol`) to the `nev`-th brings its eigenvectors along, up to
+    `extra` more: cutting through an eigenspace would leave the span of ϕ to the solver's choice of basis in it."""
+    lam, V = spla.eigsh(sp.csc_matrix(A), k=min(nev + extra, A.shape[0] - 1), sigma=0.0, which="LM")
+    order = np.argsort(lam)
+    lam, V = lam[order], V[:, order]
+    m = nev
+    while m < lam.size and lam[m] - lam[nev - 1] <= rtol * lam[nev - 1]:
+        m += 1
+    return np.asfortranarray(V[:, :m])
+
+
+def main(argv=None):
+    args = parse_args(argv)
     pkg = graft.load_package()
     fem, api = pkg.fem, pkg.api
     a = lambda x, y: 1.0 + 0 * x                        # Example03:63-65
@@ -87,6 +114,24 @@ def main():
         print(f"lorasc-pcg: n = {A.shape[0]}, ndom = {ndom}, iter = {it}")                             # :256
         e = fem.append_bc(P.dinds, u, mesh.points, uexact) - u_no_dd
         print(f"extrema(u_lorasc - u_no_dd) = ({e.min():.3e}, {e.max():.3e})")
+
+    if args.nn_induced:
+        t = time.time()
+        ΠSd = fem.prepare_neumann_neumann_induced_precond(P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd)                # Example03:299-308
+        setup = api.SchurSetup(ctx, P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd)                                      # cholesky(A_IIdd), EPDD.jl:2340
+        setup.keep_levels()
+        setup.run()
+        ΠA_induced_nn = api.NeumannNeumannInducedPreconditioner(ctx, P.A_IΓdd, (sub, P.dinds), sub.gather_idx, sub.node_Γ_cnt,
+                                                                ΠSd, setup, coupling=args.nn_induced)
+        print(f"prepare_neumann_neumann_induced_precond ... {time.time() - t:.2f} seconds")
+        A_dev = api.SparseMatrixCSC(ctx, A)
+        ϕ = lowest_eigvecs(A, nev)                                                                     # Example03:311
+        u, it, _ = api.defpcg(A_dev, b, np.zeros(b.size), ϕ, ΠA_induced_nn)                            # Example03:313
+        print(f"nn-induced-defpcg: n = {A.shape[0]}, ndom = {ndom}, nev = {ϕ.shape[1]}, coupling = {args.nn_induced}, iter = {it}")
+        u, it, _ = api.pcg(A_dev, b, np.zeros(b.size), ΠA_induced_nn)                                  # Example03:317
+        print(f"nn-induced-pcg: n = {A.shape[0]}, ndom = {ndom}, coupling = {args.nn_induced}, iter = {it}")   # :318
+        e = fem.append_bc(P.dinds, u, mesh.points, uexact) - u_no_dd
+        print(f"extrema(u_nn_induced - u_no_dd) = ({e.min():.3e}, {e.max():.3e})")
 
 
 if __name__ == "__main__":

@@ -416,6 +416,50 @@ int mi_lorasc_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma, con
                      mi_op_t a_gg_solver, int64_t nev, const double *E, const double *coef, int index_base, mi_op_t *op);
 int mi_lorasc_set_values(mi_op_t op, const double *ig_val);
 int mi_lorasc_set_correction(mi_op_t op, int64_t nev, const double *E, const double *coef);
+
+/* mi_nn_induced_create — the reference's `NeumannNeumannInducedPreconditioner` (EPDD.jl:2274-2285; prepared by
+ * `prepare_neumann_neumann_induced_precond`, EPDD.jl:2305-2353) with `apply_neumann_neumann_induced` (EPDD.jl:2363-2423) as
+ * its apply: the M of `defpcg(A, b, ϕ, M=ΠA_induced_nn_local_mat)` and `pcg(A, b, M=ΠA_induced_nn_local_mat)` on the FULL
+ * system (Example03:300-319), n = Σ n_i + n_gamma. With r indexed like the rows of A (`not_dirichlet_inds_g2l`):
+ *     y_Id = A_IId \ r_Id;  r_schur = r_Γ;  r_schur[gather_d] -= A_IΓdd' y_Id  (d ascending)     (EPDD.jl:2393-2400)
+ *     z_Γd = ΠS_d (r_schur[gather_d] / cnt[gather_d]);  z_Γ[gather_d] += z_Γd / cnt[gather_d]     (EPDD.jl:2403-2410)
+ *     z_Id = A_IId \ (r_Id - A_IΓdd v_d);  z[pos_I[d]] = z_Id;  z[pos_gamma] = z_Γ                (EPDD.jl:2411-2420)
+ * `coupling` chooses v_d:
+ *   MI_NNI_AS_WRITTEN  v_d = z_Γd, the local, unweighted, unassembled product — EPDD.jl:2411 as the reference has it. The
+ *                      operator is then neither symmetric nor positive definite (the reference's own notice: "this
+ *                      preconditioner only seems to work with deflation", EPDD.jl:2302).
+ *   MI_NNI_ASSEMBLED   v_d = z_Γ[gather_d]: the symmetric positive definite form
+ *                      [I -A_II⁻¹A_IΓ; 0 I] diag(A_II⁻¹, M_NN) [I 0; -A_ΓI A_II⁻¹ I].
+ * `interior` is a set-up plan with mi_schur_setup_keep_levels(plan, 1) and a run after it (all A_IId \ f at once, exact).
+ * The operator borrows it: while it is alive, mi_schur_setup_destroy(interior) and mi_schur_setup_keep_levels(interior, 0)
+ * return MI_ERR_BAD_ARG and change nothing. A later mi_schur_setup_run moves the plan, and with it this operator, to a new
+ * realization. The ΠS_d blocks are owned, in the layout and storage kinds of mi_nn_create_stored (MI_STORE_F64 /
+ * MI_STORE_F32); for the same r_schur the Γ part carries the bits of that operator's apply. The apply is plain launches
+ * (two level solves, the batched ΠS_d GEMV, five small kernels), no atomics, fixed summation orders: bitwise reproducible,
+ * captured into the solvers' graphs.
+ *   create: HOST arrays, `index_base`-based. n_gamma_d[d], n_i[d] as in the plan; pos_I[d][i] / pos_gamma[g]: the row of A
+ *           of interior node i of subdomain d / of Γ node g (together a permutation of the n rows); gather_idx[d][l]: the Γ
+ *           index of local interface node l (`ind_Γd_Γ2l`); cnt[g]: `node_Γ_cnt`; ig_*[d]: the CSC arrays of A_IΓdd,
+ *           n_i[d] x n_gamma_d[d] with LOCAL columns — what the plan itself was created from (EPDD.jl:2278); PiSd[d]:
+ *           n_gamma_d[d] x n_gamma_d[d], column-major fp64.
+ *   mi_nn_induced_set_values: the concatenated CSC nzval of all A_IΓdd for a new realization; mi_nn_induced_set_blocks: the
+ *           new ΠS_d, concatenated column-major fp64 (both: host or device pointer per the context's pointer mode);
+ *           mi_nn_induced_set_coupling: the other form of EPDD.jl:2411 on the same operator.
+ * MI_ERR_BAD_ARG with a message that names the offending numbers: maps that are no permutation, an index out of range,
+ * n != Σ n_i + n_gamma, an n_i or n_gamma_d that differs from the plan's, a plan of another context, a plan without kept
+ * levels or with no run since keeping them, a gather_idx outside [0, n_gamma), a cnt[g] that is not the number of
+ * subdomains whose gather_idx holds g, an unknown storage or coupling, a context that is one rank of several (the operator
+ * is replicated only). */
+#define MI_NNI_AS_WRITTEN 0
+#define MI_NNI_ASSEMBLED 1
+int mi_nn_induced_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma, const int64_t *n_gamma_d, const int64_t *n_i,
+                         const int64_t *const *pos_I, const int64_t *pos_gamma, const int64_t *const *gather_idx,
+                         const int64_t *cnt, const int64_t *const *ig_colptr, const int64_t *const *ig_rowval,
+                         const double *const *ig_nzval, const double *const *PiSd, int storage, mi_setup_t interior,
+                         int coupling, int index_base, mi_op_t *op);
+int mi_nn_induced_set_values(mi_op_t op, const double *ig_val);
+int mi_nn_induced_set_blocks(mi_op_t op, const double *PiSd);
+int mi_nn_induced_set_coupling(mi_op_t op, int coupling);
 int mi_nn_pinv(mi_ctx_t ctx, int64_t ndom, const int64_t *n_gamma_d, const double *Sd, double rtol, double *PiSd);
 int mi_dense_set_blocks(mi_op_t op, const double *blocks);
 

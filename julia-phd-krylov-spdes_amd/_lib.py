@@ -17,6 +17,7 @@ MI_OK = 0
 MI_ERR_BAD_ARG, MI_ERR_HIP, MI_ERR_SINGULAR, MI_ERR_RES_CAPACITY = -1, -2, -3, -4
 MI_ERR_COMM, MI_ERR_NO_DEVICE, MI_ERR_CALLBACK, MI_ERR_BOUNDS = -5, -6, -7, -8
 MI_PTR_HOST, MI_PTR_DEVICE = 0, 1
+MI_NNI_AS_WRITTEN, MI_NNI_ASSEMBLED = 0, 1
 MI_COMM_ID_BYTES = 128
 MI_PEER_HANDLE_BYTES = 64
 
@@ -99,6 +100,11 @@ SIGNATURES = {
                          C.POINTER(vp)],
     "mi_lorasc_set_values": [vp, vp],
     "mi_lorasc_set_correction": [vp, i64, vp, vp],
+    "mi_nn_induced_create": [vp, i64, i64, i64, i64p, i64p, i64pp, i64p, i64pp, i64p, i64pp, i64pp, f64pp, f64pp, C.c_int, vp,
+                             C.c_int, C.c_int, C.POINTER(vp)],
+    "mi_nn_induced_set_values": [vp, vp],
+    "mi_nn_induced_set_blocks": [vp, vp],
+    "mi_nn_induced_set_coupling": [vp, C.c_int],
     "mi_nn_pinv": [vp, i64, i64p, vp, C.c_double, vp],
     "mi_dense_set_blocks": [vp, vp],
     "mi_schur_matfree_rhs": [vp, vp, vp, vp],

@@ -592,6 +592,91 @@ class NeumannNeumannSchurPreconditioner(Operator):
         return "f32" if s.value == 1 else "f64"
 
 
+class NeumannNeumannInducedPreconditioner(Operator):
+    """The reference's `NeumannNeumannInducedPreconditioner` with `apply_neumann_neumann_induced` as its apply
+    (EPDD.jl:2274-2285, 2363-2423): `M` of `defpcg(A, b, ϕ, M=ΠA_induced_nn_local_mat)` and
+    `pcg(A, b, M=ΠA_induced_nn_local_mat)` on the full system (Example03:300-319), on the device (`mi_nn_induced_create`).
+
+    `A_IΓdd`: the local blocks (n_Id x n_Γd, local columns) the set-up plan was created from. `sub_or_maps`: where the
+    unknowns sit in the rows of `A` — `(pos_I, pos_Γ)`, or `(sub, dinds)`, or a `fem.SchurProblem`. `gather_idx`:
+    `ind_Γd_Γ2l` as index arrays; `node_Γ_cnt`; `ΠSd`: the blocks of `prepare_neumann_neumann_induced_precond`. `setup`: a
+    `SchurSetup` of the same subdomains with `keep_levels()` and a `run()` after it; it is kept alive by this object and
+    cannot be closed before it. `storage`: "f64" or "f32", as for `NeumannNeumannSchurPreconditioner`.
+
+    `coupling="reference"` is EPDD.jl:2411 as written: the interior is coupled to the local, unweighted, unassembled
+    `z_Γd`, and the operator is neither symmetric nor positive definite (the reference's "only seems to work with
+    deflation"). `coupling="assembled"` couples it to `z_Γ[gather_d]`: the symmetric positive definite block form."""
+
+    _COUPLING = {"reference": _lib.MI_NNI_AS_WRITTEN, "assembled": _lib.MI_NNI_ASSEMBLED}
+
+    def __init__(self, ctx: Context, A_IΓdd, sub_or_maps, gather_idx, node_Γ_cnt, ΠSd, setup: "SchurSetup", storage="f64",
+                 coupling="reference", index_base: int = 0):
+        if isinstance(storage, (type, np.dtype)):
+            storage = {np.dtype(np.float64): "f64", np.dtype(np.float32): "f32"}.get(np.dtype(storage), storage)
+        # (an unknown name goes to the library as it is, if it is a number: the library's message then names it)
+        sto = NeumannNeumannSchurPreconditioner._STORAGE.get(storage, storage)
+        cpl = self._COUPLING.get(coupling, coupling)
+        if not isinstance(sto, (int, np.integer)):
+            raise ValueError(f"storage must be 'f64', 'f32', numpy.float64 or numpy.float32, not {storage!r}")
+        if not isinstance(cpl, (int, np.integer)):
+            raise ValueError(f"coupling must be 'reference' or 'assembled', not {coupling!r}")
+        pos_I, pos_Γ = _lorasc_maps(sub_or_maps)
+        ndom = len(A_IΓdd)
+        if len(pos_I) != ndom or len(gather_idx) != ndom or len(ΠSd) != ndom:
+            raise ValueError("one interior map, one gather list and one ΠS_d block per subdomain expected")
+        n_i = _i64([len(p) for p in pos_I])
+        pI = [_i64(p) + index_base for p in pos_I]
+        pΓ = _i64(pos_Γ) + index_base
+        n_Γ = int(pΓ.size)
+        g = [_i64(a) + index_base for a in gather_idx]
+        nd = _i64([a.size for a in g])
+        cnt = _i64(node_Γ_cnt)
+        blocks = _blocks(ΠSd, 0, ndom)
+        for d in range(ndom):
+            if blocks[d].shape != (nd[d], nd[d]):
+                raise ValueError(f"ΠSd[{d}] has shape {blocks[d].shape}, expected {(nd[d], nd[d])}")
+        igp, igi, igv = _csc_parts(A_IΓdd, 0, ndom, index_base)
+        h = vp()
+        check(ctx._L.mi_nn_induced_create(
+            ctx._h, i64(ndom), i64(int(n_i.sum()) + n_Γ), i64(n_Γ), nd.ctypes.data_as(i64p), n_i.ctypes.data_as(i64p),
+            _ptrs(pI, i64p), pΓ.ctypes.data_as(i64p), _ptrs(g, i64p), cnt.ctypes.data_as(i64p), _ptrs(igp, i64p),
+            _ptrs(igi, i64p), _ptrs(igv, f64p), _ptrs(blocks, f64p), C.c_int(int(sto)), setup._h, C.c_int(int(cpl)),
+            C.c_int(index_base), C.byref(h)))
+        super().__init__(ctx, h, keep=(setup,))
+        self.setup = setup
+        self.n_Γ, self.nnz, self.n_blocks = n_Γ, int(sum(v.size for v in igv)), int((nd * nd).sum())
+        self.storage = "f32" if int(sto) == 1 else "f64"
+        self.coupling = "assembled" if int(cpl) == _lib.MI_NNI_ASSEMBLED else "reference"
+
+    def set_values(self, ig_val) -> None:
+        """The concatenated CSC `nzval` of all A_IΓdd of a new realization: numpy array or torch CUDA tensor
+        (`mi_nn_induced_set_values`). The interior factors move with `setup.run(...)`."""
+        self.ctx._mode_for(ig_val)
+        k, p = self.ctx._ptr(ig_val, self.nnz)
+        self.ctx._order((k,), after=False)
+        check(self.ctx._L.mi_nn_induced_set_values(self._h, p))
+
+    def set_blocks(self, ΠSd) -> None:
+        """New ΠS_d: one concatenated column-major buffer, numpy array or torch CUDA tensor (`mi_nn_induced_set_blocks`)."""
+        self.ctx._mode_for(ΠSd)
+        k, p = self.ctx._ptr(ΠSd, self.n_blocks)
+        self.ctx._order((k,), after=False)
+        check(self.ctx._L.mi_nn_induced_set_blocks(self._h, p))
+        self.ctx._record(ΠSd)
+
+    def set_coupling(self, coupling) -> None:
+        """"reference" (EPDD.jl:2411 as written) or "assembled" (`mi_nn_induced_set_coupling`)."""
+        cpl = self._COUPLING.get(coupling, coupling)
+        if not isinstance(cpl, (int, np.integer)):
+            raise ValueError(f"coupling must be 'reference' or 'assembled', not {coupling!r}")
+        check(self.ctx._L.mi_nn_induced_set_coupling(self._h, C.c_int(int(cpl))))
+        self.coupling = "assembled" if int(cpl) == _lib.MI_NNI_ASSEMBLED else "reference"
+
+    def close(self) -> None:
+        super().close()                 # before the plan it borrows
+        self._keep = ()
+
+
 def _wrap_interior(solvers: Sequence[Callable]):
     """`solvers[d](rhs) -> A_II[d]^{-1} rhs` on the host, as the C callback (EPDD.jl:648-650)."""
     def cb(_user, idom, n, rhs, sol):
@@ -989,6 +1074,10 @@ def apply_neumann_neumann_schur(Πnn: NeumannNeumannSchurPreconditioner, r):
 
 def apply_lorasc(Πlorasc: LorascPreconditioner, x):
     return Πlorasc.apply(x)
+
+
+def apply_neumann_neumann_induced(Πnn: NeumannNeumannInducedPreconditioner, r):
+    return Πnn.apply(r)
 
 
 # ------------------------------------------------------------------ solvers

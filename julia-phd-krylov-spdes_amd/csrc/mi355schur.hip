@@ -8,6 +8,7 @@
 #include "setup_gj.hpp"
 #include "spd_direct.hpp"
 #include "lorasc.hpp"
+#include "nn_induced.hpp"
 
 namespace mi {
 
@@ -584,6 +585,42 @@ int mi_lorasc_set_correction(mi_op_t op, int64_t nev, const double *E, const dou
   });
 }
 
+static NnInducedOp *as_nn_induced(mi_op_t op) { return op && op->impl ? dynamic_cast<NnInducedOp *>(op->impl.get()) : nullptr; }
+int mi_nn_induced_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma, const int64_t *n_gamma_d, const int64_t *n_i,
+                         const int64_t *const *pos_I, const int64_t *pos_gamma, const int64_t *const *gather_idx,
+                         const int64_t *cnt, const int64_t *const *ig_colptr, const int64_t *const *ig_rowval,
+                         const double *const *ig_nzval, const double *const *PiSd, int storage, mi_setup_t interior,
+                         int coupling, int index_base, mi_op_t *op) {
+  MI_NEW_OP(ctx, op, new NnInducedOp(ctx, ndom, n, n_gamma, n_gamma_d, n_i, pos_I, pos_gamma, gather_idx, cnt, ig_colptr, ig_rowval,
+                                     ig_nzval, PiSd, storage, interior, coupling, index_base));
+}
+int mi_nn_induced_set_values(mi_op_t op, const double *ig_val) {
+  NnInducedOp *m = as_nn_induced(op);
+  if (!m || !ig_val) return fail(MI_ERR_BAD_ARG, "mi_nn_induced_set_values: not a Neumann-Neumann induced preconditioner, or NULL ig_val");
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    DevBuf<double> st;
+    In vi(c, ig_val, (size_t)m->nnz, st);
+    m->set_values(vi.dev);
+    MI_HIP(hipStreamSynchronize(c->stream));   // the staging buffer goes out of scope
+    return MI_OK;
+  });
+}
+int mi_nn_induced_set_coupling(mi_op_t op, int coupling) {
+  NnInducedOp *m = as_nn_induced(op);
+  if (!m) return fail(MI_ERR_BAD_ARG, "mi_nn_induced_set_coupling: not a Neumann-Neumann induced preconditioner");
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    NnInducedOp::check_coupling(coupling, "mi_nn_induced_set_coupling");
+    MI_HIP(hipStreamSynchronize(c->stream));
+    for (auto &kv : c->workspaces) kv.second->drop_graphs_of(m);   // the index and operand arrays of launch 6 are arguments of captured applies
+    m->coupling = coupling;
+    return MI_OK;
+  });
+}
+
 int mi_schur_assembled_create(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d,
                               const int64_t *const *gather_idx, const double *const *Sd, int index_base,
                               int64_t dom_begin, int64_t dom_end, mi_op_t *op) {
@@ -1072,6 +1109,7 @@ int mi_schur_setup_run(mi_setup_t plan, const double *ii_val, const double *ig_v
 int mi_schur_setup_keep_levels(mi_setup_t plan, int on) {
   if (!plan) return fail(MI_ERR_BAD_ARG, "plan is NULL");
   if (!on && plan->bound > 0) return fail(MI_ERR_BAD_ARG, "mi_schur_setup_keep_levels: %d live LORASC operator(s) solve with the kept levels", plan->bound);
+  if (!on && plan->bound_nni > 0) return fail(MI_ERR_BAD_ARG, "mi_schur_setup_keep_levels: %d live Neumann-Neumann induced operator(s) solve with the kept levels", plan->bound_nni);
   return guarded([&]() -> int {
     plan->ctx->use();
 #ifdef MI355_EXPERIMENTAL
@@ -1117,6 +1155,7 @@ int mi_schur_matfree_interior_levels(mi_op_t op, mi_setup_t plan) {
 int mi_schur_setup_destroy(mi_setup_t plan) {
   if (!plan) return MI_OK;
   if (plan->bound > 0) return fail(MI_ERR_BAD_ARG, "mi_schur_setup_destroy: %d live LORASC operator(s) use this plan; destroy them first", plan->bound);
+  if (plan->bound_nni > 0) return fail(MI_ERR_BAD_ARG, "mi_schur_setup_destroy: %d live Neumann-Neumann induced operator(s) use this plan; destroy them first", plan->bound_nni);
   return guarded([&]() -> int {
     plan->ctx->use();
     (void)hipStreamSynchronize(plan->ctx->stream);
@@ -1142,9 +1181,7 @@ int mi_nn_pinv(mi_ctx_t ctx, int64_t ndom, const int64_t *n_gamma_d, const doubl
     return MI_OK;
   });
 }
-int mi_dense_set_blocks(mi_op_t op, const double *blocks) {
-  DenseBlockOp *dop = op && op->impl ? op->impl->as_dense() : nullptr;
-  if (!dop || !blocks) return fail(MI_ERR_BAD_ARG, "mi_dense_set_blocks: not an assembled-Schur / Neumann-Neumann operator, or NULL blocks");
+static int dense_set_blocks(DenseBlockOp *dop, const double *blocks) {
   mi_ctx_s *c = dop->ctx;
   return guarded([&]() -> int {
     c->use();
@@ -1165,6 +1202,16 @@ int mi_dense_set_blocks(mi_op_t op, const double *blocks) {
     if (c->ptr_mode != MI_PTR_DEVICE) MI_HIP(hipStreamSynchronize(c->stream));   // the staging buffer goes out of scope
     return MI_OK;
   });
+}
+int mi_dense_set_blocks(mi_op_t op, const double *blocks) {
+  DenseBlockOp *dop = op && op->impl ? op->impl->as_dense() : nullptr;
+  if (!dop || !blocks) return fail(MI_ERR_BAD_ARG, "mi_dense_set_blocks: not an assembled-Schur / Neumann-Neumann operator, or NULL blocks");
+  return dense_set_blocks(dop, blocks);
+}
+int mi_nn_induced_set_blocks(mi_op_t op, const double *PiSd) {
+  NnInducedOp *m = as_nn_induced(op);
+  if (!m || !PiSd) return fail(MI_ERR_BAD_ARG, "mi_nn_induced_set_blocks: not a Neumann-Neumann induced preconditioner, or NULL PiSd");
+  return dense_set_blocks(m->nn.get(), PiSd);
 }
 
 // ---------------------------------------------------------------- events

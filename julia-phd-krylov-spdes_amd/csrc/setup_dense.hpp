@@ -147,6 +147,7 @@ struct mi_setup_s {
   mi::DevBuf<int> c_ptr, c_row, c_src;
   std::unique_ptr<mi::GjState> gj;
   int bound = 0;                         // operators that borrow this plan (lorasc.hpp): mi_schur_setup_destroy is refused while > 0
+  int bound_nni = 0;                     // ... and the Neumann-Neumann induced operators that do (nn_induced.hpp)
   ~mi_setup_s();
   void release_lanes() {
     for (auto &l : lanes) {

@@ -840,6 +840,15 @@ def prepare_neumann_neumann_schur_precond(Sd: Sequence[np.ndarray]):
     return out
 
 
+def prepare_neumann_neumann_induced_precond(A_IIdd, A_IΓdd, A_ΓΓdd):
+    """The numeric half of `prepare_neumann_neumann_induced_precond` (EPDD.jl:2305-2353): per subdomain the dense
+    `Sd_mat = Array(Sd)` of `apply_local_schur` (:2322-2338) and ΠS_d = pinv(Sd_mat, rtol = sqrt(eps)) (:2339). The
+    blocks come from `assemble_local_schurs` (exact elimination in place of the reference's interior CG at reltol 1e-12)
+    and `prepare_neumann_neumann_schur_precond`; the Cholesky factors of :2340 are the kept levels of the device set-up
+    plan. Returns the list of ΠS_d, column-major."""
+    return prepare_neumann_neumann_schur_precond(assemble_local_schurs(A_IIdd, A_IΓdd, A_ΓΓdd))
+
+
 def prepare_lorasc_precond(S, A_ΓΓ, nvec: int = 25, ε: float = 0.01):
     """The low-rank correction of `prepare_lorasc_precond`, its `low_rank_correction = :exact` branch (EPDD.jl:1541-1617),
     on the host: the `nvec` least dominant generalized eigenpairs S e = σ A_ΓΓ e by a dense `scipy.linalg.eigh(S, A_ΓΓ)`

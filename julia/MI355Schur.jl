@@ -34,7 +34,7 @@ export MiContext, MiOperator, MiPrecond,
        LocalSchurs, LocalSchur, MatrixFreeLocalSchurs, GlobalSchur,
        AssemblyPlan, assemble!, set_values!, SchurSetup, set_blocks!, interior_precond!, interior_iterations,
        keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!,
-       SparseDirectPreconditioner, spd_direct_stats, MiLorasc, set_correction!
+       SparseDirectPreconditioner, spd_direct_stats, MiLorasc, set_correction!, MiNNInduced, set_coupling!
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -596,5 +596,93 @@ set_correction!(Π::MiLorasc, E::Matrix{Float64}, coef=nothing) =
 pcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiLorasc; maxit=0) = solve(:pcg, A, M.op, b, x, nothing, maxit)   # Example03:255
 defpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, W::Matrix{Float64}, M::MiLorasc; maxit=0) =
   solve(:defpcg, A, M.op, b, x, W, maxit)                                                                                        # Example03:262, 268
+
+
+# ---------------------------------------------------------------- Neumann-Neumann induced (Example03:300-319)
+# Fem exports `NeumannNeumannInducedPreconditioner`, `prepare_neumann_neumann_induced_precond` and
+# `apply_neumann_neumann_induced` (Fem.jl:84-86): the methods below are added to Fem's own functions by their qualified
+# names, so nothing of the reference is shadowed.
+const MI_NNI_AS_WRITTEN = Cint(0)
+const MI_NNI_ASSEMBLED = Cint(1)
+nni_coupling(c::Symbol) = c == :reference ? MI_NNI_AS_WRITTEN : c == :assembled ? MI_NNI_ASSEMBLED :
+  throw(ArgumentError("coupling must be :reference or :assembled, not $c"))
+
+"""`MiNNInduced`: the device form of Fem's `NeumannNeumannInducedPreconditioner` (EPDD.jl:2274-2285). `op` applies
+`apply_neumann_neumann_induced` (EPDD.jl:2363-2423) on the device; `plan` (the exact `A_IIdd \\ f` by level solves, in
+place of `chol_A_IId`) is borrowed by `op` and therefore kept in a field: the library refuses to destroy it while `op`
+lives."""
+mutable struct MiNNInduced
+  op::MiOperator
+  plan::SchurSetup
+  n_Γ::Int
+end
+
+"""`Fem.NeumannNeumannInducedPreconditioner(ctx, ΠSd, A_IΓdd, ind_Id_g2l, ind_Γ_g2l, ind_Γd_Γ2l, node_Γ_cnt,
+not_dirichlet_inds_g2l, plan; storage, coupling)`: a method added to the constructor of Fem's struct. `plan` is a
+`SchurSetup` of the same subdomains after `keep_levels!` and an `assemble_local_schurs(plan, …)`. `coupling = :reference`
+is EPDD.jl:2411 as written — the interior coupled to the local, unweighted, unassembled `z_Γd`: neither symmetric nor
+positive definite, the reference's "only seems to work with deflation" (EPDD.jl:2302); `:assembled` couples it to
+`z_Γ[gather_d]`, the symmetric positive definite form. `storage = Float32` holds the ΠS_d as fp32 on the device."""
+function Fem.NeumannNeumannInducedPreconditioner(ctx::MiContext, ΠSd::Vector{Matrix{Float64}}, A_IΓdd::Vector{SparseMatrixCSC{Float64,Int}},
+                                                 ind_Id_g2l::Vector{Dict{Int,Int}}, ind_Γ_g2l::Dict{Int,Int},
+                                                 ind_Γd_Γ2l::Vector{Dict{Int,Int}}, node_Γ_cnt::Vector{Int},
+                                                 not_dirichlet_inds_g2l::Dict{Int,Int}, plan::SchurSetup;
+                                                 storage::Type=Float64, coupling::Symbol=:reference)
+  ndom = length(A_IΓdd); n_Γ = length(ind_Γ_g2l)
+  pI, pΓ = lorasc_maps(ind_Id_g2l, ind_Γ_g2l, not_dirichlet_inds_g2l)                     # EPDD.jl:2383-2391
+  ni = Int64[length(p) for p in pI]
+  g = flatten_maps(ind_Γd_Γ2l); nd = Int64[length(x) for x in g]
+  cnt = Vector{Int64}(node_Γ_cnt)
+  igp, igi, igv = csc_parts(A_IΓdd)
+  storage === Float64 || storage === Float32 || error("storage must be Float64 or Float32")
+  sto = storage === Float32 ? Cint(1) : Cint(0)   # MI_STORE_F32 / MI_STORE_F64
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  GC.@preserve pI g igp igi igv ΠSd begin
+    check(ccall((:mi_nn_induced_create, lib), Cint,
+                (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Int64}}, Ptr{Int64}, Ptr{Ptr{Int64}}, Ptr{Int64},
+                 Ptr{Ptr{Int64}}, Ptr{Ptr{Int64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Cint, Ptr{Cvoid}, Cint, Cint, Ref{Ptr{Cvoid}}),
+                ctx.h, ndom, sum(ni) + n_Γ, n_Γ, nd, ni, ptrs(pI), pΓ, ptrs(g), cnt, ptrs(igp), ptrs(igi), ptrs(igv), Ptr{Float64}[pointer(B) for B in ΠSd],
+                sto, plan.h, nni_coupling(coupling), 1, r))
+  end
+  MiNNInduced(wrap(ctx, r), plan, n_Γ)
+end
+
+"""`Fem.prepare_neumann_neumann_induced_precond(ctx, A_IIdd, A_IΓdd, A_ΓΓdd, ind_Id_g2l, ind_Γ_g2l, ind_Γd_Γ2l, node_Γ_cnt,
+node_Γ, not_dirichlet_inds_g2l; storage, coupling)`: Example03:299-308 (EPDD.jl:2305-2353) on the device. The dense S_d come
+from the exact level elimination of a set-up plan (in place of `Array(Sd)` through the interior CG at reltol 1e-12,
+:2322-2338), ΠS_d = pinv(S_d, rtol = sqrt(eps)) from `mi_nn_pinv` (:2339), and the plan's kept levels stand in for
+`cholesky(A_IIdd[idom])` (:2340)."""
+function Fem.prepare_neumann_neumann_induced_precond(ctx::MiContext, A_IIdd::Vector{SparseMatrixCSC{Float64,Int}},
+                                                     A_IΓdd::Vector{SparseMatrixCSC{Float64,Int}}, A_ΓΓdd::Vector{SparseMatrixCSC{Float64,Int}},
+                                                     ind_Id_g2l, ind_Γ_g2l, ind_Γd_Γ2l, node_Γ_cnt, node_Γ, not_dirichlet_inds_g2l;
+                                                     storage::Type=Float64, coupling::Symbol=:reference)
+  plan = SchurSetup(ctx, A_IIdd, A_IΓdd, A_ΓΓdd)
+  keep_levels!(plan)
+  Sd = assemble_local_schurs(plan, A_IIdd, A_IΓdd, A_ΓΓdd)
+  nd = Int64[size(S, 1) for S in Sd]
+  cat = reduce(vcat, [vec(S) for S in Sd]); out = similar(cat)
+  check(ccall((:mi_nn_pinv, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Float64, Ptr{Float64}), ctx.h, length(Sd), nd, cat, 0.0, out))
+  ends = cumsum(nd .^ 2)
+  ΠSd = [reshape(out[(e - n * n + 1):e], n, n) for (e, n) in zip(ends, nd)]
+  Fem.NeumannNeumannInducedPreconditioner(ctx, ΠSd, A_IΓdd, ind_Id_g2l, ind_Γ_g2l, ind_Γd_Γ2l, Vector{Int}(node_Γ_cnt),
+                                          not_dirichlet_inds_g2l, plan; storage=storage, coupling=coupling)
+end
+
+Fem.apply_neumann_neumann_induced(Π::MiNNInduced, r::Vector{Float64}) = Π.op * r                    # EPDD.jl:2363-2423
+\(Π::MiNNInduced, x::Vector{Float64}) = Fem.apply_neumann_neumann_induced(Π, x)                    # EPDD.jl:2427-2429
+ldiv!(z::Vector{Float64}, Π::MiNNInduced, r::Vector{Float64}) = mul!(z, Π.op, r)                   # EPDD.jl:2431-2435
+ldiv!(Π::MiNNInduced, r::Vector{Float64}) = (r .= Fem.apply_neumann_neumann_induced(Π, copy(r)))   # EPDD.jl:2437-2440
+"""New values of all A_IΓdd (same patterns) for a new realization; the interior factors move with
+`assemble_local_schurs(Π.plan, …)`, the blocks with `set_blocks!(Π, ΠSd)`."""
+set_values!(Π::MiNNInduced, A_IΓdd::Vector{SparseMatrixCSC{Float64,Int}}) =
+  check(ccall((:mi_nn_induced_set_values, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), Π.op.h, reduce(vcat, [A.nzval for A in A_IΓdd])))
+set_blocks!(Π::MiNNInduced, ΠSd::Vector{Matrix{Float64}}) =
+  check(ccall((:mi_nn_induced_set_blocks, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), Π.op.h, reduce(vcat, [vec(B) for B in ΠSd])))
+"""`:reference` (EPDD.jl:2411 as written) or `:assembled`."""
+set_coupling!(Π::MiNNInduced, coupling::Symbol) =
+  check(ccall((:mi_nn_induced_set_coupling, lib), Cint, (Ptr{Cvoid}, Cint), Π.op.h, nni_coupling(coupling)))
+pcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiNNInduced; maxit=0) = solve(:pcg, A, M.op, b, x, nothing, maxit)   # Example03:317
+defpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, W::Matrix{Float64}, M::MiNNInduced; maxit=0) =
+  solve(:defpcg, A, M.op, b, x, W, maxit)                                                                                          # Example03:313
 
 end # module
