@@ -161,6 +161,35 @@ int mi_spd_direct_create(mi_ctx_t ctx, int64_t n, const int64_t *colptr, const i
 int mi_spd_direct_set_values(mi_op_t op, const double *nzval);
 int mi_spd_direct_stats(mi_op_t op, int64_t *pieces, int64_t *separator);
 
+/* mi_block_jacobi_create — the reference's `BJPreconditioner(nb, A)` (MyPreconditioners/BJPreconditioner.jl:1-32), the M of
+ * pcg / defpcg / eigpcg / eigdefpcg on the full matrix in Examples 06, 09 (`bj$(nbj)_0`), 15, 17 and 19: nb contiguous
+ * index slices of A, each factorised exactly,
+ *     bsize = floor(n / nb);  slice(i) = (i-1) bsize + 1 : i bsize  for i < nb,  (i-1) bsize + 1 : n  for i = nb
+ *     y[slice(i)] = cholesky(A[slice(i), slice(i)]) \ x[slice(i)]
+ * on the device by the breadth-first level elimination of mi_schur_setup_* used as a complete block LDL' (block_jacobi.hpp):
+ * per block a seed set G, levels grown from the nodes next to it, the level inverses kept, S_G^-1 dense. One apply is ONE
+ * forward and one backward sweep over the kept inverses (3 steps + 2 plain launches, steps = the deepest block's levels),
+ * captured into the solvers' graphs; no atomics, fixed summation orders: bitwise reproducible. nb = 1 is `A \ b`.
+ *   create    : colptr (n + 1), rowval, nzval (nnz) of the CSC matrix, HOST arrays, `index_base`-based indices.
+ *               seed_ptr (nb + 1, starting at index_base) / seed_idx (block-local, `index_base`-based): explicit seeds per block;
+ *               seed_ptr == NULL selects the default rule, per connected component of a block's graph (components in ascending
+ *               order of their lowest node): the nodes with a stored entry of A in a column before the slice; else those with
+ *               one in a column after it; else the component's lowest node.
+ *               MI_ERR_BAD_ARG, the message naming the numbers: nb < 1 or nb > n (the reference's bsize = 0 is not
+ *               reproduced); a pattern that is not structurally symmetric; a component of a block without a seed (block
+ *               and node); a level or a seed set of more than 2048 nodes; a context that is one rank of several (the
+ *               operator is replicated only).
+ *   set_values: new nzval on the same pattern (a new realization, Example06:600), host or device pointer per the context's
+ *               pointer mode: one gather and the numeric phase. Synchronous.
+ *   Both return MI_ERR_SINGULAR when a block is singular or not positive definite as far as the factor shows it (a value
+ *   that is not finite, a diagonal entry of a kept inverse or of S_G^-1 that is not positive, or a failed certificate of
+ *   S_G^-1: mi_nn_pinv's probe, the plain inverse only); set_values then keeps the previous factor.
+ * mi_block_jacobi_stats — per block (arrays of nb, any may be NULL): seeds, levels, widest level; kept_bytes = 8 Σ n_level². */
+int mi_block_jacobi_create(mi_ctx_t ctx, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval, int64_t nb,
+                           const int64_t *seed_ptr, const int64_t *seed_idx, int index_base, mi_op_t *op);
+int mi_block_jacobi_set_values(mi_op_t op, const double *nzval);
+int mi_block_jacobi_stats(mi_op_t op, int64_t *n_g, int64_t *n_levels, int64_t *max_level, int64_t *kept_bytes);
+
 /* mi_schur_assembled_create — `apply_local_schurs(Sd, ind_Γd_Γ2l, node_Γ_cnt, x)`, EPDD.jl:761-785:
  * Sx = Σ_d R_d' S_d R_d x with dense local Schur complements.
  *   Sd[d]          n_gamma_d[d]^2 doubles, column-major (Julia `Array(Sd[d])`)

@@ -431,6 +431,66 @@ class SparseDirectPreconditioner(Operator):
         return int(a.value), int(b.value)
 
 
+class BlockJacobiPreconditioner(Operator):
+    """The reference's `BJPreconditioner(nb, A)` (MyPreconditioners/BJPreconditioner.jl:1-32) on the device
+    (`mi_block_jacobi_create`): `M \\ r` solves the nb contiguous slices of `A` exactly, `bsize = n ÷ nb`, the last slice to
+    the end. `A` is a scipy sparse matrix or a (colptr, rowval, nzval, n) tuple of CSC arrays with a structurally symmetric
+    pattern. `seeds`: None for the default rule, or one array of block-local node indices per block (every connected
+    component of a block needs one). `nb = 1` is `A \\ b`."""
+
+    def __init__(self, ctx: Context, nb: int, A, seeds=None, index_base: int = 0):
+        if isinstance(A, tuple):
+            ptr, idx, val, n = A
+            ptr, idx, val = _i64(ptr), _i64(idx), _f64(val)
+        else:
+            A = sp.csc_matrix(A)
+            A.sum_duplicates()
+            A.sort_indices()
+            n = A.shape[0]
+            if A.shape[0] != A.shape[1]:
+                raise ValueError("square matrix expected")
+            ptr, idx, val = _i64(A.indptr), _i64(A.indices), _f64(A.data)
+        sq = sx = None
+        if seeds is not None:
+            if len(seeds) != nb:
+                raise ValueError(f"{len(seeds)} seed lists for nb = {nb} blocks")
+            sq = _i64(np.concatenate(([0], np.cumsum([len(s) for s in seeds]))) + index_base)
+            sx = _i64(np.concatenate([np.asarray(s, dtype=np.int64).ravel() for s in seeds] + [np.zeros(0, dtype=np.int64)]))
+            sx = _i64(np.concatenate((sx, [0])))          # never a NULL pointer for an empty list
+        h = vp()
+        check(ctx._L.mi_block_jacobi_create(ctx._h, i64(n), ptr.ctypes.data_as(i64p), idx.ctypes.data_as(i64p),
+                                            val.ctypes.data_as(f64p), i64(nb), None if sq is None else sq.ctypes.data_as(i64p),
+                                            None if sx is None else sx.ctypes.data_as(i64p), C.c_int(index_base), C.byref(h)))
+        super().__init__(ctx, h)
+        self.nb, self.nnz = int(nb), int(val.size)
+
+    def set_values(self, A_or_nzval) -> None:
+        """A new realization on the pattern of construction: a scipy sparse matrix, or its CSC values as a numpy array or a
+        torch CUDA tensor (`mi_block_jacobi_set_values`). MiError(MI_ERR_SINGULAR) leaves the previous factor in place.
+        The test behind it is necessary, not sufficient: the elimination does not pivot and reports no pivots, so what is
+        checked is that every value is finite, that every diagonal entry of every kept level inverse and of S_G^-1 is
+        positive, and the probe certificate of S_G^-1. An indefinite matrix whose inverses all have positive diagonals is
+        accepted (the same holds at construction)."""
+        v = A_or_nzval
+        if sp.issparse(v):
+            v = sp.csc_matrix(v)
+            v.sum_duplicates()
+            v.sort_indices()
+            v = _f64(v.data)
+        self.ctx._mode_for(v)
+        k, p = self.ctx._ptr(v, self.nnz)
+        self.ctx._order((k,), after=False)
+        check(self.ctx._L.mi_block_jacobi_set_values(self._h, p))   # synchronous
+
+    def stats(self):
+        """dict(n_g, n_levels, max_level: arrays of nb; kept_bytes = 8 Σ n_level²)"""
+        a, b, c = (np.zeros(self.nb, dtype=np.int64) for _ in range(3))
+        kb = i64()
+        check(self.ctx._L.mi_block_jacobi_stats(self._h, a.ctypes.data_as(i64p), b.ctypes.data_as(i64p), c.ctypes.data_as(i64p),
+                                                C.byref(kb)))
+        return dict(n_g=a, n_levels=b, max_level=c, kept_bytes=int(kb.value))
+
+
 class LorascPreconditioner(Operator):
     """The reference's `LorascPreconditioner` with `apply_lorasc` as its apply (EPDD.jl:1406-1428, 1908-1976): `M` of
     `pcg(A, b, zeros, ΠA_lorasc)` and `defpcg(A, b, zeros, ϕ, ΠA_lorasc)` on the full system (Example03:245-268), on the

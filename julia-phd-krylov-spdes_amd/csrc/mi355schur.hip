@@ -9,6 +9,7 @@
 #include "spd_direct.hpp"
 #include "lorasc.hpp"
 #include "nn_induced.hpp"
+#include "block_jacobi.hpp"
 
 namespace mi {
 
@@ -548,6 +549,35 @@ int mi_spd_direct_stats(mi_op_t op, int64_t *pieces, int64_t *separator) {
   return MI_OK;
 }
 
+
+static BlockJacobiOp *as_block_jacobi(mi_op_t op) { return op && op->impl ? dynamic_cast<BlockJacobiOp *>(op->impl.get()) : nullptr; }
+int mi_block_jacobi_create(mi_ctx_t ctx, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval, int64_t nb,
+                           const int64_t *seed_ptr, const int64_t *seed_idx, int index_base, mi_op_t *op) {
+  if (!nzval) return fail(MI_ERR_BAD_ARG, "mi_block_jacobi_create: nzval is NULL");
+  MI_NEW_OP(ctx, op, new BlockJacobiOp(ctx, n, colptr, rowval, nzval, nb, seed_ptr, seed_idx, index_base));
+}
+int mi_block_jacobi_set_values(mi_op_t op, const double *nzval) {
+  BlockJacobiOp *m = as_block_jacobi(op);
+  if (!m || !nzval) return fail(MI_ERR_BAD_ARG, "mi_block_jacobi_set_values: not a block-Jacobi preconditioner, or NULL nzval");
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    In vi(c, nzval, (size_t)m->nnz, m->stage);
+    m->factor(vi.dev);   // synchronous: a singular or indefinite block is reported here
+    return MI_OK;
+  });
+}
+int mi_block_jacobi_stats(mi_op_t op, int64_t *n_g, int64_t *n_levels, int64_t *max_level, int64_t *kept_bytes) {
+  BlockJacobiOp *m = as_block_jacobi(op);
+  if (!m) return fail(MI_ERR_BAD_ARG, "mi_block_jacobi_stats: not a block-Jacobi preconditioner");
+  for (int d = 0; d < m->nb; ++d) {
+    if (n_g) n_g[d] = m->plan->dom[d].n_g;
+    if (n_levels) n_levels[d] = m->plan->dom[d].nlev;
+    if (max_level) max_level[d] = m->plan->dom[d].max_lev;
+  }
+  if (kept_bytes) *kept_bytes = m->kept;
+  return MI_OK;
+}
 
 static LorascOp *as_lorasc(mi_op_t op) { return op && op->impl ? dynamic_cast<LorascOp *>(op->impl.get()) : nullptr; }
 int mi_lorasc_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma, const int64_t *n_i, const int64_t *const *pos_I,

@@ -31,6 +31,7 @@ constexpr int GJ_B = MI355_GJ_B;   // pivot block: 64 (one full-matrix pass per 
                                    // register inversions and 32 x 32 matrix-core products) or 32 (round 2's form)
 constexpr int GJ_H = 32;    // rows one wave inverts in registers
 constexpr int GJ_T = 64;    // tile of the update launch (256 threads, 4 x 4 outputs each)
+constexpr int GJ_MAX_DOM = 65535;   // subdomains of one plan / blocks of one batch: they are the launches' grid.z
 static_assert(GJ_B == 32 || GJ_B == 64, "pivot block");
 
 struct GjStep {             // one per (step, subdomain); n0 == 0: the subdomain is not active in this step
@@ -464,7 +465,8 @@ __global__ __launch_bounds__(256) void k_gj_pivot(int step, int kb, int ndom, co
 // column-major matrix are 128-byte segments. Wave v owns rows 16 v .. 16 v + 15 of the tile.
 __device__ __forceinline__ unsigned *gj_ready_flag(const GjDom &dm) { return reinterpret_cast<unsigned *>(dm.P + 2 * GJ_B * GJ_B); }
 __global__ void k_gj_reset(int ndom, const GjDom *__restrict__ doms) {
-  if ((int)threadIdx.x < ndom) *gj_ready_flag(doms[threadIdx.x]) = 0u;
+  const int d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d < ndom) *gj_ready_flag(doms[d]) = 0u;
 }
 template <bool HEAD_T>
 __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom, const GjStep *__restrict__ steps,
@@ -790,7 +792,8 @@ __global__ __launch_bounds__(256) void k_gj_keep(int step, int ndom, const GjSte
 }
 // y = Z_{k+1} g_{k+1} (the deeper level, handled one step earlier)
 __global__ __launch_bounds__(256) void k_lv_zg(int step, int ndom, const GjStep *__restrict__ steps, const GjDom *__restrict__ doms,
-                                               const double *__restrict__ zstore, const double *__restrict__ gstore) {
+                                               const double *__restrict__ zstore, const double *__restrict__ gstore, const int *done) {
+  if (done && *done) return;
   const GjStep st = steps[(size_t)step * ndom + blockIdx.z];
   if (st.n0 == 0 || st.n1 == 0 || (int)blockIdx.x * 64 >= st.n1) return;
   const GjStep sp = steps[(size_t)(step - 1) * ndom + blockIdx.z];
@@ -800,7 +803,8 @@ __global__ __launch_bounds__(256) void k_lv_zg(int step, int ndom, const GjStep 
 __global__ __launch_bounds__(256) void k_lv_g(int step, int ndom, const GjStep *__restrict__ steps, const GjDom *__restrict__ doms,
                                               const int *__restrict__ c_ptr, const int *__restrict__ c_row, const int *__restrict__ c_src,
                                               const double *__restrict__ ii_val, const int *__restrict__ perm, const double *__restrict__ f,
-                                              double *__restrict__ gstore) {
+                                              double *__restrict__ gstore, const int *done) {
+  if (done && *done) return;
   const GjStep st = steps[(size_t)step * ndom + blockIdx.z];
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= st.n0) return;
@@ -817,10 +821,29 @@ __global__ __launch_bounds__(256) void k_lv_g(int step, int ndom, const GjStep *
 // u = Z (g - C u_shallower) for the level of `step` (64 rows per workgroup; the operand is formed in LDS first: every
 // workgroup needs all of it). last == 1: the shallowest level, u_0 = Z_0 g_0.
 constexpr int LV_MAX = 2048;
+// 64 rows per workgroup of out = Z t (Z n x n column-major, t in LDS): the columns dealt to the four waves, sixteen in flight
+// per thread, the partial sums combined as (p0 + p1) + (p2 + p3). The one place that fixes the summation order of the
+// back-substitution (k_lv_back) and of block_jacobi.hpp's Γ step and level 0.
+__device__ __forceinline__ void lv_gemv64_lds(const double *__restrict__ Z, int n, const double *t, double (*part)[64], double *__restrict__ out) {
+  const int r = blockIdx.x * 64 + (threadIdx.x & 63), wv = threadIdx.x >> 6;
+  double s2 = 0.0;
+  if (r < n)
+    for (int b0 = wv; b0 < n; b0 += 64) {
+      double z[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) { const int b = b0 + 4 * k; z[k] = b < n ? Z[r + (size_t)b * n] : 0.0; }
+#pragma unroll
+      for (int k = 0; k < 16; ++k) { const int b = b0 + 4 * k; if (b < n) s2 += z[k] * t[b]; }
+    }
+  part[wv][threadIdx.x & 63] = s2;
+  __syncthreads();
+  if (threadIdx.x < 64 && r < n) out[r] = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+}
 __global__ __launch_bounds__(256) void k_lv_back(int step, int last, int ndom, const GjStep *__restrict__ steps,
                                                  const double *__restrict__ zstore, const double *__restrict__ gstore,
                                                  const int *__restrict__ r_ptr, const int *__restrict__ r_col, const int *__restrict__ r_src,
-                                                 const double *__restrict__ ii_val, double *__restrict__ ustore) {
+                                                 const double *__restrict__ ii_val, double *__restrict__ ustore, const int *done) {
+  if (done && *done) return;
   const GjStep st = steps[(size_t)step * ndom + blockIdx.z];
   const int n = st.n0;
   if (n == 0 || (int)blockIdx.x * 64 >= n) return;
@@ -840,20 +863,7 @@ __global__ __launch_bounds__(256) void k_lv_back(int step, int last, int ndom, c
     }
   }
   __syncthreads();
-  const double *Z = zstore + st.zoff;
-  const int r = blockIdx.x * 64 + (threadIdx.x & 63), wv = threadIdx.x >> 6;
-  double s2 = 0.0;
-  if (r < n)
-    for (int b0 = wv; b0 < n; b0 += 64) {
-      double z[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) { const int b = b0 + 4 * k; z[k] = b < n ? Z[r + (size_t)b * n] : 0.0; }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) { const int b = b0 + 4 * k; if (b < n) s2 += z[k] * t[b]; }
-    }
-  part[wv][threadIdx.x & 63] = s2;
-  __syncthreads();
-  if (threadIdx.x < 64 && r < n) ustore[st.b_off + r] = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+  lv_gemv64_lds(zstore + st.zoff, n, t, part, ustore + st.b_off);
 }
 __global__ __launch_bounds__(256) void k_lv_scatter(long long n, const int *__restrict__ perm, const double *__restrict__ ustore, double *__restrict__ u) {
   for (long long q = blockIdx.x * 256ll + threadIdx.x; q < n; q += (long long)gridDim.x * 256) u[perm[q]] = ustore[q];
@@ -927,8 +937,8 @@ inline void gj_enqueue(mi_setup_s &P, hipStream_t s, const double *ii, const dou
   // levels of at most `head_maxn` nodes invert the step's pivot block at the head of the launch, larger ones look ahead
   static const int head_maxn = GJ_B == GJ_T ? env_int("MI355_GJ_HEAD_MAXN", MI355_GJ_HEAD ? (1 << 30) : 0) : 0;
   unsigned seq = 0;
-  if (nd > 1024) raise(MI_ERR_BAD_ARG, "device set-up: more than 1024 subdomains in one plan");
-  hipLaunchKernelGGL(k_gj_reset, dim3(1), dim3(1024), 0, s, nd, dm);
+  if (nd > GJ_MAX_DOM) raise(MI_ERR_BAD_ARG, "device set-up: more than %d subdomains in one plan", GJ_MAX_DOM);
+  hipLaunchKernelGGL(k_gj_reset, dim3(cdiv(nd, 1024)), dim3(1024), 0, s, nd, dm);
   for (int step = 0; step < G.nsteps; ++step) {
     nm = G.n_step[step];   // grids cover the largest level of this step only
     if (bI && step > 0) hipLaunchKernelGGL(k_gj_zg, dim3(cdiv(nm, 64), 1, nd), dim3(256), 0, s, step, nd, st, dm);
@@ -1006,7 +1016,11 @@ inline void gj_set_keep(mi_setup_s &P, bool on) {
   G.gstore.alloc((size_t)P.n_bi + 1); G.ustore.alloc((size_t)P.n_bi + 1);
   G.sv_in.alloc((size_t)P.n_bi + 1); G.sv_out.alloc((size_t)P.n_bi + 1);
 }
-inline void gj_level_enqueue(mi_setup_s &P, hipStream_t s, const double *f, double *u) {
+// The two sweeps of a level solve as plain launches on `s`. Forward: g (level order, gstore) from f, read through `perm`
+// (position in level order -> index into f). Backward: u (ustore, level order) for the levels of steps `from` .. 0; from ==
+// nsteps - 1 starts with u_0 = Z_0 g_0, a smaller `from` expects the u of step from + 1 in ustore (block_jacobi.hpp forms
+// its own level 0). `done` (device flag, may be NULL): set = every launch returns at once.
+inline void gj_level_forward(mi_setup_s &P, hipStream_t s, const int *perm, const double *f, const int *done) {
   GjState &G = *P.gj;
   const int nd = P.ndom;
   const GjStep *st = G.steps.p;
@@ -1015,14 +1029,24 @@ inline void gj_level_enqueue(mi_setup_s &P, hipStream_t s, const double *f, doub
   const double *ii = G.in_ii.p;   // the values of the last run
   for (int step = 0; step < G.nsteps; ++step) {
     const int nm = G.n_step[step];
-    if (step > 0) hipLaunchKernelGGL(k_lv_zg, dim3(cdiv(nm, 64), 1, nd), dim3(256), 0, s, step, nd, st, dm, G.zstore.p, G.gstore.p);
-    hipLaunchKernelGGL(k_lv_g, dim3(cdiv(nm, 256), 1, nd), dim3(256), 0, s, step, nd, st, dm, P.c_ptr.p, P.c_row.p, P.c_src.p, ii, P.perm.p, f, G.gstore.p);
+    if (step > 0) hipLaunchKernelGGL(k_lv_zg, dim3(cdiv(nm, 64), 1, nd), dim3(256), 0, s, step, nd, st, dm, G.zstore.p, G.gstore.p, done);
+    hipLaunchKernelGGL(k_lv_g, dim3(cdiv(nm, 256), 1, nd), dim3(256), 0, s, step, nd, st, dm, P.c_ptr.p, P.c_row.p, P.c_src.p, ii, perm, f, G.gstore.p, done);
   }
-  for (int step = G.nsteps - 1; step >= 0; --step) {
+}
+inline void gj_level_backward(mi_setup_s &P, hipStream_t s, int from, const int *done) {
+  GjState &G = *P.gj;
+  const int nd = P.ndom;
+  auto cdiv = [](int a, int b) { return (a + b - 1) / b; };
+  for (int step = from; step >= 0; --step) {
     const int nm = G.n_step[step];
-    hipLaunchKernelGGL(k_lv_back, dim3(cdiv(nm, 64), 1, nd), dim3(256), 0, s, step, step == G.nsteps - 1 ? 1 : 0, nd, st, G.zstore.p, G.gstore.p,
-                       G.r_ptr.p, G.r_col.p, G.r_src.p, ii, G.ustore.p);
+    hipLaunchKernelGGL(k_lv_back, dim3(cdiv(nm, 64), 1, nd), dim3(256), 0, s, step, step == G.nsteps - 1 ? 1 : 0, nd, G.steps.p, G.zstore.p, G.gstore.p,
+                       G.r_ptr.p, G.r_col.p, G.r_src.p, G.in_ii.p, G.ustore.p, done);
   }
+}
+inline void gj_level_enqueue(mi_setup_s &P, hipStream_t s, const double *f, double *u) {
+  GjState &G = *P.gj;
+  gj_level_forward(P, s, P.perm.p, f, nullptr);
+  gj_level_backward(P, s, G.nsteps - 1, nullptr);
   hipLaunchKernelGGL(k_lv_scatter, dim3(std::min<long long>(4096, std::max<long long>(1, (P.n_bi + 255) / 256))), dim3(256), 0, s, (long long)P.n_bi,
                      P.perm.p, G.ustore.p, u);
   MI_HIP(hipGetLastError());
@@ -1168,9 +1192,11 @@ __global__ __launch_bounds__(256) void k_copy_add_const(long long n, const doubl
 }
 inline std::atomic<long long> &spectral_pinv_calls() { static std::atomic<long long> n{0}; return n; }   // blocks sent to the eigen-decomposition (mi_ctx_query)
 
-inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, const double *Sd, double rtol, double *Pi) {
+// `spd_only` (block_jacobi.hpp: the Schur complements of an SPD matrix are SPD): the plain inverse with its certificate or
+// MI_ERR_SINGULAR; the floating and the spectral route are never taken.
+inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, const double *Sd, double rtol, double *Pi, bool spd_only = false) {
   hipStream_t s = c->stream;
-  if (env_int("MI355_PINV_EIG", 0)) { spectral_pinv_calls() += ndom; pinv_blocks(c, ndom, n_gamma_d, Sd, rtol, Pi); return; }
+  if (!spd_only && env_int("MI355_PINV_EIG", 0)) { spectral_pinv_calls() += ndom; pinv_blocks(c, ndom, n_gamma_d, Sd, rtol, Pi); return; }
   std::vector<GjStep> st(ndom);
   std::vector<GjDom> dm(ndom);
   size_t tot = 0;
@@ -1206,8 +1232,8 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
     std_.upload(sb, s); dmd.upload(db, s);
     const int nb_ = (int)ds.size();
     constexpr bool gj_head = false;   // (pinv batches: look-ahead form)
-    if (nb_ > 1024) raise(MI_ERR_BAD_ARG, "pinv: more than 1024 blocks in one batch");
-    hipLaunchKernelGGL(k_gj_reset, dim3(1), dim3(1024), 0, s, nb_, dmd.p);
+    if (nb_ > GJ_MAX_DOM) raise(MI_ERR_BAD_ARG, "pinv: more than %d blocks in one batch", GJ_MAX_DOM);
+    hipLaunchKernelGGL(k_gj_reset, dim3(cdiv(nb_, 1024)), dim3(1024), 0, s, nb_, dmd.p);
     for (int kb = 0; kb < nbmax; ++kb) {
       if (kb == 0 && !gj_head) hipLaunchKernelGGL(k_gj_pivot, dim3(1, 1, nb_), dim3(256), 0, s, 0, kb, nb_, std_.p, dmd.p);   // later pivots: look-ahead in the update
       const int tx = cdiv(nmax, GJ_T);
@@ -1258,6 +1284,11 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
     const bool inv_ok = std::isfinite(nS[d]) && std::isfinite(nZ[d]) && nZ[d] > 0.0 && 1.0 / nZ[d] > rtol * nS[d] &&
                         probe_ok(n, nS[d], nZ[d], nR[d]);
     if (inv_ok) MI_HIP(hipMemcpyAsync(Pi + off[d], dm[d].Z[st[d].nb & 1], sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, s));
+    else if (spd_only) {
+      MI_HIP(hipStreamSynchronize(s));             // the copies out of Z above
+      raise(MI_ERR_SINGULAR, "block %d (%d x %d) is singular or its inverse fails the certificate (probe residual %.3e, bar %.3e)", d, n, n, nR[d],
+            PROBE_C * n * eps * nS[d] * nZ[d]);
+    }
     // (max |S_ii| and ||S||_inf / sqrt(n) are both <= σ_max: an S 1 this small means pinv drops at least one eigenvalue)
     else if (std::isfinite(nS[d]) && nS[d] > 0.0 && nS1[d] <= rtol * std::max(nD[d], nS[d] / std::sqrt((double)n)) &&
              !env_int("MI355_PINV_NO_SHIFT", 0)) {

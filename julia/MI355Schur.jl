@@ -23,6 +23,7 @@ import Base: *, \, size
 import LinearAlgebra: mul!, ldiv!
 import RecyclingKrylovSolvers
 import RecyclingKrylovSolvers: cg, pcg, defcg, defpcg, eigcg, eigpcg, eigdefcg, eigdefpcg, initcg, initpcg
+import MyPreconditioners
 import Fem
 import Fem: apply_local_schur, apply_local_schurs, apply_global_schur, apply_neumann_neumann_schur,
             get_schur_rhs, get_subdomain_solutions, NeumannNeumannSchurPreconditioner,
@@ -34,7 +35,7 @@ export MiContext, MiOperator, MiPrecond,
        LocalSchurs, LocalSchur, MatrixFreeLocalSchurs, GlobalSchur,
        AssemblyPlan, assemble!, set_values!, SchurSetup, set_blocks!, interior_precond!, interior_iterations,
        keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!,
-       SparseDirectPreconditioner, spd_direct_stats, MiLorasc, set_correction!, MiNNInduced, set_coupling!
+       SparseDirectPreconditioner, spd_direct_stats, bj_set_values!, MiLorasc, set_correction!, MiNNInduced, set_coupling!
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -501,6 +502,24 @@ function spd_direct_stats(M::MiOperator)
   check(ccall((:mi_spd_direct_stats, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), M.h, p, s))
   (p[], s[])
 end
+
+# ---------------------------------------------------------------- block-Jacobi on the full matrix (Example09 `bj$(nbj)_0`)
+"""`MyPreconditioners.BJPreconditioner(ctx, nb, A)`: a device method ADDED to the reference's constructor
+(MyPreconditioners/BJPreconditioner.jl:16-21; `mi_block_jacobi_create`): `nb` contiguous slices of `A`, `bsize = n ÷ nb`, the
+last one to the end, each solved exactly. A script that writes `using MyPreconditioners: BJPreconditioner` calls
+`BJPreconditioner(ctx, nbj, A)` where it called `BJPreconditioner(nbj, A)`; the two-argument method keeps resolving, and the
+shim exports no name of its own for it. `M \\ r` and `ldiv!` work as for every operator; `bj_set_values!(M, A)` takes a new
+realization on the same pattern (Example06:600)."""
+function MyPreconditioners.BJPreconditioner(ctx::MiContext, nb::Int, A::SparseMatrixCSC{Float64,Int})
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  cp, rv = Vector{Int64}(A.colptr), Vector{Int64}(A.rowval)
+  check(ccall((:mi_block_jacobi_create, lib), Cint,
+              (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Cint, Ref{Ptr{Cvoid}}),
+              ctx.h, A.n, cp, rv, A.nzval, nb, C_NULL, C_NULL, 1, r))
+  wrap(ctx, r)
+end
+bj_set_values!(M::MiOperator, A::SparseMatrixCSC{Float64,Int}) =
+  check(ccall((:mi_block_jacobi_set_values, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), M.h, A.nzval))
 
 # `pcg(S, b_schur, zeros(S.N), A_ΓΓ)` as Example07:412/416 write it: the device factor is cached per matrix object, refilled
 # (set_values!) when its values changed since the last call and rebuilt when its pattern or the context did.
