@@ -142,6 +142,10 @@ struct EigKrylov {
     // VtAV[1:nvec,1:nvec] = WtAW; V[:,1:nvec] = W; ivec = nvec + 1; V[:, ivec] = z / sqrt(rTz)  (defcg.jl:158-163 / 391-396)
     const int ivec0 = deflated ? nvec : 0;
     std::vector<double> T((size_t)spdim * spdim, 0.0);
+    // A stop before the window holds nvec columns returns the columns behind the newest Lanczos vector as they are. The
+    // reference leaves them undefined (V = Array(undef, n, spdim), eigcg.jl:41 / 159); the oracle defines them as zeros, and
+    // so does the device: without this they were the columns of the previous solve on the workspace.
+    if (!deflated) MI_HIP(hipMemsetAsync(ws.eV.p, 0, sizeof(double) * (size_t)n * nvec, s));
     if (deflated) {
       for (int j = 0; j < nvec; ++j)
         for (int i = 0; i < nvec; ++i) T[i + (size_t)j * spdim] = k.gram_host[i + (size_t)j * nvec];

@@ -349,8 +349,12 @@ def _ritz_restart(VtAV, m, nvec, sym_H):
     return vals, Q @ Z, nev
 
 
-def _eig_solver(A, b, x, M, W, nvec, spdim, maxit, eps, kind):
-    """Shared body of eigcg (eigcg.jl:27-123), eigpcg (:143-267), eigdefcg (defcg.jl:111-223), eigdefpcg (:337-473)."""
+def _eig_solver(A, b, x, M, W, nvec, spdim, maxit, eps, kind, state=None):
+    """Shared body of eigcg (eigcg.jl:27-123), eigpcg (:143-267), eigdefcg (defcg.jl:111-223), eigdefpcg (:337-473).
+    `state`: a dict that receives the window's state when the loop ends, before the final extraction (also when that
+    raises): ivec (1-based), just_restarted, first_restart, restarts, VtAV (copy), kept (Ritz values of the last restart),
+    restart_T (the projected matrix that restart worked on); and, if the final extraction runs, extract_m.
+    Tests only (tests/eig_synth.py); the results do not depend on it."""
     pre = M is not None
     deflated = W is not None
     n = A.n
@@ -368,6 +372,7 @@ def _eig_solver(A, b, x, M, W, nvec, spdim, maxit, eps, kind):
     just_restarted = False
     first_restart = True
     hlpr = 0.0
+    restarts, kept, restart_T = 0, None, None
     if maxit == 0:
         maxit = n
     if deflated:
@@ -442,8 +447,11 @@ def _eig_solver(A, b, x, M, W, nvec, spdim, maxit, eps, kind):
                 for j in range(spdim):
                     AV[:, j] = A(V[:, j])                            # eigcg.jl:233-240
                 VtAV[:, :] = V.T @ AV
+            if state is not None:
+                restart_T = VtAV.copy()
             vals, QZ, nev = _ritz_restart(VtAV, spdim, nvec, sym_H=pre)
             V[:, :nev] = V @ QZ
+            restarts, kept = restarts + 1, vals[:nev].copy()
             ivec = nev + 1
             V[:, ivec - 1] = vnew()
             VtAV[:, :] = 0.0
@@ -459,6 +467,9 @@ def _eig_solver(A, b, x, M, W, nvec, spdim, maxit, eps, kind):
             V[:, ivec - 1] = vnew()
             VtAV[ivec - 2, ivec - 1] = -np.sqrt(beta) / alpha
             VtAV[ivec - 1, ivec - 1] = beta / alpha
+    if state is not None:
+        state.update(ivec=ivec, just_restarted=just_restarted, first_restart=first_restart, restarts=restarts,
+                     VtAV=VtAV.copy(), kept=kept, restart_T=restart_T)
     if pre and not just_restarted:                                   # eigcg.jl:269-287 / defcg.jl:451-470 (pcg variants only)
         if ivec > nvec:
             ivec -= 1
@@ -467,25 +478,27 @@ def _eig_solver(A, b, x, M, W, nvec, spdim, maxit, eps, kind):
             if ivec - 1 < nvec:
                 # eigvecs(Tm[1:ivec-1, 1:ivec-1])[:, 1:nvec] (eigcg.jl:275 / defcg.jl:461) is out of range
                 raise BoundsError(f"attempt to access {ivec - 1} x {ivec - 1} eigenvector matrix at columns 1:{nvec}")
+            if state is not None:
+                state.update(extract_m=ivec, VtAV=VtAV.copy())
             vals, QZ, nev = _ritz_restart(VtAV, ivec, nvec, sym_H=True)
             V[:, :nev] = V[:, :ivec] @ QZ
     return x, it, res_norm[:it].copy(), V[:, :nvec].copy()
 
 
-def eigcg(A, b, x, nvec, spdim, maxit=0, eps=1e-7):
-    return _eig_solver(A, b, x, None, None, nvec, spdim, maxit, eps, "eigcg")
+def eigcg(A, b, x, nvec, spdim, maxit=0, eps=1e-7, state=None):
+    return _eig_solver(A, b, x, None, None, nvec, spdim, maxit, eps, "eigcg", state)
 
 
-def eigpcg(A, b, x, M, nvec, spdim, maxit=0, eps=1e-7):
-    return _eig_solver(A, b, x, M, None, nvec, spdim, maxit, eps, "eigpcg")
+def eigpcg(A, b, x, M, nvec, spdim, maxit=0, eps=1e-7, state=None):
+    return _eig_solver(A, b, x, M, None, nvec, spdim, maxit, eps, "eigpcg", state)
 
 
-def eigdefcg(A, b, x, W, spdim, maxit=0, eps=1e-7):
-    return _eig_solver(A, b, x, None, W, 0, spdim, maxit, eps, "eigdefcg")
+def eigdefcg(A, b, x, W, spdim, maxit=0, eps=1e-7, state=None):
+    return _eig_solver(A, b, x, None, W, 0, spdim, maxit, eps, "eigdefcg", state)
 
 
-def eigdefpcg(A, b, x, M, W, spdim, maxit=0, eps=1e-7):
-    return _eig_solver(A, b, x, M, W, 0, spdim, maxit, eps, "eigdefpcg")
+def eigdefpcg(A, b, x, M, W, spdim, maxit=0, eps=1e-7, state=None):
+    return _eig_solver(A, b, x, M, W, 0, spdim, maxit, eps, "eigdefpcg", state)
 
 
 def _init_guess(A, b, x, W):
