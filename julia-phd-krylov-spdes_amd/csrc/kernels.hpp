@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "exchange_dev.hpp"
+#include "dense_tiles.hpp"
 #include "spmv_blocks.hpp"
 
 namespace mi {
@@ -841,15 +842,6 @@ __global__ __launch_bounds__(NT) void k_csr_inv_diag(int n, const int *__restric
 // g (slots in ascending subdomain order, W = max multiplicity; unused slots stay 0). The
 // scatter-add over subdomains `Sx[lΓ] += Sdxd[lΓd]` (EPDD.jl:779-781 / 1379-1381) is then a
 // contiguous W-term sum per Γ node, taken by the consumer kernel in the reference's idom order.
-struct GemvTile {
-  long long mat_off;  // element offset of the subdomain block
-  int n, ld;          // n_Γd and padded leading dimension
-  int loc_off, row0;  // offset of the block in the local index space, first row of this tile
-  int active, nrows;  // active 0: the block of this subdomain lives on another rank (multi-GPU): nothing to stream here;
-                      // otherwise 1 + the slot of this tile's partial dot products in the folded launches.
-                      // nrows: rows [row0, row0 + nrows) whose owner duties this tile performs in the folded launches
-                      // (active: the WAVES*RPW streamed rows; inactive: up to one row per thread)
-};
 struct DenseMeta {
   const void *M;          // all blocks of this rank, row-major, padded: doubles, or floats for fp32-stored blocks (GemvRows<RPW, MT>)
   const GemvTile *tiles;  // [ntiles]
@@ -857,7 +849,6 @@ struct DenseMeta {
   const double *cnt;      // [nloc] node_Γ_cnt as double (NN only)
   const int *out_pos;     // [nloc] slot g*W + j of every local row
 };
-constexpr int GEMV_PANEL = 2048;  // doubles of x_d staged per pass (16 KiB LDS)
 #ifndef MI355_OPERAND_FIRST
 #define MI355_OPERAND_FIRST 1   // 0: matrix stream first (measured 7 % slower in the folded PCG launches)
 #endif
@@ -1202,7 +1193,11 @@ struct PcgFold {
   PinnedFlags *exit_flags;
   long long *dbg;           // MI355_FOLD_DEBUG: wall-clock stamps of workgroup dbg_wg, 8 per launch (tools/fold_stamps.py)
   int dbg_wg;
+  // launch of an operator that is sharded over ranks (XCHG kernels only): the partials are summed by PART_LANES threads,
+  // so that ranks that chose different tilings for their slices associate the sum alike
+  int canon;
 };
+constexpr int PART_LANES = 256;   // the smallest workgroup of the folded launches (4 waves)
 #define MI_FSTAMP(i) \
   do { if (f.dbg && (int)blockIdx.x == f.dbg_wg && threadIdx.x == 0) f.dbg[dbg_row * 8 + (i)] = wall_clock64(); } while (0)
 __device__ __forceinline__ double slot_sum(const double *slots, int g, int W) {
@@ -1269,11 +1264,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
   const int dbg_row = (int)((PHASE == 1 ? 2 * it_nxt0 : 2 * it0 + 1) & 63);
   MI_FSTAMP(0);
   double pa = 0.0, pb = 0.0;
-  for (int i0 = threadIdx.x; i0 < f.n_in; i0 += 8 * NTH) {  // up to eight partials in flight per thread, added in order
+  // Threads that sum the partials. A launch whose tiling is this rank's own (sharded operator) must not let its thread count
+  // decide how the sum is associated — alpha, beta and the stop rule would then differ between the ranks in the last bits:
+  // its first PART_LANES threads sum, whatever WAVES is (the other waves add zeros to the tree below: exact).
+  const int SL = XCHG && f.canon ? PART_LANES : NTH;
+  for (int i0 = XCHG && f.canon && threadIdx.x >= PART_LANES ? f.n_in : (int)threadIdx.x; i0 < f.n_in; i0 += 8 * SL) {  // up to eight partials in flight per thread, added in order
     double ta[8], tb[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const int i = i0 + k * NTH;
+      const int i = i0 + k * SL;
       ta[k] = i < f.n_in ? part_in0[i] : 0.0;
       tb[k] = PHASE == 0 && i < f.n_in ? part_in1[i] : 0.0;
     }

@@ -30,7 +30,6 @@ inline int to_i32(int64_t v, int64_t lo, int64_t hi, const char *what) {
 }
 
 // ------------------------------------------------------------------ base class
-constexpr int PART_ROWS = 4;   // fewest rows a streamed tile can have (4 waves x 1 row)
 inline std::atomic<long long> &folded_pcg_launches() { static std::atomic<long long> n{0}; return n; }   // k_gemv_pcg launches issued (mi_ctx_query)
 struct DenseBlockOp;
 struct Operator {
@@ -212,6 +211,7 @@ struct LocalMaps {
   DevBuf<int> jrank, peer, tgt;  // local-order bookkeeping of the folded PCG launches (kernels.hpp PcgFold)
   std::vector<int> tgt_h;        // host copy of tgt (the peer exchange lists a rank's own table entries from it)
   int slot_width = 1;  // W: contribution slots per Γ node (max multiplicity over this rank's subdomains)
+  bool local_slots = false;  // a slice built without the other ranks' gather lists: W and the slot ranks are this rank's alone
   void build(mi_ctx_s *c, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d, const int64_t *const *gather_idx,
              int base, int64_t d0, int64_t d1) {
     if (ndom <= 0 || n_gamma < 0 || n_gamma >= INT32_MAX || !n_gamma_d || !gather_idx || d0 < 0 || d1 > ndom || d0 > d1)
@@ -257,9 +257,12 @@ struct LocalMaps {
     // of g, on every rank alike — then the ranks' slot tables are disjoint (their sum is a union, x + 0) and have one
     // width. The gather lists of the other ranks' subdomains are index arrays every rank has (set_subdomains is global);
     // if a caller leaves them NULL the local ranks are used: still a correct sum, but colliding slots are added by the
-    // all-reduce (no longer the single-GPU order) and all ranks must then happen to agree on the width.
+    // all-reduce (no longer the single-GPU order). The width is then this rank's own (`local_slots`): nothing that is
+    // exchanged over the ranks may depend on it — the dense operators all-reduce the assembled Γ vector instead of the
+    // slot table, and the staging reserved below holds n_Γ entries.
     bool global_slots = ndl < ndom;
     for (int64_t d = 0; d < ndom && global_slots; ++d) global_slots = !(n_gamma_d[d] > 0 && !gather_idx[d]);
+    local_slots = ndl < ndom && !global_slots;
     if (global_slots) {
       std::vector<int> seen_cnt((size_t)n_gamma, 0);
       for (int64_t d = 0; d < ndom; ++d)
@@ -297,7 +300,8 @@ struct LocalMaps {
     jrank.upload(jr, c->stream); peer.upload(pe, c->stream); tgt.upload(tg, c->stream);
     tgt_h = tg;
     // sums over ranks that this operator will issue inside captured graphs need their staging before the capture
-    if (sharded && c->use_peer()) c->peer->reserve_stage((size_t)n_gamma * (size_t)std::max(slot_width, 1) + 4);
+    // (collective bump allocation: the size must be the same on every rank, so a rank-local width stays out of it)
+    if (sharded && c->use_peer()) c->peer->reserve_stage((size_t)n_gamma * (size_t)(local_slots ? 1 : std::max(slot_width, 1)) + 4);
   }
   void assemble(mi_ctx_s *c, int64_t n_gamma, const double *yloc, double *y, const int *done) const {
     hipLaunchKernelGGL(k_assemble, dim3(vec_grid(n_gamma)), dim3(NT), 0, c->stream, (int)n_gamma, aptr.p, apos.p, yloc,
@@ -394,58 +398,29 @@ struct DenseBlockOp : Operator {
     waves = env_int("MI355_GEMV_WAVES", 16);
     if (waves != 4 && waves != 8 && waves != 16) waves = 16;
     if (reduce_over_ranks && full_maps && !env_int("MI355_GEMV_WAVES", 0) && !env_int("MI355_GEMV_RPW", 0)) {
-      // A rank that owns 1/N of the blocks would keep 1/N of the CUs busy with 32-row tiles (a launch lasts as long as
-      // one tile): cut the owned rows into about one tile per CU instead.
+      // the sharded rule of dense_tiles.hpp: about one tile of the owned rows per CU
       int64_t owned_rows = 0;
       for (int64_t d = d0; d < d1; ++d) owned_rows += n_gamma_d[d];
       hipDeviceProp_t prop;
       MI_HIP(hipGetDeviceProperties(&prop, c->device));
-      const int64_t per_tile = std::max<int64_t>(1, owned_rows / std::max(1, prop.multiProcessorCount));
-      if (per_tile >= 24) { waves = 16; rpw = 2; }
-      else if (per_tile >= 12) { waves = 16; rpw = 1; }
-      else if (per_tile >= 6) { waves = 8; rpw = 1; }
-      else { waves = 4; rpw = 1; }
+      const DenseTiling tl = dense_sharded_tiling(owned_rows, prop.multiProcessorCount);
+      waves = tl.waves; rpw = tl.rpw;
     }
-    std::vector<long long> moff;
-    std::vector<int> ldv;
-    std::vector<GemvTile> tv;
     const bool sharded_parts = reduce_over_ranks && full_maps;
-    part_total = 0;
-    long long tot = 0;
     auto owned = [&](int dl) { return m0 + dl >= d0 && m0 + dl < d1; };
-    for (int dl = 0; dl < maps.ndl; ++dl) {
-      const int n_d = maps.nd[dl];
-      // rows padded to whole 128-byte lines: 16 doubles / 32 floats
-      const int line = f32() ? 32 : 16;
-      int l = (n_d + line - 1) / line * line;
-      // A row stride that is a multiple of 2 KiB puts every row of a tile on the same HBM channels: measured 27 % slower
-      // at n_Γd = 1024 (profiles/r01_gemv_variant_sweep.txt). One extra 128-byte line per row breaks the pattern. The
-      // pattern is one of bytes: 256 doubles, 512 floats. (l == GEMV_PANEL keeps its stride in both formats: the operand
-      // panel of the folded launches holds no more columns.)
-      if (l % (16 * line) == 0 && l != GEMV_PANEL) l += line;
-      const bool own = owned(dl);
-      if (own && n_d && !blocks[m0 + dl]) raise(MI_ERR_BAD_ARG, "dense block %d is NULL", dl);
-      moff.push_back(own ? tot : 0); ldv.push_back(l);
-      max_nd = std::max(max_nd, n_d);
-      max_ld = std::max(max_ld, l);
-      // tiles of another rank's block only do owner duties in the folded launches: as few workgroups as possible
-      const int step = own ? waves * rpw : 64 * waves;
-      // `active` of a streamed tile = 1 + the slot of its partial dot products. One GPU: the tile number. Sharded over ranks:
-      // a layout every rank derives from the maps alone, whatever tiling each rank chose for its own blocks — subdomain
-      // after subdomain, one slot per PART_ROWS rows (no tiling has fewer rows per tile), so the ranks' arrays are a
-      // disjoint union of one array and the exchange adds nothing.
-      for (int r = 0; r < n_d; r += step) {
-        const int slot = sharded_parts ? part_total + r / PART_ROWS : (int)tv.size();
-        tv.push_back(GemvTile{own ? tot : 0, n_d, l, maps.loc_off[dl], r, own ? slot + 1 : 0, std::min(step, n_d - r)});
-      }
-      if (sharded_parts) part_total += (n_d + PART_ROWS - 1) / PART_ROWS;
-      if (own) {
-        tot += (long long)n_d * l;
-        alg_bytes += (f32() ? 4ll : 8ll) * n_d * n_d + 16ll * n_d + 4ll * n_d;
-      }
-    }
+    for (int dl = 0; dl < maps.ndl; ++dl)
+      if (owned(dl) && maps.nd[dl] && !blocks[m0 + dl]) raise(MI_ERR_BAD_ARG, "dense block %d is NULL", dl);
+    // tile list, block offsets and padded strides (dense_tiles.hpp)
+    const DenseTilePlan plan = dense_tile_plan(maps.nd, maps.loc_off, (int)(d0 - m0), (int)(d1 - m0), DenseTiling{waves, rpw},
+                                               sharded_parts, f32() ? 32 : 16);
+    const std::vector<long long> &moff = plan.moff;
+    const std::vector<int> &ldv = plan.ld;
+    const std::vector<GemvTile> &tv = plan.tiles;
+    const long long tot = plan.elems;
+    part_total = plan.part_total; max_nd = plan.max_nd; max_ld = plan.max_ld;
     ntiles = (int)tv.size();
-    if (!sharded_parts) part_total = ntiles;
+    for (int dl = 0; dl < maps.ndl; ++dl)
+      if (owned(dl)) alg_bytes += (f32() ? 4ll : 8ll) * maps.nd[dl] * maps.nd[dl] + 16ll * maps.nd[dl] + 4ll * maps.nd[dl];
     moff_h = moff; ld_h = ldv;
     for (int dl = 0; dl < maps.ndl; ++dl) owned_h.push_back(owned(dl) ? 1 : 0);
     // (+ one zeroed panel behind the last block: the persistent kernel reads whole 128-double groups of a row without
@@ -505,7 +480,7 @@ struct DenseBlockOp : Operator {
     fold_part1.alloc((size_t)ntiles + 1); fold_part1.zero(c->stream);
     if (reduce_over_ranks && c->use_peer()) {
       // staging of the generic sums this operator issues (plain applies: the slot table), reserved outside any capture
-      c->peer->reserve_stage(std::max<size_t>(fold_pack_n, (size_t)n_gamma * maps.slot_width + 4));
+      c->peer->reserve_stage(full_maps ? std::max<size_t>(fold_pack_n, (size_t)n_gamma * maps.slot_width + 4) : (size_t)n_gamma + 4);
       if (full_maps) {
         // the folded launches' table: entries this rank produces = the contribution slots its rows write (tgt) and the
         // per-row partials of its rows
@@ -558,10 +533,14 @@ struct DenseBlockOp : Operator {
     gemv(x, done);
     // Multi-GPU: the slot tables of the ranks are disjoint, so their sum is the full table and the Γ-sum below runs in
     // the single-GPU order (reducing y instead would add per-rank partial sums: same value, different rounding).
-    if (reduce_over_ranks) ctx->allreduce(yslots.p, yslots_all.p, (size_t)n * maps.slot_width);
+    // Local-only maps (the other ranks' gather lists were not given): slot width and slot ranks are this rank's own, so
+    // the ranks' tables are neither disjoint nor of one size. Each rank takes its own Γ-sum and the n_Γ-vectors are added.
+    const bool slots_over_ranks = reduce_over_ranks && full_maps;
+    if (slots_over_ranks) ctx->allreduce(yslots.p, yslots_all.p, (size_t)n * maps.slot_width);
     hipLaunchKernelGGL(k_assemble_slots, dim3(vec_grid(n)), dim3(NT), 0, ctx->stream, (int)n, maps.slot_width,
-                       reduce_over_ranks ? yslots_all.p : yslots.p, y, done);
+                       slots_over_ranks ? yslots_all.p : yslots.p, y, done);
     MI_HIP(hipGetLastError());
+    if (reduce_over_ranks && !full_maps) ctx->allreduce(y, (size_t)n);
   }
   DenseBlockOp *as_dense() override { return this; }
   // New blocks on the same maps: `src` holds the owned blocks back to back, column-major (device pointer).
@@ -588,7 +567,8 @@ struct DenseBlockOp : Operator {
   void gemv_pcg(int phase, const PcgFold &f) {
     if (!ntiles) return;
     ++folded_pcg_launches();
-    const bool xchg = f.xp != nullptr || f.x_inwait != 0;   // this launch stores into the peers' arenas and / or waits for them
+    // this launch stores into the peers' arenas and / or waits for them, or sums its partials in the rank-independent order
+    const bool xchg = f.xp != nullptr || f.x_inwait != 0 || f.canon != 0;
     // fp32-stored blocks have the ΠS launch without peer exchange only (Krylov's fold decision keeps everything else away)
     if (f32() && (phase != 1 || xchg)) raise(MI_ERR_BAD_ARG, "folded PCG launch: no fp32 kernel for phase %d%s", phase, xchg ? " with peer exchange" : "");
 #define MI_PCG4(R, P, C, V) do { if (xchg) hipLaunchKernelGGL((k_gemv_pcg<R, P, C, V, true>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, f); \
@@ -612,11 +592,19 @@ struct DenseBlockOp : Operator {
     return n == o.n && maps.slot_width == o.maps.slot_width && maps.nd == o.maps.nd && maps.gidx_h == o.maps.gidx_h;
   }
   AsmView view_of(double *) override {
+    if (reduce_over_ranks && !full_maps) return AsmView{yslots_all.p, 0};   // local-only maps: the summed Γ vector (apply_view)
     return reduce_over_ranks ? AsmView{yslots_all.p, maps.slot_width} : AsmView{yslots.p, maps.slot_width};
   }
   AsmView apply_view(const double *x, double *y, const int *done) override {
     gemv(x, done);
     if (!reduce_over_ranks) return AsmView{yslots.p, maps.slot_width};
+    if (!full_maps) {   // local-only maps: own Γ-sum, then the sum of the ranks' vectors (see apply)
+      hipLaunchKernelGGL(k_assemble_slots, dim3(vec_grid(n)), dim3(NT), 0, ctx->stream, (int)n, maps.slot_width, yslots.p,
+                         yslots_all.p, done);
+      MI_HIP(hipGetLastError());
+      ctx->allreduce(yslots_all.p, (size_t)n);
+      return AsmView{yslots_all.p, 0};
+    }
     // Multi-GPU: every rank wrote only its own subdomains' slots (the rest are zero), so the out-of-place sum
     // over ranks IS the full slot table (x + 0 is exact): the consumer then takes the Γ-sum in the same
     // ascending-subdomain order as on one GPU, and no separate assemble launch is needed.

@@ -364,6 +364,9 @@ struct Krylov {
       if (redM && Md->xt_on()) { f.in_epoch = &ctx->peer->st->epoch; f.in_stride = (long long)Md->xt_copy; }
     }
     if (inwait()) { f.x_inwait = 1; f.xst = ctx->peer->st; f.xpw = ctx->peer->peers_dev; }
+    // A sharded operator's tiling is its rank's own (operators.hpp): its launch sums the partials it reads in an order
+    // that does not depend on it. (A replicated operator has one tiling on all ranks.)
+    f.canon = (phase ? Md : Ad)->reduce_over_ranks ? 1 : 0;
     return f;
   }
 
