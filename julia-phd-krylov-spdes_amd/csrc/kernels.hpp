@@ -273,11 +273,11 @@ __device__ __forceinline__ int spmv_block_of(int nblocks) {
   const int per = (nblocks + 7) >> 3;
   return (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
 }
-__global__ __launch_bounds__(NT, 8) void k_spmv_pcg(int nblocks, const SpmvBlock *__restrict__ blk, const int *__restrict__ rowptr,
-                                                 const int *__restrict__ col, const double *__restrict__ val, SolverState *st,
-                                                 const double *part_rr, const double *part_rz, int g_vec, double *pz0, double *pz1,
-                                                 double *__restrict__ Ap, double *__restrict__ part_pAp, double *res_norm,
-                                                 int precond) {
+__global__ __launch_bounds__(NT, 8) void k_spmv_pcg(int nblocks, int precond, const SpmvBlock *__restrict__ blk, SolverState *st,
+                                                 const double *part_rr, const double *part_rz, int g_vec,
+                                                 const int *__restrict__ rowptr,   // (up to here: preloaded into SGPRs at wave start)
+                                                 const int *__restrict__ col, const double *__restrict__ val, double *pz0, double *pz1,
+                                                 double *__restrict__ Ap, double *__restrict__ part_pAp, double *res_norm) {
   __shared__ __attribute__((aligned(16))) double prod[SPMV_TILE];
   __shared__ double sm[NT / 64 + 1];
   const int b = spmv_block_of(nblocks);
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(NT) void k_update_xr_blk(const int *__restrict__ xc
   const int done0 = st->done;
   const long long it_n = st->it_nxt;
   const double rTr0 = st->rTr, rTz0 = st->rTz;
-  asm volatile("" ::"s"(R0), "s"(R1), "s"(done0), "s"(it_n), "s"(rTr0), "s"(rTz0));   // one round trip, then the exit test
+  asm volatile("" ::"s"(R0), "s"(R1), "s"(done0), "s"(it_n), "s"(rTr0), "s"(rTz0), "s"(nj));   // one round trip (the grid size, an implicit kernel argument, included), then the exit test
   if (done0) return;
   const int lo = (int)(R0 + (R1 - R0) * j / nj), hi = (int)(R0 + (R1 - R0) * (j + 1) / nj);
   const double num = precond ? rTz0 : rTr0;
@@ -934,11 +934,12 @@ struct GemvRows {
   double acc[RPW];
   Vec buf[RPW][GemvElem<MT>::G];
   int lane, ld;
-  __device__ __forceinline__ void begin(const DenseMeta &m, const GemvTile &t) {
+  __device__ __forceinline__ void begin(const DenseMeta &m, const GemvTile &t) { begin(m.M, t); }
+  __device__ __forceinline__ void begin(const void *M, const GemvTile &t) {   // M = DenseMeta::M
     lane = threadIdx.x & 63;
     ld = t.ld;
     const int row_base = t.row0 + (threadIdx.x >> 6) * RPW;
-    const MT *Md = static_cast<const MT *>(m.M) + t.mat_off;   // (mat_off and ld count elements of the storage type)
+    const MT *Md = static_cast<const MT *>(M) + t.mat_off;   // (mat_off and ld count elements of the storage type)
 #pragma unroll
     for (int k = 0; k < RPW; ++k) {
       const int r = min(row_base + k, t.n - 1);  // clamp: tail rows re-read a valid row, result dropped
@@ -961,15 +962,19 @@ struct GemvRows {
   }
 };
 
+// Arguments: the fields of DenseMeta as plain pointers, the seven the head of the launch dereferences first (14 dwords:
+// what kernel-argument preload delivers in SGPRs at wave start; a struct passed by value is never preloaded).
 template <int RPW, bool SCALE, int WAVES, typename MT = double>
-__global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(DenseMeta m, const double *__restrict__ x,
-                                                             double *__restrict__ yslots, const int *done,
-                                                             const int *zero_x) {
+__global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(const GemvTile *tiles, const int *done, const int *zero_x,
+                                                             const int *__restrict__ gidx, const double *__restrict__ x,
+                                                             const double *__restrict__ cnt, const void *M,
+                                                             double *__restrict__ yslots, const int *__restrict__ out_pos) {
   constexpr int NTH = 64 * WAVES;
   // tile record and both flags in ONE memory round trip (tested one after the other they cost three, 1.2-2 us each)
-  const GemvTile t = m.tiles[blockIdx.x];
+  const GemvTile t = tiles[blockIdx.x];
   const int done0 = done ? *done : 0, zero0 = zero_x ? *zero_x : 0;
-  asm volatile("" ::"s"(t.mat_off), "s"(t.n), "s"(t.ld), "s"(t.loc_off), "s"(t.row0), "s"(t.active), "s"(done0), "s"(zero0));
+  asm volatile("" ::"s"(t.mat_off), "s"(t.n), "s"(t.ld), "s"(t.loc_off), "s"(t.row0), "s"(t.active), "s"(done0), "s"(zero0),
+               "s"(yslots), "s"(out_pos));   // (the two arguments behind the preloaded ones: requested in the same batch)
   if (done0) return;
   __shared__ __attribute__((aligned(16))) double xs[GEMV_PANEL];
   if (!t.active) return;
@@ -978,12 +983,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(DenseMeta m, const 
     const int row_base = t.row0 + (threadIdx.x >> 6) * RPW;
     if ((threadIdx.x & 63) == 0)
       for (int k = 0; k < RPW; ++k)
-        if (row_base + k < n) yslots[m.out_pos[off + row_base + k]] = 0.0;
+        if (row_base + k < n) yslots[out_pos[off + row_base + k]] = 0.0;
     return;
   }
   GemvRows<RPW, MT> rows;
 #if !MI355_OPERAND_FIRST
-  rows.begin(m, t);
+  rows.begin(M, t);
 #endif
   for (int c0 = 0; c0 < t.ld; c0 += GEMV_PANEL) {
     const int pw = min(GEMV_PANEL, t.ld - c0);  // multiple of 16
@@ -996,7 +1001,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(DenseMeta m, const 
 #pragma unroll
     for (int q = 0; q < XPT; ++q) {
       const int j = c0 + q * NTH + (int)threadIdx.x;
-      gi[q] = (q * NTH + (int)threadIdx.x < pw && j < n) ? m.gidx[off + j] : -1;
+      gi[q] = (q * NTH + (int)threadIdx.x < pw && j < n) ? gidx[off + j] : -1;
     }
     double xv[XPT];
 #pragma unroll
@@ -1005,10 +1010,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(DenseMeta m, const 
       xv[q] = 0.0;
       if (gi[q] >= 0) {
         xv[q] = x[gi[q]];
-        if (SCALE) xv[q] = xv[q] / m.cnt[off + j];
+        if (SCALE) xv[q] = xv[q] / cnt[off + j];
       }
     }
-    if (c0 == 0) rows.begin(m, t);
+    if (c0 == 0) rows.begin(M, t);
 #pragma unroll
     for (int q = 0; q < XPT; ++q) {
       const int l = q * NTH + (int)threadIdx.x;
@@ -1019,8 +1024,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(DenseMeta m, const 
       const int j = c0 + l;
       double v = 0.0;
       if (j < n) {
-        v = x[m.gidx[off + j]];
-        if (SCALE) v = v / m.cnt[off + j];
+        v = x[gidx[off + j]];
+        if (SCALE) v = v / cnt[off + j];
       }
       xs[l] = v;
     }
@@ -1034,7 +1039,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(DenseMeta m, const 
 #pragma unroll
   for (int k = 0; k < RPW; ++k) {
     const int r = row_base + k;
-    if (rows.lane == 0 && r < n) yslots[m.out_pos[off + r]] = SCALE ? sum[k] / m.cnt[off + r] : sum[k];
+    if (rows.lane == 0 && r < n) yslots[out_pos[off + r]] = SCALE ? sum[k] / cnt[off + r] : sum[k];
   }
 }
 
@@ -1043,11 +1048,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_batched(DenseMeta m, const 
 // per column. Per (row, vector) the products are accumulated in the order of k_gemv_batched: results are bit-identical
 // to KV single applies. X is column-major with leading dimension ldx; vector v writes its slot table at v*slot_stride.
 template <int RPW, int KV, bool SCALE, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_gemv_multi(DenseMeta m, const double *__restrict__ X, long long ldx, int kv,
-                                                           double *__restrict__ yslots, long long slot_stride) {
+__global__ __launch_bounds__(64 * WAVES) void k_gemv_multi(const GemvTile *tiles, const int *__restrict__ gidx,
+                                                           const double *__restrict__ X, const double *__restrict__ cnt,
+                                                           const double *__restrict__ M, long long ldx, int kv,
+                                                           double *__restrict__ yslots, long long slot_stride,
+                                                           const int *__restrict__ out_pos) {   // (DenseMeta's fields; 13 dwords preloaded)
   constexpr int NTH = 64 * WAVES;
   __shared__ __attribute__((aligned(16))) double xs[KV][GEMV_PANEL];
-  const GemvTile t = m.tiles[blockIdx.x];
+  const GemvTile t = tiles[blockIdx.x];
   if (!t.active) return;
   const int off = t.loc_off, n = t.n, lane = threadIdx.x & 63;
   const int row_base = t.row0 + (threadIdx.x >> 6) * RPW;
@@ -1055,7 +1063,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_multi(DenseMeta m, const do
   double acc[RPW][KV];
 #pragma unroll
   for (int k = 0; k < RPW; ++k) {
-    rowp[k] = static_cast<const double *>(m.M) + t.mat_off + (long long)min(row_base + k, n - 1) * t.ld;   // (fp64 storage only)
+    rowp[k] = M + t.mat_off + (long long)min(row_base + k, n - 1) * t.ld;   // (fp64 storage only)
 #pragma unroll
     for (int v = 0; v < KV; ++v) acc[k][v] = 0.0;
   }
@@ -1064,8 +1072,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_multi(DenseMeta m, const do
     if (c0) __syncthreads();
     for (int l = threadIdx.x; l < pw; l += NTH) {
       const int j = c0 + l;
-      const int gi = j < n ? m.gidx[off + j] : -1;
-      const double cn = (SCALE && j < n) ? m.cnt[off + j] : 1.0;
+      const int gi = j < n ? gidx[off + j] : -1;
+      const double cn = (SCALE && j < n) ? cnt[off + j] : 1.0;
 #pragma unroll
       for (int v = 0; v < KV; ++v) {
         double xv = 0.0;
@@ -1104,7 +1112,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_multi(DenseMeta m, const do
     for (int v = 0; v < KV; ++v) {
       const double sum = wave_sum(acc[k][v]);
       if (lane == 0 && r < n && v < kv)
-        yslots[(long long)v * slot_stride + m.out_pos[off + r]] = SCALE ? sum / m.cnt[off + r] : sum;
+        yslots[(long long)v * slot_stride + out_pos[off + r]] = SCALE ? sum / cnt[off + r] : sum;
     }
   }
 }
@@ -1145,26 +1153,41 @@ __global__ __launch_bounds__(NT) void k_assemble_slots_multi(int n, int width, c
 // Start-up: it_nxt = 0 marks the first PHASE 1 launch (alpha = 0, so r_new = r_0 and x is untouched;
 // p = 0 and rTz_prev = 1 make the first PHASE 0 produce p = z_0, it = 1, res_norm[1] = ||r_0||).
 struct PcgFold {
-  SolverState *st;
-  const double *con_in;     // [nloc*W] contributions to sum: S (PHASE 1) / ΠS (PHASE 0), local order
-  double *con_out;          // [nloc*W]
-  const double *part_in0;   // PHASE 1: partial p'Ap         PHASE 0: partial r'r
-  const double *part_in1;   //                               PHASE 0: partial r'z
+  // ---- what the head of a launch needs, contiguous at the front: with DenseMeta ahead of it in the kernel-argument segment
+  // these are fetched by ONE batch of scalar loads, issued together with the tile record and the state block (k_gemv_pcg)
   int n_in;
-  double *part_out0;        // PHASE 1: partial r'r          PHASE 0: partial p'Ap
-  double *part_out1;        // PHASE 1: partial r'z
-  double *r_cur, *r_nxt, *p_cur, *p_nxt;  // [nloc] local-order copies
-  double *x;                // [n_Γ]
-  const double *r_gamma;    // [n_Γ] r_0 in Γ order: the first PHASE 1 launch gathers it (no separate scatter pass)
-  double *res_norm;
-  const int *tgt;           // [nloc*W] where this row's result goes in each sharing subdomain's contribution row (-1 pad)
-  const int *peer;          // [nloc*W] local positions of the same Γ node in the sharing subdomains (-1 pad)
-  const int *jrank;         // [nloc] rank of this subdomain among the contributors of the node (0 = owner)
   int W;
+  // deflation (defcg.jl:291-305; nvec == 0: plain pcg). PHASE 1 also leaves per-tile partials of WtA*z; k_defl_mu turns
+  // them into mu = WtAW \ (WtA*z) and (W*mu) in local order; PHASE 0 subtracts that from beta*p + z.
+  int nvec;
+  int dbg_wg;               // MI355_FOLD_DEBUG: the workgroup that writes stamps (tested at the first stamp, right behind the exit)
   // inputs that come out of a peer exchange (exchange.hpp) are double-buffered by the parity of the exchange number:
   // con_in / part_in0 / part_in1 point at copy 0, copy (*in_epoch & 1) is in_stride doubles further
-  const unsigned long long *in_epoch;
   long long in_stride;
+  long long *dbg;           // MI355_FOLD_DEBUG: wall-clock stamps of workgroup dbg_wg, 8 per launch (tools/fold_stamps.py)
+  const double *r_gamma;    // [n_Γ] r_0 in Γ order: the first PHASE 1 launch gathers it (no separate scatter pass)
+  const int *jrank;         // [nloc] rank of this subdomain among the contributors of the node (0 = owner)
+  const int *peer;          // [nloc*W] local positions of the same Γ node in the sharing subdomains (-1 pad)
+  const int *tgt;           // [nloc*W] where this row's result goes in each sharing subdomain's contribution row (-1 pad)
+  double *r_cur, *r_nxt, *p_cur, *p_nxt;  // [nloc] local-order copies
+  double *x;                // [n_Γ]
+  const double *wm_loc;     // [nloc] (W*mu)[gidx[loc]]
+  // ---- used after the operand is staged
+  double *con_out;          // [nloc*W]
+  double *part_out0;        // PHASE 1: partial r'r          PHASE 0: partial p'Ap
+  double *part_out1;        // PHASE 1: partial r'z
+  double *res_norm;
+  long long n_gamma;
+  const double *AW;         // [nvec * n_Γ] WtA[v, :] = A*W[:, v], Γ order
+  double *part_mu;          // [nvec * ntiles(ΠS)] layout v * ntiles + tile
+  // ---- passed to the kernel as leading plain parameters (preloaded into SGPRs at wave start); the kernel does not read
+  // these copies, the launch (operators.hpp: gemv_pcg) takes them from here
+  SolverState *st;
+  const double *con_in;     // [nloc*W] contributions to sum: S (PHASE 1) / ΠS (PHASE 0), local order
+  const double *part_in0;   // PHASE 1: partial p'Ap         PHASE 0: partial r'r
+  const double *part_in1;   //                               PHASE 0: partial r'z
+  const unsigned long long *in_epoch;
+  // ---- peer exchange
   // outputs of a launch that is sharded over ranks and exchanged by peer stores (exchange.hpp): con_out / part_out0 /
   // part_out1 then point at copy 0 of the table in the OWN arena; every streamed tile stores its results into copy
   // ((epoch + 1) & 1) of the table in EVERY arena, publishes them and counts itself in; the last of the n_arrive tiles
@@ -1178,28 +1201,20 @@ struct PcgFold {
   // A launch whose inputs come out of an exchange (in_stride != 0) waits for the flags itself, with its first matrix loads
   // already in flight. The exchange number is then carried like it / it_nxt: a PHASE p launch reads xst->xep[p] and its
   // lead thread writes xst->xep[1 - p] (the launches alternate), so no workgroup reads a word its own launch writes.
-  const XchgPeers *xpw;     // peers to wait for (device copy)
   int x_inwait;
-  // deflation (defcg.jl:291-305; nvec == 0: plain pcg). PHASE 1 also leaves per-tile partials of WtA*z; k_defl_mu turns
-  // them into mu = WtAW \ (WtA*z) and (W*mu) in local order; PHASE 0 subtracts that from beta*p + z.
-  int nvec;
-  long long n_gamma;
-  const double *AW;         // [nvec * n_Γ] WtA[v, :] = A*W[:, v], Γ order
-  double *part_mu;          // [nvec * ntiles(ΠS)] layout v * ntiles + tile
-  const double *wm_loc;     // [nloc] (W*mu)[gidx[loc]]
+  const XchgPeers *xpw;     // peers to wait for (device copy)
+  // launch of an operator that is sharded over ranks (XCHG kernels only): the partials are summed by PART_LANES threads,
+  // so that ranks that chose different tilings for their slices associate the sum alike
+  int canon;
+  // ---- exit
   // whole-solve graphs: the PHASE 0 launch that meets the stop rule hands the results to the host itself (block 0),
   // so that the host is released before this launch and the graph's tail have drained
   const SolveArgs *exit_args;
   PinnedFlags *exit_flags;
-  long long *dbg;           // MI355_FOLD_DEBUG: wall-clock stamps of workgroup dbg_wg, 8 per launch (tools/fold_stamps.py)
-  int dbg_wg;
-  // launch of an operator that is sharded over ranks (XCHG kernels only): the partials are summed by PART_LANES threads,
-  // so that ranks that chose different tilings for their slices associate the sum alike
-  int canon;
 };
 constexpr int PART_LANES = 256;   // the smallest workgroup of the folded launches (4 waves)
 #define MI_FSTAMP(i) \
-  do { if (f.dbg && (int)blockIdx.x == f.dbg_wg && threadIdx.x == 0) f.dbg[dbg_row * 8 + (i)] = wall_clock64(); } while (0)
+  do { if (dbg && (int)blockIdx.x == dbg_wg && threadIdx.x == 0) dbg[dbg_row * 8 + (i)] = wall_clock64(); } while (0)
 __device__ __forceinline__ double slot_sum(const double *slots, int g, int W) {
   double s = 0.0;
   if (W == 4) {
@@ -1217,46 +1232,72 @@ __device__ __forceinline__ double slot_sum(const double *slots, int g, int W) {
 // FOLD_CPT = columns per thread staged in registers: the launch needs max n_Γd <= FOLD_CPT * 64 * WAVES (<= GEMV_PANEL)
 // XCHG = false compiles every peer-exchange branch out: the single-GPU launches are the kernel they were before.
 // MT = float: the blocks of this launch are stored as fp32 (PHASE 1, XCHG = false only: the Neumann-Neumann launch).
+// Arguments: the seven pointers in front of the structs are the 14 dwords gfx950 delivers in SGPRs when a wave starts
+// (kernel-argument preload, csrc/Makefile PRELOAD; a struct passed by value is never preloaded): what the first loads
+// of a launch dereference — tile record, state block, the partials and contributions to sum, the current copy of the
+// phase's vector (`vec_cur`: r_cur for PHASE 1, p_cur for PHASE 0), the exchange parity. The body reads these, not the
+// copies in `m` / `f`. (n_in and W would be dwords 15 and 16: they come with the one batch below instead — `in_epoch` has
+// to be dereferenced before the first vector load and would otherwise cost a sharded solve a round trip of its own.)
 template <int RPW, int PHASE, int FOLD_CPT, int WAVES, bool XCHG, typename MT = double>
-__global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f) {
+__global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(const GemvTile *tiles, SolverState *st, const double *part_in0_,
+                                                         const double *part_in1_, const double *con_in_, const double *vec_cur,
+                                                         const unsigned long long *in_epoch, DenseMeta m, PcgFold f) {
   constexpr int NTH = 64 * WAVES, NR = WAVES * RPW;  // threads and rows per workgroup
-  SolverState *st = f.st;
   const bool x_push = XCHG && f.xp != nullptr, x_inwait = XCHG && f.x_inwait != 0;
   // The tile record and the state block are requested together, before the stop flag is looked at (one memory round trip
   // instead of two at the top of every launch; the empty asm takes them all as inputs — without it the compiler sinks
-  // every load but `done` below the early exit).
-  const GemvTile t = m.tiles[blockIdx.x];
+  // every load but `done` below the early exit). Their addresses are in registers when the wave starts, and every other
+  // kernel argument the prologue needs is requested in the same batch: one scalar wait ahead of the first vector load.
+  const GemvTile t = tiles[blockIdx.x];
   const int done0 = st->done;
   const long long it0 = st->it, it_nxt0 = st->it_nxt, maxit = st->maxit, cap = st->res_cap;
   const double tol = st->tol, rTz0 = st->rTz, old = st->rTz_prev;
   const unsigned long long xo = XCHG && f.xst ? (x_inwait ? f.xst->xep[PHASE] : f.xst->epoch) : 0ull;   // (same round trip as the state block)
-  const unsigned long long xe = x_inwait ? xo : (f.in_epoch ? *f.in_epoch : 0ull);
+  const unsigned long long xe = x_inwait ? xo : (in_epoch ? *in_epoch : 0ull);
+  const int n_in = f.n_in, W = f.W, nvec = f.nvec;
+  const long long in_stride = f.in_stride;
+  const void *const Mp = m.M;
+  const int *const gidx = m.gidx, *const jrank = f.jrank, *const peer = f.peer, *const tgt = f.tgt;
+  const double *const cntp = m.cnt, *const r_gamma = f.r_gamma, *const vec_nxt = PHASE == 1 ? f.p_nxt : f.r_nxt;
+  double *const xg = f.x;
+  // (two statements: an asm takes 30 operands at most. The first holds the kernel arguments of the prologue, the debug
+  // stamps' included — MI_FSTAMP(0) tests them right behind the exit — and, for PHASE 1, of the epilogue's stores.)
+  double *const con_out = f.con_out, *const part_out0 = f.part_out0, *const part_out1 = PHASE == 1 ? f.part_out1 : nullptr;
+  long long *const dbg = f.dbg;
+  const int dbg_wg = f.dbg_wg;
+  const double *const AW = PHASE == 1 ? f.AW : nullptr;
+  double *const part_mu = PHASE == 1 ? f.part_mu : nullptr;
+  const long long n_gamma = f.n_gamma;
+  if constexpr (!XCHG)   // (the launches with peer exchange keep the compiler's placement: some of them sit at a VGPR step of the occupancy)
+    asm volatile("" ::"s"(n_in), "s"(W), "s"(nvec), "s"(in_stride), "s"(Mp), "s"(gidx), "s"(cntp), "s"(jrank), "s"(peer), "s"(tgt),
+                 "s"(r_gamma), "s"(vec_nxt), "s"(xg), "s"(dbg), "s"(dbg_wg), "s"(con_out), "s"(part_out0), "s"(part_out1), "s"(AW),
+                 "s"(part_mu), "s"(n_gamma));
   asm volatile("" ::"s"(t.mat_off), "s"(t.n), "s"(t.ld), "s"(t.loc_off), "s"(t.row0), "s"(t.active), "s"(t.nrows), "s"(it0),
                "s"(it_nxt0), "s"(maxit), "s"(cap), "s"(tol), "s"(rTz0), "s"(old), "s"(done0), "s"(xe), "s"(xo));
   if (done0) return;
   GemvRows<RPW, MT> rows;
-  if (x_inwait && f.in_stride) {
+  if (x_inwait && in_stride) {
     // the tables this launch reads are complete when every rank's flag in the own arena has reached the exchange number
-    if (t.active) rows.begin(m, t);      // (the matrix does not depend on them: its first loads travel while the flags are polled)
+    if (t.active) rows.begin(Mp, t);      // (the matrix does not depend on them: its first loads travel while the flags are polled)
     if (threadIdx.x < 64) xchg_wait(f.xst, *f.xpw, xo);
     __syncthreads();
     // (the tables sit in fine-grained memory — no level of cache keeps their lines across the peers' stores; the vector
     // caches were emptied when this launch began and have not seen the tables since)
     if (__hip_atomic_load(&f.xst->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;   // expired: the solve fails with MI_ERR_COMM
   }
-  const bool streaming = x_inwait && f.in_stride;
-  const long long xoff = (long long)(xe & 1ull) * f.in_stride;
-  const double *con_in = f.con_in + xoff, *part_in0 = f.part_in0 + xoff, *part_in1 = PHASE == 0 ? f.part_in1 + xoff : nullptr;
+  const bool streaming = x_inwait && in_stride;
+  const long long xoff = (long long)(xe & 1ull) * in_stride;
+  const double *con_in = con_in_ + xoff, *part_in0 = part_in0_ + xoff, *part_in1 = PHASE == 0 ? part_in1_ + xoff : nullptr;
   __shared__ __attribute__((aligned(16))) double xs[GEMV_PANEL];
   __shared__ double sm[2 * (NTH / 64)];
   __shared__ double rowv[NR], rowc0[NR], rowc1[NR];
   __shared__ double rowy[NR];   // deflation: the rows' z-contributions
   __shared__ int rowg[NR];      //            and their Γ indices
-  const int off = t.loc_off, W = f.W, n = t.n;
+  const int off = t.loc_off, n = t.n;
   const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
   if (threadIdx.x < NR) { rowc0[threadIdx.x] = 0.0; rowv[threadIdx.x] = 0.0; rowy[threadIdx.x] = 0.0; rowg[threadIdx.x] = 0; }  // visible after the barrier of the sums
 #if !MI355_OPERAND_FIRST
-  if (t.active && !streaming) rows.begin(m, t);  // matrix stream in flight from here on
+  if (t.active && !streaming) rows.begin(Mp, t);  // matrix stream in flight from here on
 #endif
 
   // ---- every load of the prologue is issued before the first barrier (one memory round trip), all contiguous
@@ -1268,13 +1309,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
   // decide how the sum is associated — alpha, beta and the stop rule would then differ between the ranks in the last bits:
   // its first PART_LANES threads sum, whatever WAVES is (the other waves add zeros to the tree below: exact).
   const int SL = XCHG && f.canon ? PART_LANES : NTH;
-  for (int i0 = XCHG && f.canon && threadIdx.x >= PART_LANES ? f.n_in : (int)threadIdx.x; i0 < f.n_in; i0 += 8 * SL) {  // up to eight partials in flight per thread, added in order
+  for (int i0 = XCHG && f.canon && threadIdx.x >= PART_LANES ? n_in : (int)threadIdx.x; i0 < n_in; i0 += 8 * SL) {  // up to eight partials in flight per thread, added in order
     double ta[8], tb[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int i = i0 + k * SL;
-      ta[k] = i < f.n_in ? part_in0[i] : 0.0;
-      tb[k] = PHASE == 0 && i < f.n_in ? part_in1[i] : 0.0;
+      ta[k] = i < n_in ? part_in0[i] : 0.0;
+      tb[k] = PHASE == 0 && i < n_in ? part_in1[i] : 0.0;
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) { pa += ta[k]; if (PHASE == 0) pb += tb[k]; }
@@ -1287,8 +1328,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
     if (j < n) {
       const int loc = off + j;
       cs[q] = slot_sum(con_in, loc, W);
-      if (PHASE == 1) { cv[q] = first1 ? f.r_gamma[m.gidx[loc]] : f.r_cur[loc]; cc[q] = m.cnt[loc]; }
-      else { cv[q] = f.p_cur[loc]; if (f.nvec > 0) cc[q] = f.wm_loc[loc]; }
+      if (PHASE == 1) { cv[q] = first1 ? r_gamma[gidx[loc]] : vec_cur[loc]; cc[q] = cntp[loc]; }
+      else { cv[q] = vec_cur[loc]; if (nvec > 0) cc[q] = f.wm_loc[loc]; }
     }
   }
   // The thread whose column j is also a row of this tile serves that row (at most one column per thread:
@@ -1306,14 +1347,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
       // everything an owner needs is requested unconditionally (a load behind `if (owner)` would wait for jrank first:
       // a second memory round trip on the way to the operand barrier); x[g] — a dependent load — is consumed only in the
       // epilogue, after the matrix stream
-      o_own = f.jrank[loc] == 0;
-      if (PHASE == 1) { o_a = first1 ? 0.0 : f.p_nxt[loc]; o_g = m.gidx[loc]; }
-      else o_a = f.r_nxt[loc];
+      o_own = jrank[loc] == 0;
+      if (PHASE == 1) { o_a = first1 ? 0.0 : vec_nxt[loc]; o_g = gidx[loc]; }
+      else o_a = vec_nxt[loc];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) if (k < W) o_peer[k] = f.peer[loc * W + k];
+      for (int k = 0; k < 4; ++k) if (k < W) o_peer[k] = peer[loc * W + k];
     }
   }
-  if (PHASE == 1 && o_q >= 0 && o_own) o_x = f.x[o_g];
+  if (PHASE == 1 && o_q >= 0 && o_own) o_x = xg[o_g];
   // lane 0 of every wave stores the results of its RPW rows into the contribution rows of all sharing subdomains
   int e_tgt[RPW][4];
   double e_cnt[RPW];
@@ -1325,9 +1366,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
     for (int q = 0; q < 4; ++q) e_tgt[k][q] = -1;
     if ((threadIdx.x & 63) == 0 && r < n) {
       const int loc = off + r;
-      if (PHASE == 1) e_cnt[k] = m.cnt[loc];
+      if (PHASE == 1) e_cnt[k] = cntp[loc];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) if (q < W) e_tgt[k][q] = f.tgt[loc * W + q];
+      for (int q = 0; q < 4; ++q) if (q < W) e_tgt[k][q] = tgt[loc * W + q];
     }
   }
 
@@ -1335,10 +1376,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
   int x_tgt = -1;
   if (x_push && t.active && threadIdx.x < 4 * NR) {
     const int r = t.row0 + (int)(threadIdx.x >> 2), k = threadIdx.x & 3;
-    if (r < n && k < W) x_tgt = f.tgt[(off + r) * W + k];
+    if (r < n && k < W) x_tgt = tgt[(off + r) * W + k];
   }
 #if MI355_OPERAND_FIRST
-  if (t.active && !streaming) rows.begin(m, t);  // matrix stream in flight from here on: issued AFTER the prologue's loads (results return in issue order)
+  if (t.active && !streaming) rows.begin(Mp, t);  // matrix stream in flight from here on: issued AFTER the prologue's loads (results return in issue order)
 #endif
   MI_FSTAMP(1);   // all prologue loads and the first matrix group issued
   // ---- scalars
@@ -1373,7 +1414,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
       if (f.exit_args && blockIdx.x == 0) {
         // x is final (the ΠS launch before this one stored it): results to the caller, then ONE store of the solve number
         const SolveArgs q = *f.exit_args;
-        for (long long i = threadIdx.x; i < f.n_gamma; i += NTH) q.x_out[i] = f.x[i];
+        for (long long i = threadIdx.x; i < n_gamma; i += NTH) q.x_out[i] = xg[i];
         if (q.res_stage) {
           const long long mres = it_new < q.ncap ? it_new : q.ncap;
           for (long long i = threadIdx.x; i < mres; i += NTH) q.res_stage[i] = i == it_new - 1 ? res : f.res_norm[i];
@@ -1404,14 +1445,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
         // values, and 0 * NaN left there by a solve that ended non-finite would poison every later solve)
         v = PHASE == 1 ? (first1 ? cv[q] : cv[q] + (-coef) * cs[q])   // r - alpha*Ap
                        : coef * cv[q] + cs[q];                        // beta*p + z
-        if (PHASE == 0 && f.nvec > 0) v = v - cc[q];                  // ... - W*mu (defcg.jl:303)
+        if (PHASE == 0 && nvec > 0) v = v - cc[q];                  // ... - W*mu (defcg.jl:303)
         vs = PHASE == 1 ? v / cc[q] : v;
       }
       xs[j] = vs;
       if (q == o_q) {
         const int ri = j - t.row0;
         if (t.active) rowv[ri] = v;
-        if (PHASE == 1 && f.nvec > 0) rowg[ri] = o_g;
+        if (PHASE == 1 && nvec > 0) rowg[ri] = o_g;
         if (o_own) {                                      // owner of this Γ node
           if (PHASE == 1) {
             if (t.active) rowc0[ri] = v * v;
@@ -1436,7 +1477,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
   // owner stores of p / r, x) and stops here; its contribution rows and partial dots come from the owning rank through the
   // exchange that follows the launch (its own entries stay zero).
   if (!t.active) {
-    if (PHASE == 1 && o_q >= 0 && o_own) f.x[o_g] = o_x + coef * o_a;  // x + alpha*p (cg.jl:97)
+    if (PHASE == 1 && o_q >= 0 && o_own) xg[o_g] = o_x + coef * o_a;  // x + alpha*p (cg.jl:97)
     return;
   }
   MI_FSTAMP(3);   // operand staged
@@ -1456,7 +1497,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int tg = e_tgt[k][q];
-            if (tg >= 0) f.con_out[tg] = y;
+            if (tg >= 0) con_out[tg] = y;
           }
         }
       }
@@ -1464,7 +1505,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
       if (PHASE == 1 || x_push) rowy[ri] = y;
     }
   }
-  if (PHASE == 1 && o_q >= 0 && o_own) f.x[o_g] = o_x + coef * o_a;  // x + alpha*p (cg.jl:97), off the critical path
+  if (PHASE == 1 && o_q >= 0 && o_own) xg[o_g] = o_x + coef * o_a;  // x + alpha*p (cg.jl:97), off the critical path
   __syncthreads();
   MI_FSTAMP(5);   // results scattered
   const long long xpo = (long long)((xo + 1) & 1ull) * f.out_stride;
@@ -1475,11 +1516,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
     for (int q = 0; q < P.n; ++q)
       xchg_store(reinterpret_cast<double *>(reinterpret_cast<char *>(f.con_out) + (P.arena[q] - own)) + xpo + x_tgt, y);
   }
-  if (PHASE == 1 && f.nvec > 0 && (int)threadIdx.x >= 64 && (int)threadIdx.x < 64 + f.nvec) {
+  if (PHASE == 1 && nvec > 0 && (int)threadIdx.x >= 64 && (int)threadIdx.x < 64 + nvec) {
     // per-tile partial of WtA*z (defcg.jl:301): sum over this tile's rows of WtA[v, g(row)] * (z-contribution of the row);
     // the second wave does it while the first one reduces the dot products (nvec <= 64)
     const int v = (int)threadIdx.x - 64;
-    const double *aw = f.AW + (long long)v * f.n_gamma;
+    const double *aw = AW + (long long)v * n_gamma;
     double s = 0.0;
     for (int i0 = 0; i0 < NR; i0 += 8) {
       double a[8];
@@ -1489,7 +1530,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
       for (int k = 0; k < 8; ++k)
         if (i0 + k < NR) s += a[k] * rowy[i0 + k];
     }
-    f.part_mu[(long long)v * gridDim.x + blockIdx.x] = s;
+    part_mu[(long long)v * gridDim.x + blockIdx.x] = s;
   }
   if (threadIdx.x < 64) {  // per-tile partials of the next dot products: one shuffle tree over the NR row terms
     double a = 0.0, b = 0.0;
@@ -1499,8 +1540,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pcg(DenseMeta m, PcgFold f)
     if (threadIdx.x == 0) {
       const int ps = t.active - 1;   // the tile number on one GPU; a tiling-independent slot when the launch is sharded over ranks
       if (!x_push) {
-        if (PHASE == 1) { f.part_out1[ps] = a; f.part_out0[ps] = b; }
-        else f.part_out0[ps] = a;
+        if (PHASE == 1) { part_out1[ps] = a; part_out0[ps] = b; }
+        else part_out0[ps] = a;
       } else {
         const XchgPeers &P = *f.xp;
         const char *own = P.arena[P.rank];
@@ -1959,9 +2000,9 @@ __global__ __launch_bounds__(NT) void k_gather_w_loc(int nvec, long long n_gamma
 // wm_loc[loc] = (W*mu)[gidx[loc]] in column-axpy order (`W * mu`, defcg.jl:303) for this workgroup's slice of the
 // local positions, where the S launch reads it contiguously. 1024 threads: 16 per deflation vector for the sums.
 __global__ __launch_bounds__(1024) void k_defl_mu(const SolverState *st, int nvec, int ntiles, const double *__restrict__ part_mu,
-                                                  const double *__restrict__ LU, const int *__restrict__ piv,
-                                                  const double *__restrict__ W, long long n_gamma, int nloc,
-                                                  const int *__restrict__ gidx, double *__restrict__ wm_loc,
+                                                  const double *__restrict__ LU, const int *__restrict__ piv, int nloc,
+                                                  const int *__restrict__ gidx,   // (up to here: preloaded into SGPRs at wave start)
+                                                  const double *__restrict__ W, long long n_gamma, double *__restrict__ wm_loc,
                                                   double *__restrict__ mu_out, const double *__restrict__ W_loc) {
   // One memory round trip for everything whose address is known at launch (stop flag, LU factors, pivots, Γ index, the
   // first batch of partials), a second one for the W entries behind the Γ index: the kernel is nothing but latency.

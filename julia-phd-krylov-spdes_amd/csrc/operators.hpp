@@ -515,9 +515,11 @@ struct DenseBlockOp : Operator {
   void gemv(const double *x, const int *done) {
     if (!ntiles) return;
     const int *zx = zero_hint;
-#define MI_GEMV(R, S, V) hipLaunchKernelGGL((k_gemv_batched<R, S, V>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, x, yslots.p, done, zx)
+    // (the seven leading pointers are preloaded into SGPRs at wave start: kernels.hpp)
+#define MI_GEMV_HEAD meta.tiles, done, zx, meta.gidx, x, meta.cnt, meta.M
+#define MI_GEMV(R, S, V) hipLaunchKernelGGL((k_gemv_batched<R, S, V>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, MI_GEMV_HEAD, yslots.p, meta.out_pos)
 #define MI_GEMV_R(S, V) do { if (rpw == 1) MI_GEMV(1, S, V); else if (rpw == 2) MI_GEMV(2, S, V); else MI_GEMV(4, S, V); } while (0)
-#define MI_GEMV32(R, V) hipLaunchKernelGGL((k_gemv_batched<R, true, V, float>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, x, yslots.p, done, zx)
+#define MI_GEMV32(R, V) hipLaunchKernelGGL((k_gemv_batched<R, true, V, float>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, MI_GEMV_HEAD, yslots.p, meta.out_pos)
 #define MI_GEMV32_R(V) do { if (rpw == 1) MI_GEMV32(1, V); else if (rpw == 2) MI_GEMV32(2, V); else MI_GEMV32(4, V); } while (0)
     if (f32())           { if (waves == 16) MI_GEMV32_R(16); else if (waves == 8) MI_GEMV32_R(8); else MI_GEMV32_R(4); }
     else if (waves == 16) { if (scale) MI_GEMV_R(true, 16); else MI_GEMV_R(false, 16); }
@@ -527,6 +529,7 @@ struct DenseBlockOp : Operator {
 #undef MI_GEMV32
 #undef MI_GEMV_R
 #undef MI_GEMV
+#undef MI_GEMV_HEAD
     MI_HIP(hipGetLastError());
   }
   void apply(const double *x, double *y, const int *done) override {
@@ -555,7 +558,8 @@ struct DenseBlockOp : Operator {
     for (int v0 = 0; v0 < k; v0 += KV) {
       const int kv = std::min(KV, k - v0);
       const double *Xv = X + (size_t)v0 * ldx;
-#define MI_GM(S) hipLaunchKernelGGL((k_gemv_multi<2, KV, S, 16>), dim3(ntiles), dim3(1024), 0, ctx->stream, meta, Xv, (long long)ldx, kv, yslots_multi.p, stride)
+#define MI_GM(S) hipLaunchKernelGGL((k_gemv_multi<2, KV, S, 16>), dim3(ntiles), dim3(1024), 0, ctx->stream, meta.tiles, meta.gidx, Xv, meta.cnt, \
+                                    static_cast<const double *>(meta.M), (long long)ldx, kv, yslots_multi.p, stride, meta.out_pos)
       if (scale) MI_GM(true); else MI_GM(false);
 #undef MI_GM
       hipLaunchKernelGGL(k_assemble_slots_multi, dim3(vec_grid(n), kv), dim3(NT), 0, ctx->stream, (int)n, maps.slot_width,
@@ -571,9 +575,11 @@ struct DenseBlockOp : Operator {
     const bool xchg = f.xp != nullptr || f.x_inwait != 0 || f.canon != 0;
     // fp32-stored blocks have the ΠS launch without peer exchange only (Krylov's fold decision keeps everything else away)
     if (f32() && (phase != 1 || xchg)) raise(MI_ERR_BAD_ARG, "folded PCG launch: no fp32 kernel for phase %d%s", phase, xchg ? " with peer exchange" : "");
-#define MI_PCG4(R, P, C, V) do { if (xchg) hipLaunchKernelGGL((k_gemv_pcg<R, P, C, V, true>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, f); \
-                                 else hipLaunchKernelGGL((k_gemv_pcg<R, P, C, V, false>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, f); } while (0)
-#define MI_PCG32(R, C, V) hipLaunchKernelGGL((k_gemv_pcg<R, 1, C, V, false, float>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, meta, f)
+    // the leading plain arguments (preloaded into SGPRs at wave start): what the first loads of a launch dereference
+#define MI_PCG_HEAD(P) meta.tiles, f.st, f.part_in0, f.part_in1, f.con_in, static_cast<const double *>((P) ? f.r_cur : f.p_cur), f.in_epoch
+#define MI_PCG4(R, P, C, V) do { if (xchg) hipLaunchKernelGGL((k_gemv_pcg<R, P, C, V, true>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, MI_PCG_HEAD(P), meta, f); \
+                                 else hipLaunchKernelGGL((k_gemv_pcg<R, P, C, V, false>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, MI_PCG_HEAD(P), meta, f); } while (0)
+#define MI_PCG32(R, C, V) hipLaunchKernelGGL((k_gemv_pcg<R, 1, C, V, false, float>), dim3(ntiles), dim3(64 * V), 0, ctx->stream, MI_PCG_HEAD(1), meta, f)
 #define MI_PCG3(R, C, V) do { if (f32()) MI_PCG32(R, C, V); else if (phase) MI_PCG4(R, 1, C, V); else MI_PCG4(R, 0, C, V); } while (0)
 #define MI_PCG2(R, V) do { const int c = (max_ld + 64 * V - 1) / (64 * V); \
                            if (c <= 2) MI_PCG3(R, 2, V); else if (c == 3) MI_PCG3(R, 3, V); else if (c == 4) MI_PCG3(R, 4, V); \
@@ -585,6 +591,7 @@ struct DenseBlockOp : Operator {
 #undef MI_PCG3
 #undef MI_PCG32
 #undef MI_PCG4
+#undef MI_PCG_HEAD
     MI_HIP(hipGetLastError());
   }
   bool same_maps(const DenseBlockOp &o) const {

@@ -423,7 +423,7 @@ struct Krylov {
       if (Md->reduce_over_ranks) Md->reduce_fold(dn, inwait());  // ΠS contributions + partial r'r, r'z: union over the ranks
       if (nvec > 0) {  // mu = WtAW \ (WtA * z); W*mu in local order for the S launch (defcg.jl:301-303)
         hipLaunchKernelGGL(k_defl_mu, dim3((Ad->maps.nloc + 1023) / 1024), dim3(1024), 0, s, ws.st, nvec, Md->ntiles, ws.fold_mu.p,
-                           ws.LU.p, ws.piv.p, ws.W.p, (long long)n, Ad->maps.nloc, Ad->maps.gidx.p, ws.fold_wm.p, ws.mu.p, ws.fold_wloc.p);
+                           ws.LU.p, ws.piv.p, Ad->maps.nloc, Ad->maps.gidx.p, ws.W.p, (long long)n, ws.fold_wm.p, ws.mu.p, ws.fold_wloc.p);
         MI_HIP(hipGetLastError());
       }
       Ad->gemv_pcg(0, fold_args(0));
@@ -474,8 +474,8 @@ struct Krylov {
       const int grid = ((Ac->nblocks + 7) / 8) * 8;
       double *pz0 = ws.cf_pz.p, *pz1 = pz0 + 2 * (size_t)n;
       CsrOp *co = static_cast<CsrOp *>(A);
-      hipLaunchKernelGGL(k_spmv_pcg, dim3(grid), dim3(NT), 0, s, Ac->nblocks, Ac->blk.p, Ac->rowptr.p, Ac->col.p, Ac->val.p, ws.st,
-                         ws.cf_rr.p, ws.cf_rz.p, CF_VEC_GRID, pz0, pz1, ws.Ap, co->dot_part.p, ws.res_norm.p, pre);
+      hipLaunchKernelGGL(k_spmv_pcg, dim3(grid), dim3(NT), 0, s, Ac->nblocks, pre, Ac->blk.p, ws.st, ws.cf_rr.p, ws.cf_rz.p, CF_VEC_GRID,
+                         Ac->rowptr.p, Ac->col.p, Ac->val.p, pz0, pz1, ws.Ap, co->dot_part.p, ws.res_norm.p);
       hipLaunchKernelGGL(k_update_xr_blk, dim3(CF_VEC_GRID), dim3(NT), 0, s, Ac->xcd_row.p, ws.st, co->dot_part.p, Ac->nblocks, pz0,
                          pz1, ws.Ap, ws.x, ws.r, dinv, diag, pre, ws.cf_rr.p, ws.cf_rz.p);
       MI_HIP(hipGetLastError());

@@ -269,14 +269,14 @@ int main(int argc, char **argv) {
     for (int k = 0; k < 2; ++k) {
       CK(hipMemsetAsync(y, 0, ops[k].nloc * 8, s));
       DenseMeta m{ops[k].M, ops[k].tiles, ops[k].gidx, ops[k].cnt, ops[k].out_pos};
-      hipLaunchKernelGGL((k_gemv_batched<2, false, 16>), dim3(ops[k].ntiles), dim3(1024), 0, s, m, x, y, (const int *)nullptr, (const int *)nullptr);
+      hipLaunchKernelGGL((k_gemv_batched<2, false, 16>), dim3(ops[k].ntiles), dim3(1024), 0, s, m.tiles, (const int *)nullptr, (const int *)nullptr, m.gidx, x, m.cnt, m.M, y, m.out_pos);
       CK(hipStreamSynchronize(s));
       check(ops[k], y, yref[k], "baseline");
     }
     const double us = time_graph(s, 40, 10, [&](int i) {
       const Op &o = ops[i & 1];
       DenseMeta m{o.M, o.tiles, o.gidx, o.cnt, o.out_pos};
-      hipLaunchKernelGGL((k_gemv_batched<2, false, 16>), dim3(o.ntiles), dim3(1024), 0, s, m, x, y, (const int *)nullptr, (const int *)nullptr);
+      hipLaunchKernelGGL((k_gemv_batched<2, false, 16>), dim3(o.ntiles), dim3(1024), 0, s, m.tiles, (const int *)nullptr, (const int *)nullptr, m.gidx, x, m.cnt, m.M, y, m.out_pos);
     });
     printf("%-44s tiles=%4d  %7.2f us  %6.2f TB/s  frac %.3f\n", "baseline k_gemv_batched<2,16> 32-row tiles", ops[0].ntiles, us,
            ops[0].alg_bytes / us / 1e6, ops[0].alg_bytes / us / 1e6 / 8.0);
@@ -288,7 +288,7 @@ int main(int argc, char **argv) {
     const double us0 = time_graph(s, 40, 10, [&](int i) {
       const Op &o = ops[i & 1];
       DenseMeta m{o.M, o.tiles, o.gidx, o.cnt, o.out_pos};
-      hipLaunchKernelGGL((k_gemv_batched<2, false, 16>), dim3(o.ntiles), dim3(1024), 0, s, m, x, y, (const int *)one, (const int *)nullptr);
+      hipLaunchKernelGGL((k_gemv_batched<2, false, 16>), dim3(o.ntiles), dim3(1024), 0, s, m.tiles, (const int *)one, (const int *)nullptr, m.gidx, x, m.cnt, m.M, y, m.out_pos);
     });
     printf("%-44s tiles=%4d  %7.2f us\n", "same grid, early exit", ops[0].ntiles, us0);
   }

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_ring(DenseMeta m, const dou
     // for 128 KB of matrix requests in the CU's queue, so the stream starts thin and is topped up once the vector waves
     // have issued their second hop (barrier B): the ring then covers the rest of the gather and the staging.
     RingStream<D> rs;
-    rs.begin(m.M + t.mat_off + (long long)t.row0 * t.ld, t.ld, t.nrows, w, SW, lds_addr(ring) + (unsigned)w * (D * 1024u));
+    rs.begin(static_cast<const double *>(m.M) + t.mat_off + (long long)t.row0 * t.ld, t.ld, t.nrows, w, SW, lds_addr(ring) + (unsigned)w * (D * 1024u));
     if ((threadIdx.x & 63) == 0) {
       wrow[2 * w] = (int)((unsigned)rs.u0 / (unsigned)rs.ppr);
       wrow[2 * w + 1] = rs.u1 > rs.u0 ? (int)((unsigned)(rs.u1 - 1) / (unsigned)rs.ppr) : -1;
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemv_pipe(DenseMeta m, const dou
     cn[q] = SCALE && j < n ? m.cnt[off + j] : 1.0;
   }
   PipeStream<NB> ps;
-  ps.begin(m.M + t.mat_off + (long long)t.row0 * t.ld, t.ld, t.nrows, w, WAVES);
+  ps.begin(static_cast<const double *>(m.M) + t.mat_off + (long long)t.row0 * t.ld, t.ld, t.nrows, w, WAVES);
   if ((threadIdx.x & 63) == 0) {
     wrow[2 * w] = (int)((unsigned)ps.u0 / (unsigned)ps.ppr);
     wrow[2 * w + 1] = ps.total > 0 ? (int)((unsigned)(ps.u0 + ps.total - 1) / (unsigned)ps.ppr) : -1;
