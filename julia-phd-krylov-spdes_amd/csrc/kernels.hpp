@@ -545,7 +545,7 @@ __global__ __launch_bounds__(NT) void k_icg_start(IcgMeta m, const double *p_rr,
     m.rho_cur[d] = rho; m.rho_nxt[d] = rho;
     m.tol[d] = reltol * res;
     m.iters[d] = 0;
-    const int dn = res <= m.tol[d];
+    const int dn = !(res > m.tol[d]);   // `while residual > tol`: a NaN residual ends the solve at x = 0, as in k_icg_spmv
     m.done_cur[d] = dn; m.done_nxt[d] = dn;
   }
 }
@@ -626,7 +626,7 @@ __global__ __launch_bounds__(NT) void k_icg_direction(IcgMeta m, const IcgPiece 
     m.res_nxt[d] = res;
     if (m.dinv) m.rho_nxt[d] = rho;
     const int maxiter = m.maxiter_cap > 0 ? m.maxiter_cap : n_i[d];
-    m.done_nxt[d] = (res <= m.tol[d]) || (it >= maxiter);
+    m.done_nxt[d] = !(res > m.tol[d]) || (it >= maxiter);
   }
 }
 

@@ -250,7 +250,8 @@ inline SolverWorkspace &workspace(mi_ctx_s *ctx, int64_t n) {
   return *slot;
 }
 
-// LAPACK getrf (unblocked, partial pivoting) on a column-major copy. Returns 0 or k+1 for U[k,k]==0.
+// LAPACK getrf (unblocked, partial pivoting) on a column-major copy. Returns 0 or k+1 for U[k,k]==0. A pivot that is NaN or
+// Inf is no zero pivot: getrf reports info = 0 and `WtAW \ mu` returns NaN, which ends the solve at it = 1 (res_norm[1] = NaN).
 inline int host_lu(int n, std::vector<double> &a, std::vector<int> &piv) {
   piv.resize(n);
   for (int k = 0; k < n; ++k) {
@@ -261,7 +262,7 @@ inline int host_lu(int n, std::vector<double> &a, std::vector<int> &piv) {
       if (v > mx) { mx = v; p = i; }
     }
     piv[k] = p;
-    if (a[p + (size_t)k * n] == 0.0 || !std::isfinite(a[p + (size_t)k * n])) return k + 1;
+    if (a[p + (size_t)k * n] == 0.0) return k + 1;
     if (p != k)
       for (int j = 0; j < n; ++j) std::swap(a[k + (size_t)j * n], a[p + (size_t)j * n]);
     const double piv_inv = 1.0 / a[k + (size_t)k * n];

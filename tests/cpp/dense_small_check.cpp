@@ -1,14 +1,61 @@
 // CPU check of csrc/dense_small.hpp (host-side Jacobi eigen / SVD used by the eigCG restarts).
 // Reads nothing; prints max errors for random cases; exit code 0 when all are below tolerance.
+// With the argument `nonfinite`: sym_eig_upper, svd_left and ritz_restart on inputs that hold NaN, +Inf or -Inf in one
+// diagonal entry, in one off-diagonal entry or everywhere; one JSON line per case. Every call has to return (the sweeps
+// are bounded at 100 and 60) with nev <= m and m * nev entries in G; the values themselves are not checked.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 
 #include "../../julia-phd-krylov-spdes_amd/csrc/dense_small.hpp"
 
 using namespace mi::dense;
 
-int main() {
+static int nonfinite() {
+  const double inf = std::numeric_limits<double>::infinity();
+  const double values[3] = {std::numeric_limits<double>::quiet_NaN(), inf, -inf};
+  const char *vname[3] = {"nan", "+inf", "-inf"};
+  const char *where[3] = {"diagonal", "off-diagonal", "everywhere"};
+  int bad = 0;
+  for (auto mn : {std::pair<int, int>{3, 1}, {6, 2}, {24, 10}, {70, 33}}) {
+    const int m = mn.first, nvec = mn.second, k = 2 * nvec;
+    for (int v = 0; v < 3; ++v)
+      for (int w = 0; w < 3; ++w) {
+        std::mt19937_64 rng(100 * m + 10 * v + w);
+        std::normal_distribution<double> nd;
+        Mat T((size_t)m * m, 0.0);   // Lanczos-like: upper triangle of a tridiagonal
+        for (int i = 0; i < m; ++i) { T[i + (size_t)i * m] = 2.0 + 0.1 * i; if (i) T[(i - 1) + (size_t)i * m] = -1.0; }
+        Mat Y((size_t)m * k);
+        for (auto &y : Y) y = nd(rng);
+        const int i0 = m / 2;
+        if (w == 0) { T[i0 + (size_t)i0 * m] = values[v]; Y[(i0 % k) * (size_t)m + i0] = values[v]; }
+        if (w == 1) { T[(i0 - 1 >= 0 ? i0 - 1 : 0) + (size_t)(i0 ? i0 : 1) * m] = values[v]; Y[(size_t)((i0 + 1) % k) * m + i0] = values[v]; }
+        if (w == 2) {
+          for (int j = 0; j < m; ++j)
+            for (int i = 0; i <= j; ++i) T[i + (size_t)j * m] = values[v];
+          for (auto &y : Y) y = values[v];
+        }
+        int returned = 0;
+        std::vector<double> vals, s;
+        Mat V, U;
+        sym_eig_upper(m, T.data(), m, vals, V);
+        returned += (int)vals.size() == m && V.size() == (size_t)m * m;
+        svd_left(m, k, Y, s, U);
+        returned += (int)s.size() == k && U.size() == (size_t)m * k;
+        Ritz R = ritz_restart(T.data(), m, m, nvec);
+        returned += (int)R.vals.size() == R.nev;
+        const bool ok = returned == 3 && R.nev >= 0 && R.nev <= m && R.G.size() == (size_t)m * R.nev;
+        bad += !ok;
+        std::printf("{\"m\": %d, \"nvec\": %d, \"value\": \"%s\", \"where\": \"%s\", \"returned\": %d, \"nev\": %d, \"g_size\": %zu}\n",
+                    m, nvec, vname[v], where[w], returned, R.nev, R.G.size());
+      }
+  }
+  return bad ? 1 : 0;
+}
+
+int main(int argc, char **argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "nonfinite")) return nonfinite();
   std::mt19937_64 rng(7);
   std::normal_distribution<double> nd;
   double worst = 0.0;

@@ -366,7 +366,7 @@ def run(mod, s, A, M, b, x0, W):
 
 # ------------------------------------------------------------------ the same solvers in numpy, another summation order
 def _psum(a, b):
-    return float(np.sum(a * b))          # pairwise; the oracle's orc_dot adds left to right
+    return np.sum(a * b)                 # pairwise; the oracle's orc_dot adds left to right. np.float64: x / 0 is IEEE's inf
 
 
 def numpy_apply(probs, prob, which):
