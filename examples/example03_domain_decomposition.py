@@ -7,9 +7,16 @@ interior solves of the set-up are direct, the least-dominant eigenvectors come f
 on the host instead of KrylovKit (Example03:209).
 
     python examples/example03_domain_decomposition.py [--N 100 --px 2 --py 2] [--lorasc] [--nn-induced {reference,assembled}]
+                                                      [--device-eigs]
 
 `--lorasc` adds Example03:245-256: `prepare_lorasc_precond` (host, dense generalized eigenpairs of (S, A_ΓΓ)) and
 `pcg(A, b, zeros, ΠA_lorasc)` with the device LORASC preconditioner.
+
+`--device-eigs` takes every eigenpair from the device eigensolver instead (thick-restart Lanczos, `api.eigsolve` /
+`api.geneigsolve`): the `ld` / `md` bases of Example03:209/219 from `S_local_mat`, the LORASC pairs of EPDD.jl:1546-1549 from
+the pencil `(S_local_mat, A_ΓΓ)` with `chol_A_ΓΓ` as the inverse, and `Arpack.eigs(A, nev, :SM)` (Example03:311) as the
+largest eigenvalues θ of `A \\ b` (`BlockJacobiPreconditioner(ctx, 1, A)`), λ = 1/θ. The printed iteration counts are those
+of the default path.
 
 `--nn-induced` adds Example03:300-319: `prepare_neumann_neumann_induced_precond`, then `defpcg(A, b, ϕ, M=ΠA_induced_nn)`
 with the least dominant eigenvectors of A and `pcg(A, b, M=ΠA_induced_nn)` on the full system. `reference` is the
@@ -40,6 +47,8 @@ def parse_args(argv=None):
     ap.add_argument("--lorasc", action="store_true", help="also run the LORASC leg, Example03:245-256")
     ap.add_argument("--nn-induced", choices=("reference", "assembled"), default=None,
                     help="also run the Neumann-Neumann induced leg, Example03:300-319, with this coupling (EPDD.jl:2411)")
+    ap.add_argument("--device-eigs", action="store_true",
+                    help="eigenpairs from the device eigensolver (api.eigsolve / api.geneigsolve) instead of the dense host detour")
     return ap.parse_args(argv)
 
 
@@ -50,6 +59,21 @@ def lowest_eigvecs(A, nev, extra=6, rtol=1e-8):
     lam, V = spla.eigsh(sp.csc_matrix(A), k=min(nev + extra, A.shape[0] - 1), sigma=0.0, which="LM")
     order = np.argsort(lam)
     lam, V = lam[order], V[:, order]
+    m = nev
+    while m < lam.size and lam[m] - lam[nev - 1] <= rtol * lam[nev - 1]:
+        m += 1
+    return np.asfortranarray(V[:, :m])
+
+
+def lowest_eigvecs_device(api, ctx, A, nev, extra=6, rtol=1e-8, tol=1e-8):
+    """The same space from the device: Arpack.eigs(A, nev, :SM) as the nev + extra LARGEST eigenvalues θ of A^-1, applied
+    exactly by the block-Jacobi preconditioner with one block (`A \\ b`); λ = 1/θ. The cut follows lowest_eigvecs."""
+    Ainv = api.BlockJacobiPreconditioner(ctx, 1, sp.csc_matrix(A))
+    k = min(nev + extra, A.shape[0] - 1)
+    θ, V, info = api.eigsolve(Ainv, k, "LR", krylovdim=2 * k, tol=tol, maxiter=200)   # tol is absolute: θ = 1/λ is O(1e2 .. 1e3) here
+    Ainv.close()
+    lam = 1.0 / θ                                       # ascending, as θ is descending
+    print(f"device eigsolve(A^-1, {k}, LR): converged {info.converged}, restarts {info.numiter}, applies {info.numops}")
     m = nev
     while m < lam.size and lam[m] - lam[nev - 1] <= rtol * lam[nev - 1]:
         m += 1
@@ -94,19 +118,35 @@ def main(argv=None):
     print(f"extrema(u_with_dd - u_no_dd) = ({e.min():.3e}, {e.max():.3e})")                            # :204
 
     nev = ndom + 10                                                                                    # :206
-    Sdense = np.column_stack([S_local_mat * col for col in np.eye(n_Γ)])
-    lam, V = np.linalg.eigh((Sdense + Sdense.T) / 2)
-    for tag, ϕ in (("ld", V[:, :nev]), ("md", V[:, -nev:])):
+    if args.device_eigs:
+        t = time.time()
+        bases = []
+        for which in ("SR", "LR"):                                                                     # Example03:209, :219
+            _, ϕ, info = api.eigsolve(S_local_mat, nev, which, krylovdim=2 * nev, tol=1e-10, maxiter=500)
+            print(f"device eigsolve(S_local_mat, {nev}, {which}): converged {info.converged}, restarts {info.numiter}, applies {info.numops}")
+            bases.append(ϕ)
+        print(f"eigsolve (device) ... {time.time() - t:.2f} seconds")
+        Sdense = None
+    else:
+        Sdense = np.column_stack([S_local_mat * col for col in np.eye(n_Γ)])
+        lam, V = np.linalg.eigh((Sdense + Sdense.T) / 2)
+        bases = [V[:, :nev], V[:, -nev:]]
+    for tag, ϕ in zip(("ld", "md"), bases):
         u_Γ, it, _ = api.defpcg(S_local_mat, b_schur, np.zeros(n_Γ), np.asfortranarray(ϕ), ΠSnn_local_mat)  # :214, :224
         print(f"{tag}-def-neumann-neumann-pcg: n = {S_local_mat.N}, ndom = {ndom}, nev = {nev} ({tag}), iter = {it}")
 
     if args.lorasc:
         t = time.time()
-        E, Σ = fem.prepare_lorasc_precond(Sdense, A_ΓΓ)                                                # Example03:246-252
+        chol_A_ΓΓ = api.SparseDirectPreconditioner(ctx, A_ΓΓ)                                         # cholesky(A_ΓΓ), EPDD.jl:1525
+        if args.device_eigs:                                                                           # EPDD.jl:1546-1549
+            A_ΓΓ_dev = api.SparseMatrixCSC(ctx, A_ΓΓ)
+            E, Σ = fem.prepare_lorasc_precond(None, A_ΓΓ, eigs=lambda k: api.geneigsolve(
+                S_local_mat, A_ΓΓ_dev, chol_A_ΓΓ, k, "SR", krylovdim=2 * k, tol=1e-10, maxiter=500)[:2])
+        else:
+            E, Σ = fem.prepare_lorasc_precond(Sdense, A_ΓΓ)                                            # Example03:246-252
         setup = api.SchurSetup(ctx, P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd)                                      # cholesky(A_IId), EPDD.jl:1535-1537
         setup.keep_levels()
         setup.run()
-        chol_A_ΓΓ = api.SparseDirectPreconditioner(ctx, A_ΓΓ)                                         # cholesky(A_ΓΓ), EPDD.jl:1525
         ΠA_lorasc = api.LorascPreconditioner(ctx, A_IΓd, (sub, P.dinds), setup, chol_A_ΓΓ, E)
         print(f"prepare_lorasc_precond ... {time.time() - t:.2f} seconds, nev = {E.shape[1]}")
         A_dev = api.SparseMatrixCSC(ctx, A)
@@ -125,7 +165,7 @@ def main(argv=None):
                                                                 ΠSd, setup, coupling=args.nn_induced)
         print(f"prepare_neumann_neumann_induced_precond ... {time.time() - t:.2f} seconds")
         A_dev = api.SparseMatrixCSC(ctx, A)
-        ϕ = lowest_eigvecs(A, nev)                                                                     # Example03:311
+        ϕ = lowest_eigvecs_device(api, ctx, A, nev) if args.device_eigs else lowest_eigvecs(A, nev)    # Example03:311
         u, it, _ = api.defpcg(A_dev, b, np.zeros(b.size), ϕ, ΠA_induced_nn)                            # Example03:313
         print(f"nn-induced-defpcg: n = {A.shape[0]}, ndom = {ndom}, nev = {ϕ.shape[1]}, coupling = {args.nn_induced}, iter = {it}")
         u, it, _ = api.pcg(A_dev, b, np.zeros(b.size), ΠA_induced_nn)                                  # Example03:317

@@ -522,6 +522,42 @@ int mi_initcg(mi_op_t A, const double *b, double *x, const double *W, int64_t nv
 int mi_initpcg(mi_op_t A, mi_op_t M, const double *b, double *x, const double *W, int64_t nvec, int64_t maxit,
                double eps, double *res_norm, int64_t res_cap, int64_t *it);
 
+/* ---------------------------------------------------------------- eigensolver (thick-restart Lanczos on the device)
+ * mi_eigsolve — the reference's calls for extremal eigenpairs of its operators:
+ *     KrylovKit.eigsolve(x -> S_local_mat*x, n_Γ, nev, :SR | :LR, krylovdim=2*nev)   (Example03:209/219: the `ld` / `md`
+ *         deflation bases W of `defpcg(S, b, 0, W, ΠSnn)`)                                          -> B = Binv = NULL
+ *     KrylovKit.geneigsolve(x -> (S*x, A_ΓΓ*x), n_Γ, nvec, :SR, krylovdim=2*nvec, isposdef=true)  (EPDD.jl:1546-1549: the
+ *         LORASC pairs that mi_lorasc_set_correction takes)                -> B = A_ΓΓ (mi_csr), Binv = mi_spd_direct of it
+ *     Arpack.eigs(A | S, nev, :SM)  (Example03:260/291/313; Example07:246, 494)   -> the LR pairs of an exact inverse
+ *         operator (mi_block_jacobi_create with nb = 1 is `A \ b`), λ = 1/θ; :LM is MI_EIG_LR on the operator itself.
+ * For a symmetric operator KrylovKit's Krylov-Schur method is thick-restart Lanczos; here with full re-orthogonalisation
+ * (classical Gram-Schmidt twice) of every new vector against the whole window, the window and the re-orthogonalisation on
+ * the device, one hipGraph replay and one host synchronisation per restart (csrc/lanczos.hpp has the algorithm).
+ *   A        symmetric operator; B (SPD) and Binv (B^-1, exact) select the generalized problem A x = λ B x, Lanczos on
+ *            B^-1 A in the B inner product: the returned vectors satisfy X' B X = I (X' X = I for the standard problem).
+ *   which    MI_EIG_SR: the nev smallest eigenvalues, ascending; MI_EIG_LR: the nev largest, descending.
+ *   krylovdim  columns of the window; 0 means max(2 nev, 8); clamped to n (then one window is exact and no restart is made).
+ *   tol      ABSOLUTE bar on the residual estimate |beta Y[m, i]| of a Ritz pair, as KrylovKit's `tol`.
+ *   maxiter  restarts allowed. Running out of them is no error (KrylovKit's `info.converged` convention): MI_OK with
+ *            *nconv < nev, and vals / vecs / resid the current Ritz pairs.
+ *   v0       start vector, n entries (host or device pointer like vecs), or NULL: a fixed seeded vector.
+ *   vals (nev), resid (nev, may be NULL): HOST arrays; vecs: n x nev, column-major, host or device pointer per the context's
+ *            pointer mode. nconv: leading pairs with resid <= tol (at most nev); nrestart; napply: applies of A (each of
+ *            nconv / nrestart / napply may be NULL).
+ * A basis that becomes invariant (beta <= 64 eps max|T|) ends the call with the exact pairs of that subspace when it holds
+ * nev columns, and is continued with a fresh orthogonalised vector otherwise.
+ * MI_ERR_BAD_ARG with a message: nev < 1 or nev > n; which unknown; krylovdim negative, or below nev + 1 without reaching n;
+ * a window above 1024 columns; tol or maxiter negative; exactly one of B / Binv; operators of different size or context;
+ * a context that is one rank of several (sharded eigensolves are not provided).
+ * MI_ERR_SINGULAR: a start vector that is zero or not finite, or a beta / T entry that is not finite (NaN or Inf from an
+ * operator). Nothing is carried from one call to the next: all buffers of a call are its own. */
+#define MI_EIG_SR 0
+#define MI_EIG_LR 1
+int mi_eigsolve(mi_op_t A, mi_op_t B /*NULL: standard*/, mi_op_t Binv /*NULL iff B is*/,
+                int64_t nev, int which, int64_t krylovdim /*0: max(2*nev, 8)*/, double tol, int64_t maxiter,
+                const double *v0 /*NULL: seeded host vector*/, double *vals /*nev*/, double *vecs /*n x nev, col-major*/,
+                double *resid /*nev, may be NULL*/, int64_t *nconv, int64_t *nrestart, int64_t *napply);
+
 /* ---------------------------------------------------------------- timing on the context's stream */
 int mi_event_create(mi_event_t *ev);
 int mi_event_record(mi_ctx_t ctx, mi_event_t ev);

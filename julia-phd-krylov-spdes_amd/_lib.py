@@ -18,6 +18,7 @@ MI_ERR_BAD_ARG, MI_ERR_HIP, MI_ERR_SINGULAR, MI_ERR_RES_CAPACITY = -1, -2, -3, -
 MI_ERR_COMM, MI_ERR_NO_DEVICE, MI_ERR_CALLBACK, MI_ERR_BOUNDS = -5, -6, -7, -8
 MI_PTR_HOST, MI_PTR_DEVICE = 0, 1
 MI_NNI_AS_WRITTEN, MI_NNI_ASSEMBLED = 0, 1
+MI_EIG_SR, MI_EIG_LR = 0, 1
 MI_COMM_ID_BYTES = 128
 MI_PEER_HANDLE_BYTES = 64
 
@@ -120,6 +121,7 @@ SIGNATURES = {
     "mi_eigdefpcg": [vp, vp, vp, vp, vp, i64, i64, i64, C.c_double, f64p, i64, i64p, vp],
     "mi_initcg": [vp, vp, vp, vp, i64, i64, C.c_double, f64p, i64, i64p],
     "mi_initpcg": [vp, vp, vp, vp, vp, i64, i64, C.c_double, f64p, i64, i64p],
+    "mi_eigsolve": [vp, vp, vp, i64, C.c_int, i64, C.c_double, i64, vp, f64p, vp, f64p, i64p, i64p, i64p],
     "mi_event_create": [C.POINTER(vp)],
     "mi_event_record": [vp, vp],
     "mi_event_elapsed_ms": [vp, vp, f64p],

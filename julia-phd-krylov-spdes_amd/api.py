@@ -1263,4 +1263,59 @@ def initpcg(A: Operator, b, x, M: Operator, W, maxit: int = 0, eps: float = EPS)
     return _solve("initpcg", A, M, b, x, W, maxit, eps)
 
 
+
+# ------------------------------------------------------------------ eigensolver
+class ConvergenceInfo:
+    """KrylovKit's `ConvergenceInfo` by its field names: `converged` (leading pairs with normres <= tol), `normres` (the
+    residual estimates of the returned pairs), `numiter` (restarts), `numops` (applies of A)."""
+
+    def __init__(self, converged: int, normres, numiter: int, numops: int):
+        self.converged, self.normres, self.numiter, self.numops = converged, normres, numiter, numops
+
+    def __repr__(self):
+        return f"ConvergenceInfo(converged={self.converged}, numiter={self.numiter}, numops={self.numops}, normres={self.normres})"
+
+
+_WHICH = {"SR": _lib.MI_EIG_SR, "LR": _lib.MI_EIG_LR}
+
+
+def _eigsolve(A: Operator, B: Optional[Operator], Binv: Optional[Operator], nev: int, which, krylovdim: int, tol: float,
+              maxiter: int, v0):
+    ctx, n = A.ctx, A.n
+    if which not in _WHICH:
+        raise ValueError(f"which = {which!r}: 'SR' or 'LR' expected")
+    nev = int(nev)
+    ctx._mode_for(v0)
+    k0, p0 = ctx._ptr(v0, n)
+    if _is_torch(v0):
+        import torch
+        vecs = torch.empty((max(nev, 0), n), dtype=torch.float64, device=v0.device).T
+        pv = vp(vecs.data_ptr())
+    else:
+        vecs = np.empty((n, max(nev, 0)), order="F")
+        pv = vp(vecs.ctypes.data)
+    vals, res = np.empty(max(nev, 1)), np.empty(max(nev, 1))
+    nconv, nrestart, napply = i64(), i64(), i64()
+    ctx._order((k0, vecs), after=False)
+    check(ctx._L.mi_eigsolve(A._h, B._h if B is not None else None, Binv._h if Binv is not None else None, i64(nev),
+                             C.c_int(_WHICH[which]), i64(krylovdim), C.c_double(tol), i64(maxiter), p0,
+                             vals.ctypes.data_as(f64p), pv, res.ctypes.data_as(f64p), C.byref(nconv), C.byref(nrestart),
+                             C.byref(napply)))
+    ctx._order((k0, vecs), after=True)
+    return vals[:nev], vecs, ConvergenceInfo(int(nconv.value), res[:nev], int(nrestart.value), int(napply.value))
+
+
+def eigsolve(A: Operator, nev: int, which: str = "SR", krylovdim: int = 0, tol: float = 1e-12, maxiter: int = 100, v0=None):
+    """KrylovKit.eigsolve(x -> A*x, n, nev, :SR | :LR, krylovdim=...) (Example03:209/219) -> (vals, vecs, info): thick-restart
+    Lanczos on the device (`mi_eigsolve`). `vecs` is n x nev with orthonormal columns; `tol` is absolute."""
+    return _eigsolve(A, None, None, nev, which, krylovdim, tol, maxiter, v0)
+
+
+def geneigsolve(A: Operator, B: Operator, Binv: Operator, nev: int, which: str = "SR", krylovdim: int = 0, tol: float = 1e-12,
+                maxiter: int = 100, v0=None):
+    """KrylovKit.geneigsolve(x -> (A*x, B*x), n, nev, :SR, krylovdim=..., isposdef=true) (EPDD.jl:1546-1549) -> (vals, vecs, info)
+    with vecs' B vecs = I. `Binv` applies the exact inverse of the SPD `B` (e.g. SparseDirectPreconditioner(ctx, A_ΓΓ))."""
+    return _eigsolve(A, B, Binv, nev, which, krylovdim, tol, maxiter, v0)
+
+
 GlobalSchur.use_level_solver = _use_level_solver

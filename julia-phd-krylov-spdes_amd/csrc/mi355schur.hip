@@ -5,6 +5,7 @@
 #include <tuple>
 
 #include "eig_solvers.hpp"
+#include "lanczos.hpp"
 #include "setup_gj.hpp"
 #include "spd_direct.hpp"
 #include "lorasc.hpp"
@@ -198,7 +199,7 @@ using namespace mi;
 
 extern "C" {
 
-int mi_version(void) { return 200; }  // 0.2.0
+int mi_version(void) { return 300; }  // 0.3.0
 const char *mi_last_error(void) { return last_error().c_str(); }
 
 int mi_device_count(int *count) {
@@ -942,6 +943,52 @@ int mi_initcg(mi_op_t A, const double *b, double *x, const double *W, int64_t nv
 int mi_initpcg(mi_op_t A, mi_op_t M, const double *b, double *x, const double *W, int64_t nvec, int64_t maxit, double eps,
                double *res_norm, int64_t res_cap, int64_t *it) {
   return run_init_solver(A, M, b, x, W, nvec, maxit, eps, res_norm, res_cap, it, true);
+}
+
+// ---------------------------------------------------------------- eigensolver (lanczos.hpp)
+int mi_eigsolve(mi_op_t A, mi_op_t B, mi_op_t Binv, int64_t nev, int which, int64_t krylovdim, double tol, int64_t maxiter,
+                const double *v0, double *vals, double *vecs, double *resid, int64_t *nconv, int64_t *nrestart, int64_t *napply) {
+  if (!A || !A->impl || !vals || !vecs) return fail(MI_ERR_BAD_ARG, "mi_eigsolve: A, vals or vecs is NULL");
+  if ((B == nullptr) != (Binv == nullptr))
+    return fail(MI_ERR_BAD_ARG, "mi_eigsolve: B and Binv go together (both NULL: the standard problem)");
+  if (B && (!B->impl || !Binv->impl)) return fail(MI_ERR_BAD_ARG, "mi_eigsolve: B or Binv is an empty handle");
+  Operator *a = A->impl.get(), *b = B ? B->impl.get() : nullptr, *bi = B ? Binv->impl.get() : nullptr;
+  const int64_t n = a->n;
+  if (b && (b->n != n || bi->n != n || b->ctx != a->ctx || bi->ctx != a->ctx))
+    return fail(MI_ERR_BAD_ARG, "mi_eigsolve: A (%lld), B (%lld) and Binv (%lld) differ in size or context", (long long)n,
+                (long long)b->n, (long long)bi->n);
+  if (nev < 1 || nev > n) return fail(MI_ERR_BAD_ARG, "mi_eigsolve: nev = %lld outside [1, n = %lld]", (long long)nev, (long long)n);
+  if (which != MI_EIG_SR && which != MI_EIG_LR) return fail(MI_ERR_BAD_ARG, "mi_eigsolve: which = %d is neither MI_EIG_SR nor MI_EIG_LR", which);
+  if (krylovdim < 0 || (krylovdim != 0 && krylovdim < nev + 1 && krylovdim < n))
+    return fail(MI_ERR_BAD_ARG, "mi_eigsolve: krylovdim = %lld; 0 or at least nev + 1 = %lld (or n = %lld) expected", (long long)krylovdim,
+                (long long)(nev + 1), (long long)n);
+  if (!(tol >= 0.0) || maxiter < 0) return fail(MI_ERR_BAD_ARG, "mi_eigsolve: tol = %g, maxiter = %lld: both must be non-negative", tol, (long long)maxiter);
+  const int64_t m = std::min<int64_t>(krylovdim ? krylovdim : std::max<int64_t>(2 * nev, 8), n);
+  if (m > 1024) return fail(MI_ERR_BAD_ARG, "mi_eigsolve: a window of %lld columns; at most 1024 are supported", (long long)m);
+  mi_ctx_s *c = a->ctx;
+  if (c->has_comm())
+    return fail(MI_ERR_BAD_ARG, "mi_eigsolve: the context is one rank of several; sharded eigensolves are not provided");
+  return guarded([&]() -> int {
+    c->use();
+    In vi(c, v0, v0 ? (size_t)n : 0, c->scratch_a);
+    DevBuf<double> xstage;
+    InOut xo(c, vecs, (size_t)n * (size_t)nev, xstage, false);
+    LanczosResult r;
+    int rc;
+    {
+      Lanczos lz(c, a, b, bi, (int)nev, which, (int)m);
+      rc = lz.solve(v0 ? vi.dev : nullptr, tol, maxiter, xo.dev, r);
+      MI_HIP(hipStreamSynchronize(c->stream));   // the panels go back to the pool behind this brace
+    }
+    if (rc != MI_OK) return rc;
+    xo.finish();
+    std::copy(r.vals.begin(), r.vals.end(), vals);
+    if (resid) std::copy(r.resid.begin(), r.resid.end(), resid);
+    if (nconv) *nconv = r.nconv;
+    if (nrestart) *nrestart = r.nrestart;
+    if (napply) *napply = r.napply;
+    return MI_OK;
+  });
 }
 
 // ---------------------------------------------------------------- on-device block assembly

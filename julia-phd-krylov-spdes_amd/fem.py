@@ -849,7 +849,7 @@ def prepare_neumann_neumann_induced_precond(A_IIdd, A_IΓdd, A_ΓΓdd):
     return prepare_neumann_neumann_schur_precond(assemble_local_schurs(A_IIdd, A_IΓdd, A_ΓΓdd))
 
 
-def prepare_lorasc_precond(S, A_ΓΓ, nvec: int = 25, ε: float = 0.01):
+def prepare_lorasc_precond(S, A_ΓΓ, nvec: int = 25, ε: float = 0.01, eigs=None):
     """The low-rank correction of `prepare_lorasc_precond`, its `low_rank_correction = :exact` branch (EPDD.jl:1541-1617),
     on the host: the `nvec` least dominant generalized eigenpairs S e = σ A_ΓΓ e by a dense `scipy.linalg.eigh(S, A_ΓΓ)`
     in place of `KrylovKit.geneigsolve(..., nvec, :SR, isposdef=true)` (:1546-1549) — both leave `E' A_ΓΓ E = I`.
@@ -857,7 +857,21 @@ def prepare_lorasc_precond(S, A_ΓΓ, nvec: int = 25, ε: float = 0.01):
 
     The selection (:1587-1610): pairs in ascending σ; the leading ones with σ < ε are counted as nev and their Σ[k]
     becomes (ε - σ)/σ, the count stops at the first σ >= ε; nev == 0 -> nev = nvec (with untransformed Σ), as the
-    reference falls back; nev == nvec is kept (the reference only warns). ε <= 0 gives no correction (:1612-1615)."""
+    reference falls back; nev == nvec is kept (the reference only warns). ε <= 0 gives no correction (:1612-1615).
+
+    `eigs`: an optional callable nvec -> (Σ, E) that supplies the pairs instead of the dense `eigh` (the device form:
+    `lambda k: api.geneigsolve(S_op, A_ΓΓ_op, chol_A_ΓΓ, k, "SR", krylovdim=2 * k)[:2]`); `S` is then not touched and may
+    be None. The selection above is applied to what it returns."""
+    n = A_ΓΓ.shape[0]
+    if eigs is not None:
+        if ε <= 0:
+            return np.empty((n, 0)), np.empty(0)
+        nvec = min(int(nvec), n)
+        Σ, E = eigs(nvec)
+        Σ, E = np.array(Σ, dtype=np.float64), np.asarray(E, dtype=np.float64)
+        if Σ.shape != (nvec,) or E.shape != (n, nvec):
+            raise ValueError(f"eigs({nvec}) returned shapes {Σ.shape}, {E.shape}; ({nvec},) and ({n}, {nvec}) expected")
+        return _lorasc_select(Σ, E, nvec, ε)
     A = A_ΓΓ.toarray() if sp.issparse(A_ΓΓ) else np.asarray(A_ΓΓ, dtype=np.float64)
     n = A.shape[0]
     if ε <= 0:
@@ -868,6 +882,11 @@ def prepare_lorasc_precond(S, A_ΓΓ, nvec: int = 25, ε: float = 0.01):
     nvec = min(int(nvec), n)
     import scipy.linalg as sla
     Σ, E = sla.eigh((S + S.T) / 2, (A + A.T) / 2, subset_by_index=[0, nvec - 1])
+    return _lorasc_select(Σ, E, nvec, ε)
+
+
+def _lorasc_select(Σ, E, nvec: int, ε: float):
+    """EPDD.jl:1587-1610 on the nvec pairs (see prepare_lorasc_precond)."""
     order = np.argsort(Σ, kind="stable")
     Σ, E = Σ[order].copy(), E[:, order]
     nev = 0

@@ -35,7 +35,8 @@ export MiContext, MiOperator, MiPrecond,
        LocalSchurs, LocalSchur, MatrixFreeLocalSchurs, GlobalSchur,
        AssemblyPlan, assemble!, set_values!, SchurSetup, set_blocks!, interior_precond!, interior_iterations,
        keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!,
-       SparseDirectPreconditioner, spd_direct_stats, bj_set_values!, MiLorasc, set_correction!, MiNNInduced, set_coupling!
+       SparseDirectPreconditioner, spd_direct_stats, bj_set_values!, MiLorasc, set_correction!, MiNNInduced, set_coupling!,
+       mi_eigsolve, mi_geneigsolve
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -481,6 +482,34 @@ function initsolve(A::MiOperator, M, b::Vector{Float64}, x::Vector{Float64}, W::
 end
 initcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, W::Matrix{Float64}; maxit=0) = initsolve(A, nothing, b, x, W, maxit)
 initpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiOperator, W::Matrix{Float64}; maxit=0) = initsolve(A, M, b, x, W, maxit)
+
+# ---------------------------------------------------------------- eigensolver (thick-restart Lanczos on the device)
+# KrylovKit.eigsolve(x -> S_local_mat*x, n_Γ, nev, :SR | :LR, krylovdim=2*nev) (Example03:209/219) and
+# KrylovKit.geneigsolve(x -> (S*x, A_ΓΓ*x), n_Γ, nvec, :SR, krylovdim=2*nvec, isposdef=true) (EPDD.jl:1546-1549) in KrylovKit's
+# return shape (vals, [vec₁, …], info); info has KrylovKit.ConvergenceInfo's field names. `tol` is absolute, as KrylovKit's.
+# Arpack.eigs(A, nev, :SM) (Example03:311): mi_eigsolve(BJPreconditioner(ctx, 1, A), nev, :LR), λ = 1 ./ vals.
+function lanczos_call(A::MiOperator, B, Binv, nev::Int, which::Symbol, krylovdim::Int, tol::Float64, maxiter::Int, v0)
+  which in (:SR, :LR) || error("which = $which: :SR or :LR expected")
+  n = A.n
+  vals = Vector{Float64}(undef, nev); resid = Vector{Float64}(undef, nev)
+  X = Matrix{Float64}(undef, n, nev)
+  nconv = Ref{Int64}(0); nrestart = Ref{Int64}(0); napply = Ref{Int64}(0)
+  hB = B === nothing ? C_NULL : B.h
+  hBinv = Binv === nothing ? C_NULL : Binv.h
+  start = v0 === nothing ? Ptr{Float64}(C_NULL) : pointer(v0)
+  GC.@preserve v0 check(ccall((:mi_eigsolve, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Int64, Float64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+               Ptr{Float64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+              A.h, hB, hBinv, Int64(nev), Cint(which == :SR ? 0 : 1), Int64(krylovdim), tol, Int64(maxiter), start, vals, X,
+              resid, nconv, nrestart, napply))
+  info = (converged = Int(nconv[]), normres = resid, numiter = Int(nrestart[]), numops = Int(napply[]))
+  return vals, [X[:, k] for k in 1:nev], info
+end
+mi_eigsolve(A::MiOperator, nev::Int, which::Symbol=:SR; krylovdim::Int=0, tol::Float64=1e-12, maxiter::Int=100, v0=nothing) =
+  lanczos_call(A, nothing, nothing, nev, which, krylovdim, tol, maxiter, v0)
+mi_geneigsolve(A::MiOperator, B::MiOperator, Binv::MiOperator, nev::Int, which::Symbol=:SR; krylovdim::Int=0, tol::Float64=1e-12,
+               maxiter::Int=100, v0=nothing) =
+  lanczos_call(A, B, Binv, nev, which, krylovdim, tol, maxiter, v0)
 
 # ---------------------------------------------------------------- sparse direct `M \ r` (Example07:412/416)
 """`SparseDirectPreconditioner(ctx, A)`: `M \\ r` for a sparse SPD `A::SparseMatrixCSC` — RecyclingKrylovSolvers' pcg applies
