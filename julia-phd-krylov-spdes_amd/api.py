@@ -506,15 +506,8 @@ class LorascPreconditioner(Operator):
 
     def __init__(self, ctx: Context, A_IΓd, sub_or_maps, setup: "SchurSetup", A_ΓΓ_solver: "SparseDirectPreconditioner",
                  E=None, coef=None, index_base: int = 0):
-        pos_I, pos_Γ = _lorasc_maps(sub_or_maps)
-        ndom = len(A_IΓd)
-        if len(pos_I) != ndom:
-            raise ValueError("one interior map per subdomain expected")
-        n_i = _i64([len(p) for p in pos_I])
-        pI = [_i64(p) + index_base for p in pos_I]
-        pΓ = _i64(pos_Γ) + index_base
-        n_Γ = int(pΓ.size)
-        igp, igi, igv = _csc_parts(A_IΓd, 0, ndom, index_base)
+        ndom, n_Γ, n_i, pI, pΓ, igp, igi, igv = _split_parts(
+            A_IΓd, sub_or_maps, index_base, (), "one interior map per subdomain expected")
         nev, Ea, ca = _lorasc_correction(n_Γ, E, coef)
         h = vp()
         check(ctx._L.mi_lorasc_create(
@@ -529,10 +522,7 @@ class LorascPreconditioner(Operator):
     def set_values(self, ig_val) -> None:
         """The concatenated CSC `nzval` of all A_IΓd of a new realization: numpy array or torch CUDA tensor
         (`mi_lorasc_set_values`). The interior and A_ΓΓ factors move with `setup.run(...)` / `A_ΓΓ_solver.set_values(...)`."""
-        self.ctx._mode_for(ig_val)
-        k, p = self.ctx._ptr(ig_val, self.nnz)
-        self.ctx._order((k,), after=False)
-        check(self.ctx._L.mi_lorasc_set_values(self._h, p))
+        _split_set_values(self, self.ctx._L.mi_lorasc_set_values, ig_val)
 
     def set_correction(self, E=None, coef=None) -> None:
         """A new low-rank correction (`mi_lorasc_set_correction`); `E=None` removes it."""
@@ -555,6 +545,26 @@ def _lorasc_maps(sub_or_maps):
         g2l = b.not_dirichlet_g2l
         return [g2l[nodes] for nodes in a.node_Id], g2l[a.node_Γ]
     return list(a), b
+
+
+def _split_parts(A_IΓ, sub_or_maps, index_base: int, per_subdomain, complaint: str):
+    """What both preconditioners on the interior/Γ split hand to the library: ndom, n_Γ, n_i, the two maps and the CSC
+    arrays of the A_IΓ blocks in `index_base`; `per_subdomain`: further lists that must have one entry per subdomain."""
+    pos_I, pos_Γ = _lorasc_maps(sub_or_maps)
+    ndom = len(A_IΓ)
+    if any(len(a) != ndom for a in (pos_I, *per_subdomain)):
+        raise ValueError(complaint)
+    n_i = _i64([len(p) for p in pos_I])
+    pI = [_i64(p) + index_base for p in pos_I]
+    pΓ = _i64(pos_Γ) + index_base
+    return (ndom, int(pΓ.size), n_i, pI, pΓ) + _csc_parts(A_IΓ, 0, ndom, index_base)
+
+
+def _split_set_values(op, entry, ig_val) -> None:
+    op.ctx._mode_for(ig_val)
+    k, p = op.ctx._ptr(ig_val, op.nnz)
+    op.ctx._order((k,), after=False)
+    check(entry(op._h, p))
 
 
 def _lorasc_correction(n_Γ: int, E, coef):
@@ -680,14 +690,8 @@ class NeumannNeumannInducedPreconditioner(Operator):
             raise ValueError(f"storage must be 'f64', 'f32', numpy.float64 or numpy.float32, not {storage!r}")
         if not isinstance(cpl, (int, np.integer)):
             raise ValueError(f"coupling must be 'reference' or 'assembled', not {coupling!r}")
-        pos_I, pos_Γ = _lorasc_maps(sub_or_maps)
-        ndom = len(A_IΓdd)
-        if len(pos_I) != ndom or len(gather_idx) != ndom or len(ΠSd) != ndom:
-            raise ValueError("one interior map, one gather list and one ΠS_d block per subdomain expected")
-        n_i = _i64([len(p) for p in pos_I])
-        pI = [_i64(p) + index_base for p in pos_I]
-        pΓ = _i64(pos_Γ) + index_base
-        n_Γ = int(pΓ.size)
+        ndom, n_Γ, n_i, pI, pΓ, igp, igi, igv = _split_parts(
+            A_IΓdd, sub_or_maps, index_base, (gather_idx, ΠSd), "one interior map, one gather list and one ΠS_d block per subdomain expected")
         g = [_i64(a) + index_base for a in gather_idx]
         nd = _i64([a.size for a in g])
         cnt = _i64(node_Γ_cnt)
@@ -695,7 +699,6 @@ class NeumannNeumannInducedPreconditioner(Operator):
         for d in range(ndom):
             if blocks[d].shape != (nd[d], nd[d]):
                 raise ValueError(f"ΠSd[{d}] has shape {blocks[d].shape}, expected {(nd[d], nd[d])}")
-        igp, igi, igv = _csc_parts(A_IΓdd, 0, ndom, index_base)
         h = vp()
         check(ctx._L.mi_nn_induced_create(
             ctx._h, i64(ndom), i64(int(n_i.sum()) + n_Γ), i64(n_Γ), nd.ctypes.data_as(i64p), n_i.ctypes.data_as(i64p),
@@ -711,10 +714,7 @@ class NeumannNeumannInducedPreconditioner(Operator):
     def set_values(self, ig_val) -> None:
         """The concatenated CSC `nzval` of all A_IΓdd of a new realization: numpy array or torch CUDA tensor
         (`mi_nn_induced_set_values`). The interior factors move with `setup.run(...)`."""
-        self.ctx._mode_for(ig_val)
-        k, p = self.ctx._ptr(ig_val, self.nnz)
-        self.ctx._order((k,), after=False)
-        check(self.ctx._L.mi_nn_induced_set_values(self._h, p))
+        _split_set_values(self, self.ctx._L.mi_nn_induced_set_values, ig_val)
 
     def set_blocks(self, ΠSd) -> None:
         """New ΠS_d: one concatenated column-major buffer, numpy array or torch CUDA tensor (`mi_nn_induced_set_blocks`)."""

@@ -580,6 +580,18 @@ int mi_block_jacobi_stats(mi_op_t op, int64_t *n_g, int64_t *n_levels, int64_t *
   return MI_OK;
 }
 
+// new values of the stacked A_IΓ blocks of either operator on the interior/Γ split (host or device pointer)
+static int split_set_values(SplitOp *m, const double *ig_val) {
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    DevBuf<double> st;
+    In vi(c, ig_val, (size_t)m->nnz, st);
+    m->set_values(vi.dev);
+    MI_HIP(hipStreamSynchronize(c->stream));   // the staging buffer goes out of scope
+    return MI_OK;
+  });
+}
 static LorascOp *as_lorasc(mi_op_t op) { return op && op->impl ? dynamic_cast<LorascOp *>(op->impl.get()) : nullptr; }
 int mi_lorasc_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma, const int64_t *n_i, const int64_t *const *pos_I,
                      const int64_t *pos_gamma, const int64_t *const *ig_colptr, const int64_t *const *ig_rowval,
@@ -591,15 +603,7 @@ int mi_lorasc_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma, con
 int mi_lorasc_set_values(mi_op_t op, const double *ig_val) {
   LorascOp *l = as_lorasc(op);
   if (!l || !ig_val) return fail(MI_ERR_BAD_ARG, "mi_lorasc_set_values: not a LORASC preconditioner, or NULL ig_val");
-  mi_ctx_s *c = l->ctx;
-  return guarded([&]() -> int {
-    c->use();
-    DevBuf<double> st;
-    In vi(c, ig_val, (size_t)l->nnz, st);
-    l->set_values(vi.dev);
-    MI_HIP(hipStreamSynchronize(c->stream));   // the staging buffer goes out of scope
-    return MI_OK;
-  });
+  return split_set_values(l, ig_val);
 }
 int mi_lorasc_set_correction(mi_op_t op, int64_t nev, const double *E, const double *coef) {
   LorascOp *l = as_lorasc(op);
@@ -628,15 +632,7 @@ int mi_nn_induced_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma,
 int mi_nn_induced_set_values(mi_op_t op, const double *ig_val) {
   NnInducedOp *m = as_nn_induced(op);
   if (!m || !ig_val) return fail(MI_ERR_BAD_ARG, "mi_nn_induced_set_values: not a Neumann-Neumann induced preconditioner, or NULL ig_val");
-  mi_ctx_s *c = m->ctx;
-  return guarded([&]() -> int {
-    c->use();
-    DevBuf<double> st;
-    In vi(c, ig_val, (size_t)m->nnz, st);
-    m->set_values(vi.dev);
-    MI_HIP(hipStreamSynchronize(c->stream));   // the staging buffer goes out of scope
-    return MI_OK;
-  });
+  return split_set_values(m, ig_val);
 }
 int mi_nn_induced_set_coupling(mi_op_t op, int coupling) {
   NnInducedOp *m = as_nn_induced(op);

@@ -1,5 +1,5 @@
 """Synthetic partitioned full systems for the edge suite of the full-system preconditioners (csrc/nn_induced.hpp:
-k_gemv_nni, k_nni_assemble, k_nni_coupling; csrc/lorasc.hpp: k_lo_zgamma, k_lo_correct).
+k_gemv_nni, k_nni_assemble; csrc/full_split.hpp: k_lo_zgamma, k_split_coupling; csrc/lorasc.hpp: k_lo_correct).
 
 Not a conftest: tests/test_full_synth_cpu.py and tests/test_gpu_full_synth_edges.py import it. Everything here runs on the host.
 

@@ -64,7 +64,7 @@ def summarize(path, applies):
                          within_spread=abs(nni["median_us"] / nn["median_us"] - 1.0) <= max(nni["spread"], nn["spread"]))
     per_launch = {}
     for k, v in rows.items():
-        if any(t in k for t in ("k_lo_gather", "k_lo_zgamma", "k_gemv_nni", "k_nni_", "k_lv_")):
+        if any(t in k for t in ("k_lo_gather", "k_lo_zgamma", "k_gemv_nni", "k_nni_", "k_split_", "k_lv_")):
             d = [us for _, us in v]
             per_launch[k] = dict(calls=len(d), calls_per_apply=round(len(d) / (2 * (applies + WARMUP)), 2),
                                  us_avg=round(sum(d) / len(d), 2), us_min=round(min(d), 2), us_max=round(max(d), 2))
