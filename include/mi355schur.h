@@ -190,6 +190,27 @@ int mi_block_jacobi_create(mi_ctx_t ctx, int64_t n, const int64_t *colptr, const
 int mi_block_jacobi_set_values(mi_op_t op, const double *nzval);
 int mi_block_jacobi_stats(mi_op_t op, int64_t *n_g, int64_t *n_levels, int64_t *max_level, int64_t *kept_bytes);
 
+/* mi_amg_create — the reference's `Preconditioners.AMGPreconditioner{SmoothedAggregation}(A)`, the M of `pcg(A, b, 0, Π_amg)`
+ * in Example01:49-61 (and Examples 06, 09, 10, 12-20): one V(1,1) cycle of smoothed-aggregation AMG per `M \ r` (amg.hpp),
+ *     coarsest: x = A_c^-1 b;  else  x = (ω/d) b;  r = b - A_l x;  e = cycle(l + 1, P_l' r);  x += P_l e;  x += (ω/d) (b - A_l x)
+ * The smoother is Jacobi damped by ω_l where the reference sweeps symmetric Gauss-Seidel (sequential). The
+ * hierarchy comes from the host (fem.prepare_amg_precond, or any other set-up); all arrays are HOST arrays:
+ *   nlevels, n_l[nlevels]          rows of every level, strictly decreasing; the last one at most 4096
+ *   a_rowptr / a_colidx / a_val    [nlevels] pointers: CSR of the symmetric A_l (`index_base`-based)
+ *   p_rowptr / p_colidx / p_val    [nlevels - 1] pointers: CSR of P_l, n_l x n_{l+1} (may be NULL when nlevels == 1)
+ *   omega_over_d                   ω_l / diag(A_l) of the levels l < nlevels - 1, back to back (Σ n_l doubles)
+ *   coarse_inv                     the symmetric inverse of the coarsest level, n_c x n_c, column-major
+ * R_l = P_l' is built here in CSR; one apply is 4 (nlevels - 1) + 1 launches with fixed summation orders (bitwise
+ * reproducible), no atomics and no host synchronisation, captured into the solvers' graphs. nlevels == 1 is `A \ b` by the
+ * dense inverse. MI_ERR_BAD_ARG with a mi_last_error() text: nlevels < 1, level sizes that do not chain, a P_l that is not
+ * n_l x n_{l+1}, a value that is not finite, a coarsest level above 4096 rows, a context that is one rank of several.
+ * mi_amg_stats — levels, rows of the coarsest level, Σ_l nnz(A_l), and bytes_kept = Σ_{l < nlevels-1} (12 nnz(A_l) +
+ * 24 nnz(P_l) + 8 n_l) + 8 n_c² (values and column indices of the smoothed A_l, of P_l and R_l; ω/d; the inverse). Any pointer may be NULL. */
+int mi_amg_create(mi_ctx_t ctx, int64_t nlevels, const int64_t *n_l, const int64_t *const *a_rowptr, const int64_t *const *a_colidx,
+                  const double *const *a_val, const int64_t *const *p_rowptr, const int64_t *const *p_colidx, const double *const *p_val,
+                  const double *omega_over_d, const double *coarse_inv, int index_base, mi_op_t *op);
+int mi_amg_stats(mi_op_t op, int64_t *n_levels, int64_t *coarse_n, int64_t *operator_nnz, int64_t *bytes_kept);
+
 /* mi_schur_assembled_create — `apply_local_schurs(Sd, ind_Γd_Γ2l, node_Γ_cnt, x)`, EPDD.jl:761-785:
  * Sx = Σ_d R_d' S_d R_d x with dense local Schur complements.
  *   Sd[d]          n_gamma_d[d]^2 doubles, column-major (Julia `Array(Sd[d])`)

@@ -386,7 +386,7 @@ def IdentityPreconditioner(ctx: Context, n: int) -> Operator:
 
 
 def JacobiPreconditioner(ctx: Context, diag) -> Operator:
-    """z = r ./ diag(A) — stands in for Example01's AMG preconditioner (out of scope)."""
+    """z = r ./ diag(A) — config 2's stand-in for Example01's AMG preconditioner (`AMGPreconditioner` is the V-cycle itself)."""
     dinv = _f64(1.0 / np.asarray(diag, dtype=np.float64))
     h = vp()
     check(ctx._L.mi_diag_create(ctx._h, i64(dinv.size), dinv.ctypes.data_as(f64p), C.byref(h)))
@@ -489,6 +489,54 @@ class BlockJacobiPreconditioner(Operator):
         check(self.ctx._L.mi_block_jacobi_stats(self._h, a.ctypes.data_as(i64p), b.ctypes.data_as(i64p), c.ctypes.data_as(i64p),
                                                 C.byref(kb)))
         return dict(n_g=a, n_levels=b, max_level=c, kept_bytes=int(kb.value))
+
+
+class AMGPreconditioner(Operator):
+    """The reference's `AMGPreconditioner{SmoothedAggregation}(A)` (Preconditioners.jl), the `Π_amg` of
+    `pcg(A, b, zeros, Π_amg)` in Example01:49-61, on the device (`mi_amg_create`): `M \\ r` is one V(1,1) cycle of
+    smoothed-aggregation AMG. `A_or_hierarchy`: a scipy sparse matrix — the set-up then runs here, on the host, with
+    `fem.prepare_amg_precond(A, **kw)` (`max_levels`, `max_coarse`) — or a `fem.AmgHierarchy` built before. Usable as `M`
+    of pcg / defpcg / eigpcg / eigdefpcg / initpcg and through `M * r`. Deviation from the reference: damped Jacobi where it
+    smooths with symmetric Gauss-Seidel. A new matrix needs a new object (no set_values)."""
+
+    def __init__(self, ctx: Context, A_or_hierarchy, index_base: int = 0, **kw):
+        H = A_or_hierarchy
+        if sp.issparse(H) or isinstance(H, np.ndarray):
+            from . import fem
+            H = fem.prepare_amg_precond(sp.csr_matrix(H), **kw)
+        elif kw:
+            raise TypeError(f"set-up options {sorted(kw)} with a hierarchy that is already built")
+        L = H.nlevels
+        n_l = _i64(H.sizes)
+
+        def parts(mats):
+            keep = []
+            for M in mats:
+                M = sp.csr_matrix(M)
+                M.sort_indices()
+                keep.append((_i64(M.indptr) + index_base, _i64(M.indices) + index_base, _f64(M.data)))
+            return keep, _ptrs([k[0] for k in keep], i64p), _ptrs([k[1] for k in keep], i64p), _ptrs([k[2] for k in keep], f64p)
+
+        ka, ap, ai, av = parts(H.A)
+        kp, pp, pi, pv = parts(H.P)
+        wd = _f64(np.concatenate([np.asarray(w, dtype=np.float64).ravel() for w in H.omega_over_d] + [np.zeros(1)]))
+        inv = np.asfortranarray(H.coarse_inv, dtype=np.float64)
+        nc = H.A[-1].shape[0]
+        if inv.shape != (nc, nc) or len(H.A) != L or len(H.P) != L - 1 or len(H.omega_over_d) != L - 1:
+            raise ValueError(f"coarse_inv is {inv.shape} for a coarsest level of {nc} rows, or the level lists do not fit {L} levels")
+        if any(np.size(w) != a.shape[0] for w, a in zip(H.omega_over_d, H.A)):
+            raise ValueError("omega_over_d: one entry per row of its level expected")
+        h = vp()
+        check(ctx._L.mi_amg_create(ctx._h, i64(L), n_l.ctypes.data_as(i64p), ap, ai, av, pp, pi, pv, wd.ctypes.data_as(f64p),
+                                   inv.ctypes.data_as(f64p), C.c_int(index_base), C.byref(h)))
+        super().__init__(ctx, h)
+        self.hierarchy = H
+
+    def stats(self):
+        """dict(n_levels, coarse_n, operator_nnz, bytes_kept) (`mi_amg_stats`)"""
+        a, b, c, d = i64(), i64(), i64(), i64()
+        check(self.ctx._L.mi_amg_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(n_levels=int(a.value), coarse_n=int(b.value), operator_nnz=int(c.value), bytes_kept=int(d.value))
 
 
 class LorascPreconditioner(Operator):
@@ -1138,6 +1186,11 @@ def apply_lorasc(Πlorasc: LorascPreconditioner, x):
 
 def apply_neumann_neumann_induced(Πnn: NeumannNeumannInducedPreconditioner, r):
     return Πnn.apply(r)
+
+
+def apply_amg(Π_amg: AMGPreconditioner, r):
+    """`Π_amg \\ r`: one V-cycle"""
+    return Π_amg.apply(r)
 
 
 # ------------------------------------------------------------------ solvers

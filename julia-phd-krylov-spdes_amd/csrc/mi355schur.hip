@@ -11,6 +11,7 @@
 #include "lorasc.hpp"
 #include "nn_induced.hpp"
 #include "block_jacobi.hpp"
+#include "amg.hpp"
 
 namespace mi {
 
@@ -577,6 +578,25 @@ int mi_block_jacobi_stats(mi_op_t op, int64_t *n_g, int64_t *n_levels, int64_t *
     if (max_level) max_level[d] = m->plan->dom[d].max_lev;
   }
   if (kept_bytes) *kept_bytes = m->kept;
+  return MI_OK;
+}
+
+static AmgOp *as_amg(mi_op_t op) { return op && op->impl ? dynamic_cast<AmgOp *>(op->impl.get()) : nullptr; }
+int mi_amg_create(mi_ctx_t ctx, int64_t nlevels, const int64_t *n_l, const int64_t *const *a_rowptr, const int64_t *const *a_colidx,
+                  const double *const *a_val, const int64_t *const *p_rowptr, const int64_t *const *p_colidx, const double *const *p_val,
+                  const double *omega_over_d, const double *coarse_inv, int index_base, mi_op_t *op) {
+  if (op) *op = nullptr;
+  if (nlevels < 1 || nlevels > 64) return fail(MI_ERR_BAD_ARG, "mi_amg_create: nlevels = %lld (1 <= nlevels <= 64)", (long long)nlevels);
+  if (!n_l) return fail(MI_ERR_BAD_ARG, "mi_amg_create: n_l is NULL");
+  MI_NEW_OP(ctx, op, new AmgOp(ctx, nlevels, n_l, a_rowptr, a_colidx, a_val, p_rowptr, p_colidx, p_val, omega_over_d, coarse_inv, index_base));
+}
+int mi_amg_stats(mi_op_t op, int64_t *n_levels, int64_t *coarse_n, int64_t *operator_nnz, int64_t *bytes_kept) {
+  AmgOp *m = as_amg(op);
+  if (!m) return fail(MI_ERR_BAD_ARG, "mi_amg_stats: not an AMG preconditioner");
+  if (n_levels) *n_levels = m->nlev;
+  if (coarse_n) *coarse_n = m->nc;
+  if (operator_nnz) *operator_nnz = m->op_nnz;
+  if (bytes_kept) *bytes_kept = m->kept;
   return MI_OK;
 }
 

@@ -907,6 +907,137 @@ def lorasc_maps(sub: Subdomains, dinds: DirichletInds):
     return [g2l[nodes] for nodes in sub.node_Id], g2l[sub.node_Γ]
 
 
+# --------------------------------------------------------------------------------------
+# Smoothed-aggregation AMG set-up (Preconditioners.AMGPreconditioner{SmoothedAggregation}, Example01:49-61)
+# --------------------------------------------------------------------------------------
+AMG_MAX_COARSE_ROWS = 4096   # the coarsest level is kept as a dense inverse: never above this many rows
+AMG_STALL = 0.9              # aggregation that keeps >= 90 % of the rows has stalled
+
+
+@dataclass
+class AmgHierarchy:
+    """What `prepare_amg_precond` hands to the device (`api.AMGPreconditioner`) and to the tests' restatement of the cycle.
+    Level l < nlevels - 1 is smoothed and has a prolongator; the last level is solved by `coarse_inv`."""
+    A: List[sp.csr_matrix]            # [nlevels] A_l, symmetric, sorted CSR
+    P: List[sp.csr_matrix]            # [nlevels - 1] P_l, n_l x n_{l+1}, sorted CSR
+    omega: List[float]                # [nlevels - 1] ω_l = 4 / (3 g_l)
+    omega_over_d: List[np.ndarray]    # [nlevels - 1] ω_l / diag(A_l)
+    coarse_inv: np.ndarray            # n_c x n_c, symmetric, column-major
+    sizes: List[int]                  # [nlevels] n_l
+    operator_complexity: float        # Σ_l nnz(A_l) / nnz(A_0)
+
+    @property
+    def nlevels(self) -> int:
+        return len(self.A)
+
+    @property
+    def operator_nnz(self) -> int:
+        return int(sum(a.nnz for a in self.A))
+
+
+def amg_aggregate(A: sp.csr_matrix) -> np.ndarray:
+    """Standard aggregation on the strength graph "every off-diagonal non-zero" (symmetric strength, θ = 0), three passes,
+    each over the nodes in ascending order: (1) a free node whose strong neighbours are all free seeds an aggregate and
+    takes them in; (2) every remaining node joins the aggregate of its first neighbour (stored order) that pass 1
+    aggregated; (3) a leftover becomes an aggregate together with its free neighbours. Returns agg[i], 0-based, dense."""
+    n = A.shape[0]
+    ptr, idx, val = A.indptr.tolist(), A.indices.tolist(), (A.data != 0).tolist()
+    nbr = [[j for j, nz in zip(idx[ptr[i]:ptr[i + 1]], val[ptr[i]:ptr[i + 1]]) if nz and j != i] for i in range(n)]
+    agg = [-1] * n
+    na = 0
+    for i in range(n):
+        if agg[i] >= 0:
+            continue
+        nb = nbr[i]
+        for j in nb:
+            if agg[j] >= 0:
+                break
+        else:
+            agg[i] = na
+            for j in nb:
+                agg[j] = na
+            na += 1
+    first = agg[:]
+    for i in range(n):
+        if agg[i] >= 0:
+            continue
+        for j in nbr[i]:
+            if first[j] >= 0:
+                agg[i] = first[j]
+                break
+    for i in range(n):
+        if agg[i] >= 0:
+            continue
+        agg[i] = na
+        for j in nbr[i]:
+            if agg[j] < 0:
+                agg[j] = na
+        na += 1
+    return np.asarray(agg, dtype=np.int64)
+
+
+def _amg_sorted_csr(M) -> sp.csr_matrix:
+    M = sp.csr_matrix(M)
+    M.sum_duplicates()
+    M.sort_indices()
+    return M
+
+
+def prepare_amg_precond(A, max_levels: int = 10, max_coarse: int = 256) -> AmgHierarchy:
+    """Smoothed aggregation on the host, once per matrix — the set-up of the reference's
+    `AMGPreconditioner{SmoothedAggregation}(A)` (Example01:49-61; AlgebraicMultigrid.jl's defaults: symmetric strength
+    with θ = 0, standard aggregation, the constant near-null-space). Per level, with d = diag(A_l):
+
+        T[i, agg(i)] = 1 / sqrt(|agg|)                       tentative prolongator
+        P_l = (I - ω_l D^-1 A_l) T,  ω_l = 4 / (3 g_l),      g_l = max_i Σ_j |a_ij| / a_ii  (Gershgorin bound on ρ(D^-1 A_l):
+                                                             no eigen-estimate, deterministic)
+        A_{l+1} = P_l' A_l P_l, symmetrised as (M + M') / 2
+
+    Coarsening stops at n_l <= max_coarse or at max_levels levels; the last level keeps the dense inverse of its
+    symmetrised matrix, symmetrised too. `max_levels = 1` is the dense inverse of A itself. Raises ValueError when the
+    aggregation stalls (n_{l+1} >= 0.9 n_l: a large level is never densified) and when the coarsest level would hold more
+    than 4096 rows. The cycle that uses the hierarchy: one pre- and one post-sweep of Jacobi damped by ω_l."""
+    A0 = _amg_sorted_csr(A)
+    if A0.shape[0] != A0.shape[1] or A0.shape[0] == 0:
+        raise ValueError("square, non-empty matrix expected")
+    if max_levels < 1:
+        raise ValueError(f"max_levels = {max_levels} (at least 1)")
+    if not np.isfinite(A0.data).all():
+        raise ValueError("the matrix holds a value that is not finite")
+    As, Ps, om, owd = [A0], [], [], []
+    while len(As) < max_levels and As[-1].shape[0] > max_coarse:
+        Al = As[-1]
+        n = Al.shape[0]
+        d = Al.diagonal()
+        if not (d > 0).all():
+            raise ValueError(f"level {len(As) - 1}: a diagonal entry is not positive")
+        agg = amg_aggregate(Al)
+        nc = int(agg.max()) + 1
+        if nc >= AMG_STALL * n:
+            raise ValueError(f"level {len(As) - 1}: aggregation stalled, {n} rows -> {nc} aggregates "
+                             f"(>= {AMG_STALL} n); the level is not densified")
+        cnt = np.bincount(agg, minlength=nc).astype(np.float64)
+        T = sp.csr_matrix((1.0 / np.sqrt(cnt[agg]), (np.arange(n), agg)), shape=(n, nc))
+        g = float(np.max(np.asarray(abs(Al).sum(axis=1)).ravel() / d))
+        w = 4.0 / (3.0 * g)
+        wd = w / d
+        P = _amg_sorted_csr(T - sp.diags(wd) @ (Al @ T))
+        M = (P.T @ Al @ P).tocsr()
+        As.append(_amg_sorted_csr((M + M.T) * 0.5))
+        Ps.append(P); om.append(w); owd.append(wd)
+    nc = As[-1].shape[0]
+    if nc > AMG_MAX_COARSE_ROWS:
+        raise ValueError(f"the coarsest level holds {nc} rows, more than the {AMG_MAX_COARSE_ROWS} a dense inverse is kept for "
+                         f"(max_levels = {max_levels}, max_coarse = {max_coarse})")
+    Ac = As[-1].toarray()
+    inv = np.linalg.inv((Ac + Ac.T) * 0.5)
+    if not np.isfinite(inv).all():
+        raise ValueError("the coarsest level is singular")
+    inv = np.asfortranarray((inv + inv.T) * 0.5)
+    nnz = [a.nnz for a in As]
+    return AmgHierarchy(As, Ps, om, owd, inv, [a.shape[0] for a in As], float(sum(nnz)) / float(nnz[0]))
+
+
 def get_schur_rhs(b_Id, A_IId, A_IΓd, b_Γ, gather_idx=None, solvers=None):
     """`get_schur_rhs` (EPDD.jl:798-821 global columns; :835-864 local columns + scatter)."""
     b = np.array(b_Γ, dtype=np.float64, copy=True)

@@ -36,7 +36,7 @@ export MiContext, MiOperator, MiPrecond,
        AssemblyPlan, assemble!, set_values!, SchurSetup, set_blocks!, interior_precond!, interior_iterations,
        keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!,
        SparseDirectPreconditioner, spd_direct_stats, bj_set_values!, MiLorasc, set_correction!, MiNNInduced, set_coupling!,
-       mi_eigsolve, mi_geneigsolve
+       mi_eigsolve, mi_geneigsolve, MiAMGPreconditioner, amg_stats
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -732,5 +732,70 @@ set_coupling!(Π::MiNNInduced, coupling::Symbol) =
 pcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiNNInduced; maxit=0) = solve(:pcg, A, M.op, b, x, nothing, maxit)   # Example03:317
 defpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, W::Matrix{Float64}, M::MiNNInduced; maxit=0) =
   solve(:defpcg, A, M.op, b, x, W, maxit)                                                                                          # Example03:313
+
+# ---------------------------------------------------------------- smoothed-aggregation AMG (Example01:49-61)
+"""`MiAMGPreconditioner`: the device form of `Preconditioners.AMGPreconditioner{SmoothedAggregation}(A)`, the `Π_amg` of
+`pcg(A, b, zeros(n), Π_amg)` in Example01:49-61 (`mi_amg_create`). `Π \\ r` is one V(1,1) cycle; the smoother is Jacobi damped
+by ω_l = 4 / (3 g_l), g_l = max_i Σ_j |a_ij| / a_ii, where the reference sweeps symmetric Gauss-Seidel.
+
+`MiAMGPreconditioner(ctx, A_l, P_l, omega_over_d, coarse_inv)`: the hierarchy as arrays — the symmetric level matrices
+(`length(A_l)` levels), the prolongators `P_l[l]` (n_l × n_{l+1}), ω_l ./ diag(A_l) per smoothed level and the dense
+symmetric inverse of the last level. `MiAMGPreconditioner(ctx, ml)`: the same from a multilevel object with `ml.levels[l].A`,
+`ml.levels[l].P` and `ml.final_A`, as `AlgebraicMultigrid.smoothed_aggregation(A)` returns it."""
+mutable struct MiAMGPreconditioner
+  op::MiOperator
+  n_levels::Int
+end
+
+function MiAMGPreconditioner(ctx::MiContext, A_l::Vector{SparseMatrixCSC{Float64,Int}}, P_l::Vector{SparseMatrixCSC{Float64,Int}},
+                             omega_over_d::Vector{Vector{Float64}}, coarse_inv::Matrix{Float64})
+  L = length(A_l)
+  (length(P_l) == L - 1 && length(omega_over_d) == L - 1) || throw(ArgumentError("$L levels need $(L - 1) prolongators and ω ./ d vectors"))
+  n_l = Int64[A.n for A in A_l]
+  ap, ai, av = csc_parts(A_l)                                           # symmetric: the CSC arrays are the CSR arrays
+  pp, px, pv = csc_parts(SparseMatrixCSC{Float64,Int}[SparseMatrixCSC(copy(transpose(P))) for P in P_l])   # CSC of P' = CSR of P
+  wd = reduce(vcat, omega_over_d; init=Float64[])
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  GC.@preserve ap ai av pp px pv begin
+    check(ccall((:mi_amg_create, lib), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Ptr{Int64}}, Ptr{Ptr{Int64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Int64}}, Ptr{Ptr{Int64}},
+                 Ptr{Ptr{Float64}}, Ptr{Float64}, Ptr{Float64}, Cint, Ref{Ptr{Cvoid}}),
+                ctx.h, L, n_l, ptrs(ap), ptrs(ai), ptrs(av), ptrs(pp), ptrs(px), ptrs(pv), wd, coarse_inv, 1, r))
+  end
+  MiAMGPreconditioner(wrap(ctx, r), L)
+end
+
+function MiAMGPreconditioner(ctx::MiContext, ml)
+  A_l = SparseMatrixCSC{Float64,Int}[SparseMatrixCSC{Float64,Int}(lev.A) for lev in ml.levels]
+  push!(A_l, SparseMatrixCSC{Float64,Int}(ml.final_A))
+  P_l = SparseMatrixCSC{Float64,Int}[SparseMatrixCSC{Float64,Int}(lev.P) for lev in ml.levels]
+  wd = Vector{Float64}[]
+  for A in A_l[1:end-1]
+    d = Vector{Float64}(diag(A))
+    g = maximum(vec(sum(abs, A; dims=2)) ./ d)
+    push!(wd, (4 / (3g)) ./ d)
+  end
+  Ac = Matrix(A_l[end])
+  Z = inv((Ac + Ac') / 2)
+  MiAMGPreconditioner(ctx, A_l, P_l, wd, (Z + Z') / 2)
+end
+
+function amg_stats(Π::MiAMGPreconditioner)
+  a, b, c, d = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+  check(ccall((:mi_amg_stats, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), Π.op.h, a, b, c, d))
+  (n_levels=Int(a[]), coarse_n=Int(b[]), operator_nnz=Int(c[]), bytes_kept=Int(d[]))
+end
+
+\(Π::MiAMGPreconditioner, r::Vector{Float64}) = Π.op * r
+ldiv!(z::Vector{Float64}, Π::MiAMGPreconditioner, r::Vector{Float64}) = mul!(z, Π.op, r)
+ldiv!(Π::MiAMGPreconditioner, r::Vector{Float64}) = (r .= Π.op * copy(r))
+pcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditioner; maxit=0) = solve(:pcg, A, M.op, b, x, nothing, maxit)   # Example01:58
+defpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, W::Matrix{Float64}, M::MiAMGPreconditioner; maxit=0) =
+  solve(:defpcg, A, M.op, b, x, W, maxit)
+eigpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditioner, nvec::Int, spdim::Int; maxit=0) =
+  eigsolve(:eigpcg, A, M.op, b, x, nothing, nvec, spdim, maxit)
+eigdefpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditioner, W::Matrix{Float64}, spdim::Int; maxit=0) =
+  eigsolve(:eigdefpcg, A, M.op, b, x, W, size(W, 2), spdim, maxit)
+initpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditioner, W::Matrix{Float64}; maxit=0) = initsolve(A, M.op, b, x, W, maxit)
 
 end # module
