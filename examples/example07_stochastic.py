@@ -56,6 +56,9 @@ def main():
     ap.add_argument("--nn-f32", action="store_true",
                     help="run the two solves of Example07:273-277 also with fp32-STORED Neumann-Neumann blocks (storage=\"f32\": "
                          "half the preconditioner's bytes, all arithmetic fp64) and print both count vectors side by side")
+    ap.add_argument("--kl", default="", help="root file name of KL modes written by examples/example04_kl.py (Example07:124-125 reads "
+                                             "data/$root_fname.kl-eigvals.npz / .kl-eigvecs.npz); default: fem.synthetic_kl")
+    ap.add_argument("--kl-dir", default="data")
     ap.add_argument("--gg", action="store_true", help="also pcg(S, b_schur, 0, A_ΓΓ_0) and pcg(S, b_schur, 0, A_ΓΓ_t) (Example07:412, 416)")
     args = ap.parse_args()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -64,7 +67,12 @@ def main():
     f = lambda x, y: -1.0 + 0 * x
     uexact = lambda x, y: 0.734 + 0 * x
     mesh = fem.get_mesh(args.N)
-    kl = fem.synthetic_kl(mesh.points)
+    if args.kl:
+        kl = fem.SyntheticKL(*pkg.io.load_kl(args.kl, args.kl_dir))
+        if kl.Ψ.shape[0] != mesh.points.shape[1]:
+            raise SystemExit(f"--kl: modes on {kl.Ψ.shape[0]} nodes, the mesh has {mesh.points.shape[1]} (run example04_kl.py with --N {args.N})")
+    else:
+        kl = fem.synthetic_kl(mesh.points)
     rng = np.random.default_rng(args.seed)
     gs = [fem.draw(kl, rng)[1] for _ in range(args.nreals)]          # Example07:140-144: all draws up front
 

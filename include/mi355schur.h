@@ -579,6 +579,47 @@ int mi_eigsolve(mi_op_t A, mi_op_t B /*NULL: standard*/, mi_op_t Binv /*NULL iff
                 const double *v0 /*NULL: seeded host vector*/, double *vals /*nev*/, double *vecs /*n x nev, col-major*/,
                 double *resid /*nev, may be NULL*/, int64_t *nconv, int64_t *nrestart, int64_t *napply);
 
+/* ---------------------------------------------------------------- Karhunen-Loève: matrix-free covariance operators
+ * The reference's KL layer (Fem/KarhunenLoeve.jl, Fem/KarhunenLoeveDomainDecomposition.jl = "KLDD.jl", Fem/Covariances.jl)
+ * assembles the dense Galerkin matrix C[i, j] = ∫∫ ϕ_i(P) cov(P, P') ϕ_j(P') by two O(nnode nel) element loops and hands it to
+ * `Arpack.eigs(C, M)`. The first loop builds R = M K, the second C = R M (KarhunenLoeve.jl:40-105), with M the consistent P1
+ * mass matrix and K[i, j] = cov(p_i, p_j) the nodal covariance: C = M K M, and K is applied on the fly (csrc/cov_kernels.hpp)
+ * instead of being stored.
+ * Covariance models: MI_COV_SEXP, c = sig2 exp(-((x1 - x2)² + (y1 - y2)²) / L²) (`cov_sexp`, Covariances.jl:23-28);
+ * MI_COV_EXP, c = sig2 exp(-sqrt((x1 - x2)² + (y1 - y2)²) / L), the "Exp" of get_root_filename
+ * (KarhunenLoeveDomainDecompositionHelper.jl:54). The exponent is evaluated as written there (a true division).
+ *
+ * mi_cov_apply — Y[0:nt, 0:m] = Σ_j c(pt[:, i], ps[:, j]) X[j, 0:m]: the `cov(x[r], y[r], xj, yj)` evaluations of
+ *   KarhunenLoeve.jl:75-77, KLDD.jl:171-173 and of the rectangular (idom, jdom) loop KLDD.jl:508-547, applied to a panel.
+ *   pt (2 x nt) and ps (2 x ns) in the reference's `points` layout (x and y of a node adjacent); X column-major with ldx >= ns,
+ *   Y column-major with ldy >= nt; only rows [0, ns) resp. [0, nt) of a column are read resp. written. All four pointers follow
+ *   the context's pointer mode; either way the call returns when Y is complete (its workspace is its own and is handed back
+ *   before it returns; the capture-safe form is the operator below). pt == ps is allowed, Y must not
+ *   overlap X. Sources are split over workgroups when the targets alone do not fill the device; partial sums are added in a
+ *   fixed order (no atomics): equal calls give equal bits.
+ * mi_cov_tiling — the tiling mi_cov_apply uses for these sizes, a pure host function (no device, no context): target rows per
+ *   workgroup, sources per LDS chunk, columns per thread, and the number of source splits (a function of nt, ns, m only).
+ *   Any output pointer may be NULL.
+ * mi_kl_cov_create — the operator x -> C x = M (K (M x)) on the n nodes `points` (2 x n): what do_mass_covariance_assembly
+ *   (KarhunenLoeve.jl:27-108) and do_local_mass_covariance_assembly (KLDD.jl:120-204) return, as the `A` of
+ *   mi_eigsolve(C, B = M, Binv = M^-1, MI_EIG_LR) — `Arpack.eigs(C, M, nev=nev)` (KarhunenLoeve.jl:138, KLDD.jl:679); the vectors
+ *   come back with Φ' M Φ = I, the normalisation of KarhunenLoeve.jl:183-185. m_rowptr / m_colidx / m_val: CSR (= CSC) arrays
+ *   of the symmetric n x n mass matrix (get_mass_matrix, EllipticPde.jl:412-466; do_local_mass_assembly, KLDD.jl:236-293),
+ *   0-based HOST arrays like `points`. One apply is SpMV, covariance launch (+ its reduction), SpMV; all workspace is allocated
+ *   here, the apply neither allocates nor synchronises (it is replayed inside the eigensolver's graphs). mi_op_bytes names the
+ *   covariance launch as the dominant kernel (32 n bytes of points, as targets and as sources, + 16 n of vectors; it is compute bound: n² exp), and
+ *   mi_op_apply_dominant / mi_op_time_dominant launch it.
+ * MI_ERR_BAD_ARG with a mi_last_error() text, nothing written: an unknown model; L <= 0, sig2 < 0 or either not finite; points
+ *   that are not finite (host arrays); nt, ns or m < 1 (or above 2^30); ldx < ns or ldy < nt; a NULL pointer; a CSR matrix that
+ *   is not n x n; a context that is one rank of several (sharded KL operators are not provided). */
+#define MI_COV_SEXP 0
+#define MI_COV_EXP 1
+int mi_cov_apply(mi_ctx_t ctx, int model, double sig2, double L, int64_t nt, const double *pt, int64_t ns, const double *ps,
+                 int64_t m, const double *X, int64_t ldx, double *Y, int64_t ldy);
+int mi_cov_tiling(int64_t nt, int64_t ns, int64_t m, int64_t *row_tile, int64_t *src_chunk, int64_t *col_block, int64_t *splits);
+int mi_kl_cov_create(mi_ctx_t ctx, int model, double sig2, double L, int64_t n, const double *points, const int64_t *m_rowptr,
+                     const int64_t *m_colidx, const double *m_val, mi_op_t *op);
+
 /* ---------------------------------------------------------------- timing on the context's stream */
 int mi_event_create(mi_event_t *ev);
 int mi_event_record(mi_ctx_t ctx, mi_event_t ev);

@@ -19,6 +19,7 @@ MI_ERR_COMM, MI_ERR_NO_DEVICE, MI_ERR_CALLBACK, MI_ERR_BOUNDS = -5, -6, -7, -8
 MI_PTR_HOST, MI_PTR_DEVICE = 0, 1
 MI_NNI_AS_WRITTEN, MI_NNI_ASSEMBLED = 0, 1
 MI_EIG_SR, MI_EIG_LR = 0, 1
+MI_COV_SEXP, MI_COV_EXP = 0, 1
 MI_COMM_ID_BYTES = 128
 MI_PEER_HANDLE_BYTES = 64
 
@@ -124,6 +125,9 @@ SIGNATURES = {
     "mi_initcg": [vp, vp, vp, vp, i64, i64, C.c_double, f64p, i64, i64p],
     "mi_initpcg": [vp, vp, vp, vp, vp, i64, i64, C.c_double, f64p, i64, i64p],
     "mi_eigsolve": [vp, vp, vp, i64, C.c_int, i64, C.c_double, i64, vp, f64p, vp, f64p, i64p, i64p, i64p],
+    "mi_cov_apply": [vp, C.c_int, C.c_double, C.c_double, i64, vp, i64, vp, i64, vp, i64, vp, i64],
+    "mi_cov_tiling": [i64, i64, i64, i64p, i64p, i64p, i64p],
+    "mi_kl_cov_create": [vp, C.c_int, C.c_double, C.c_double, i64, f64p, i64p, i64p, f64p, C.POINTER(vp)],
     "mi_event_create": [C.POINTER(vp)],
     "mi_event_record": [vp, vp],
     "mi_event_elapsed_ms": [vp, vp, f64p],

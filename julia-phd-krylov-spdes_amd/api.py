@@ -1371,4 +1371,148 @@ def geneigsolve(A: Operator, B: Operator, Binv: Operator, nev: int, which: str =
     return _eigsolve(A, B, Binv, nev, which, krylovdim, tol, maxiter, v0)
 
 
+# ------------------------------------------------------------------ Karhunen-Loève on the matrix-free covariance kernel
+_COV_MODEL = {"SExp": _lib.MI_COV_SEXP, "Exp": _lib.MI_COV_EXP}
+
+
+def _cov_model(model) -> int:
+    if model not in _COV_MODEL:
+        raise ValueError(f"model = {model!r}: 'SExp' or 'Exp' expected")
+    return _COV_MODEL[model]
+
+
+def _points_2xn(points):
+    """(2, n) coordinates -> the reference's `points` layout in memory (x and y of a node adjacent) and n."""
+    p = np.asarray(points, dtype=np.float64)
+    if p.ndim != 2 or p.shape[0] != 2:
+        raise ValueError("points: a (2, n) array expected")
+    return np.ascontiguousarray(p.T), p.shape[1]
+
+
+def cov_tiling(nt: int, ns: int, m: int = 1):
+    """`mi_cov_tiling` -> (row_tile, src_chunk, col_block, splits); a pure host function, no device needed."""
+    out = [i64() for _ in range(4)]
+    check(_lib.load().mi_cov_tiling(i64(nt), i64(ns), i64(m), *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+def cov_apply(ctx: Context, model: str, sig2: float, L: float, pt, ps, X):
+    """Y = K(pt, ps) X with K[i, j] = cov(pt[:, i], ps[:, j]) evaluated on the fly (`mi_cov_apply`): the covariance
+    evaluations of KarhunenLoeve.jl:75-77 / KLDD.jl:508-547 applied to a vector (ns,) or a panel (ns, m). numpy arrays."""
+    pt_m, nt = _points_2xn(pt)
+    ps_m, ns = (pt_m, nt) if ps is pt else _points_2xn(ps)
+    X = np.asarray(X, dtype=np.float64)
+    vec = X.ndim == 1
+    Xf = np.asfortranarray(X.reshape(ns, -1))
+    m = Xf.shape[1]
+    Y = np.empty((nt, m), order="F")
+    check(ctx._L.mi_ctx_set_pointer_mode(ctx._h, _lib.MI_PTR_HOST))
+    check(ctx._L.mi_cov_apply(ctx._h, C.c_int(_cov_model(model)), C.c_double(sig2), C.c_double(L), i64(nt), vp(pt_m.ctypes.data),
+                              i64(ns), vp(ps_m.ctypes.data), i64(m), vp(Xf.ctypes.data), i64(ns), vp(Y.ctypes.data), i64(nt)))
+    return Y[:, 0].copy() if vec else Y
+
+
+class CovarianceOperator(Operator):
+    """x -> C x with C = M K M, K[i, j] = cov(p_i, p_j): the dense matrix of do_mass_covariance_assembly
+    (KarhunenLoeve.jl:27-108; local form KLDD.jl:120-204) as a matrix-free operator (`mi_kl_cov_create`). `M`: the mass
+    matrix of the same nodes (scipy sparse, symmetric)."""
+
+    def __init__(self, ctx: Context, points, M, model: str = "SExp", sig2: float = 1.0, L: float = 0.1):
+        pts, n = _points_2xn(points)
+        M = sp.csr_matrix(M)
+        M.sort_indices()
+        if M.shape != (n, n):
+            raise ValueError(f"M is {M.shape}, {n} nodes")
+        ptr, idx, val = _i64(M.indptr), _i64(M.indices), _f64(M.data)
+        h = vp()
+        check(ctx._L.mi_kl_cov_create(ctx._h, C.c_int(_cov_model(model)), C.c_double(sig2), C.c_double(L), i64(n),
+                                      pts.ctypes.data_as(f64p), ptr.ctypes.data_as(i64p), idx.ctypes.data_as(i64p),
+                                      val.ctypes.data_as(f64p), C.byref(h)))
+        super().__init__(ctx, h)
+        self.model, self.sig2, self.L = model, sig2, L
+
+
+def _kl_pairs(ctx: Context, points, M, nev: int, model, sig2, L, tol, maxiter):
+    """`Arpack.eigs(C, M, nev=nev)` (KarhunenLoeve.jl:138, KLDD.jl:679): the nev dominant pairs of C ϕ = λ M ϕ with Φ' M Φ = I,
+    krylovdim = Arpack's default ncv = max(20, 2 nev + 1)."""
+    Cop = CovarianceOperator(ctx, points, M, model, sig2, L)
+    Mop = SparseMatrixCSC(ctx, M)
+    Minv = None
+    try:
+        Minv = SparseDirectPreconditioner(ctx, M)
+    except MiError as e:                           # a separator above the one-level dissection's cap (n in the tens of thousands)
+        if e.code != _lib.MI_ERR_BAD_ARG:
+            raise
+        Minv = BlockJacobiPreconditioner(ctx, 1, M)   # nb = 1 is `M \ b`, exact, by breadth-first level elimination
+    try:
+        λ, Φ, info = geneigsolve(Cop, Mop, Minv, nev, "LR", krylovdim=max(20, 2 * nev + 1), tol=tol, maxiter=maxiter)
+    finally:
+        Cop.close()
+        Mop.close()
+        Minv.close()
+    if info.converged < nev:                       # Arpack throws where its iteration does not converge; so does this
+        raise RuntimeError(f"solve_kl: {info.converged} of {nev} pairs converged to {tol:g} in {maxiter} restarts")
+    return np.array(λ), np.asfortranarray(Φ), info
+
+
+def solve_kl(ctx: Context, cells, points, nev: int, model: str = "SExp", sig2: float = 1.0, L: float = 0.1, relative: float = 0.99,
+             tol: float = 1e-12, maxiter: int = 100, verbose: bool = True):
+    """`solve_kl(cells, points, cov, nev; relative)` (KarhunenLoeve.jl:123-193) -> (Λ[:nvec], Φ[:, :nvec]): the dominant pairs
+    of C ϕ = λ M ϕ on the device, then the reference's keep loop: positive eigenvalues until relative · Area · cov(centre,
+    centre) is reached."""
+    from . import fem
+    M = fem.get_mass_matrix(cells, points)
+    λ, Φ, _ = _kl_pairs(ctx, points, M, nev, model, sig2, L, tol, maxiter)
+    Area, center = fem.kl_energy(cells, points)
+    energy_expected = relative * Area * float(fem.cov(model, center[0], center[1], center[0], center[1], sig2, L))
+    nvec, energy_achieved = fem.kl_keep(λ, energy_expected)
+    if verbose:
+        print(f"{nvec}/{nev} vectors kept for {energy_achieved / energy_expected * relative:.5f} relative energy")
+    return λ[:nvec], Φ[:, :nvec]
+
+
+def solve_local_kl(ctx: Context, cells, points, epart, nev: int, idom: int, model: str = "SExp", sig2: float = 1.0, L: float = 0.1,
+                   relative: float = 0.99, tol: float = 1e-12, maxiter: int = 100, verbose: bool = True):
+    """`solve_local_kl(cells, points, epart, cov, nev, idom; relative)` (KLDD.jl:657-735) -> fem.KLSubDomain: the same on the
+    nodes and elements of subdomain `idom` (0-based)."""
+    from . import fem
+    inds_l2g, inds_g2l, elems, center = fem.kl_set_subdomain(cells, points, epart, idom)
+    M = fem.do_local_mass_assembly(cells, points, inds_g2l, elems)
+    λ, Φ, _ = _kl_pairs(ctx, points[:, inds_l2g], M, nev, model, sig2, L, tol, maxiter)
+    Area, _ = fem.kl_energy(cells, points, elems)
+    energy_expected = relative * Area * float(fem.cov(model, center[0], center[1], center[0], center[1], sig2, L))
+    nvec, energy_achieved = fem.kl_keep(λ, energy_expected)
+    if verbose:
+        print(f"idom = {idom}, {nvec}/{nev} vectors kept for {energy_achieved / energy_expected * relative:.5f} relative energy")
+    return fem.KLSubDomain(inds_g2l, inds_l2g, elems, Φ[:, :nvec], center, energy_expected / relative, M, λ)
+
+
+def do_global_mass_covariance_reduced_assembly(ctx: Context, points, subdomains, Φd, centerd, model: str = "SExp", sig2: float = 1.0,
+                                               L: float = 0.1, forget: float = -1.0):
+    """`do_global_mass_covariance_reduced_assembly` (KLDD.jl:465-614) -> K (Σ md x Σ md): for every pair idom <= jdom whose
+    centre covariance exceeds `forget`, block (idom, jdom) = Φ_i' (M_i (K(P_i, P_j) (M_j Φ_j))) with the covariance panel
+    product on the device — the dense C[i, j] of KLDD.jl:505-586 is M_i K(P_i, P_j) M_j and is never formed. The mirror block
+    is copied (KLDD.jl:604); a diagonal block is mirrored from its upper triangle, the half `Symmetric(K)` reads (KLDD.jl:791).
+    `subdomains`: objects with `.inds_l2g` and `.M` (fem.KLSubDomain)."""
+    from . import fem
+    md = [int(np.asarray(Φ).shape[1]) for Φ in Φd]
+    off = np.concatenate([[0], np.cumsum(md)]).astype(int)
+    K = np.zeros((off[-1], off[-1]))
+    P = [np.asarray(points)[:, s.inds_l2g] for s in subdomains]
+    MΦ = [np.asfortranarray(s.M @ np.asarray(Φ)) for s, Φ in zip(subdomains, Φd)]
+    for idom in range(len(Φd)):
+        for jdom in range(idom, len(Φd)):
+            ci, cj = centerd[idom], centerd[jdom]
+            if not float(fem.cov(model, ci[0], ci[1], cj[0], cj[1], sig2, L)) > forget:
+                continue
+            Z = cov_apply(ctx, model, sig2, L, P[idom], P[jdom], MΦ[jdom])
+            blk = MΦ[idom].T @ Z                                  # Φ_i' M_i Z (M_i is symmetric)
+            if idom == jdom:
+                blk = np.triu(blk) + np.triu(blk, 1).T
+            K[off[idom]:off[idom + 1], off[jdom]:off[jdom + 1]] = blk
+            if idom != jdom:
+                K[off[jdom]:off[jdom + 1], off[idom]:off[idom + 1]] = blk.T
+    return K
+
+
 GlobalSchur.use_level_solver = _use_level_solver

@@ -12,6 +12,7 @@
 #include "nn_induced.hpp"
 #include "block_jacobi.hpp"
 #include "amg.hpp"
+#include "kl.hpp"
 
 namespace mi {
 
@@ -1005,6 +1006,82 @@ int mi_eigsolve(mi_op_t A, mi_op_t B, mi_op_t Binv, int64_t nev, int which, int6
     if (napply) *napply = r.napply;
     return MI_OK;
   });
+}
+
+// ---------------------------------------------------------------- Karhunen-Loève: covariance kernel and C = M K M (kl.hpp)
+int mi_cov_tiling(int64_t nt, int64_t ns, int64_t m, int64_t *row_tile, int64_t *src_chunk, int64_t *col_block, int64_t *splits) {
+  if (nt < 1 || ns < 1 || m < 1) return fail(MI_ERR_BAD_ARG, "mi_cov_tiling: nt = %lld, ns = %lld, m = %lld: all must be at least 1", (long long)nt, (long long)ns, (long long)m);
+  if (row_tile) *row_tile = COV_ROW_TILE;
+  if (src_chunk) *src_chunk = COV_SRC_CHUNK;
+  if (col_block) *col_block = COV_CB;
+  if (splits) *splits = cov_tiling(nt, ns, m).splits;
+  return MI_OK;
+}
+
+int mi_cov_apply(mi_ctx_t ctx, int model, double sig2, double L, int64_t nt, const double *pt, int64_t ns, const double *ps,
+                 int64_t m, const double *X, int64_t ldx, double *Y, int64_t ldy) {
+  const char *me = "mi_cov_apply";
+  if (!ctx || !pt || !ps || !X || !Y) return fail(MI_ERR_BAD_ARG, "%s: ctx, pt, ps, X or Y is NULL", me);
+  const int64_t cap = (int64_t)1 << 30;
+  if (nt < 1 || ns < 1 || m < 1 || nt > cap || ns > cap || m > 65535 * (int64_t)COV_CB)
+    return fail(MI_ERR_BAD_ARG, "%s: nt = %lld, ns = %lld, m = %lld: each at least 1 (nt, ns at most 2^30)", me, (long long)nt, (long long)ns, (long long)m);
+  if (ldx < ns || ldy < nt)
+    return fail(MI_ERR_BAD_ARG, "%s: ldx = %lld < ns = %lld or ldy = %lld < nt = %lld", me, (long long)ldx, (long long)ns, (long long)ldy, (long long)nt);
+  if (ctx->has_comm()) return fail(MI_ERR_BAD_ARG, "%s: the context is one rank of several; sharded covariance applies are not provided", me);
+  return guarded([&]() -> int {
+    cov_check_model(me, model, sig2, L);
+    ctx->use();
+    hipStream_t s = ctx->stream;
+    DevBuf<double> work(std::max<size_t>(1, cov_workspace(nt, ns, m)));
+    if (ctx->ptr_mode == MI_PTR_DEVICE) {
+      cov_launch(s, model, sig2, L, (int)nt, pt, (int)ns, ps, (int)m, X, ldx, Y, ldy, work.p, nullptr);
+      MI_HIP(hipGetLastError());
+      MI_HIP(hipStreamSynchronize(s));   // the workspace goes back to the pool behind this brace
+      return MI_OK;
+    }
+    cov_check_points(me, "pt", pt, nt);
+    if (ps != pt) cov_check_points(me, "ps", ps, ns);
+    DevBuf<double> dpt(2 * (size_t)nt), dps, dX((size_t)ns * m), dY((size_t)nt * m);
+    MI_HIP(hipMemcpyAsync(dpt.p, pt, sizeof(double) * 2 * (size_t)nt, hipMemcpyHostToDevice, s));
+    const double *src = dpt.p;
+    if (ps != pt) {
+      dps.alloc(2 * (size_t)ns);
+      MI_HIP(hipMemcpyAsync(dps.p, ps, sizeof(double) * 2 * (size_t)ns, hipMemcpyHostToDevice, s));
+      src = dps.p;
+    }
+    // rows [0, ns) of every column only: the padding up to ldx is not the caller's to be read
+    MI_HIP(hipMemcpy2DAsync(dX.p, sizeof(double) * (size_t)ns, X, sizeof(double) * (size_t)ldx, sizeof(double) * (size_t)ns, (size_t)m,
+                            hipMemcpyHostToDevice, s));
+    cov_launch(s, model, sig2, L, (int)nt, dpt.p, (int)ns, src, (int)m, dX.p, ns, dY.p, nt, work.p, nullptr);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipMemcpy2DAsync(Y, sizeof(double) * (size_t)ldy, dY.p, sizeof(double) * (size_t)nt, sizeof(double) * (size_t)nt, (size_t)m,
+                            hipMemcpyDeviceToHost, s));
+    MI_HIP(hipStreamSynchronize(s));
+    return MI_OK;
+  });
+}
+
+int mi_kl_cov_create(mi_ctx_t ctx, int model, double sig2, double L, int64_t n, const double *points, const int64_t *m_rowptr,
+                     const int64_t *m_colidx, const double *m_val, mi_op_t *op) {
+  const char *me = "mi_kl_cov_create";
+  if (op) *op = nullptr;
+  if (!ctx || !op || !points || !m_rowptr || !m_colidx || !m_val) return fail(MI_ERR_BAD_ARG, "%s: ctx, op, points or an array of M is NULL", me);
+  if (n < 1 || n > ((int64_t)1 << 30)) return fail(MI_ERR_BAD_ARG, "%s: n = %lld (1 <= n <= 2^30)", me, (long long)n);
+  if (ctx->has_comm()) return fail(MI_ERR_BAD_ARG, "%s: the context is one rank of several; sharded KL operators are not provided", me);
+  MI_NEW_OP(ctx, op, ([&]() -> Operator * {
+    cov_check_model(me, model, sig2, L);
+    cov_check_points(me, "points", points, n);
+    HostCsr hm;
+    try {
+      hm = host_csr(n, n, m_rowptr, m_colidx, m_val, 0);
+    } catch (const Error &e) {
+      const std::string why = last_error();
+      raise(e.code, "%s: M is not a %lld x %lld CSR matrix: %s", me, (long long)n, (long long)n, why.c_str());
+    }
+    for (double v : hm.val)
+      if (!std::isfinite(v)) raise(MI_ERR_BAD_ARG, "%s: M holds %g (not finite)", me, v);
+    return new KlCovOp(ctx, model, sig2, L, n, points, hm);
+  })());
 }
 
 // ---------------------------------------------------------------- on-device block assembly

@@ -1105,6 +1105,162 @@ def draw(kl: SyntheticKL, rng: np.random.Generator):
 
 
 # --------------------------------------------------------------------------------------
+# Karhunen-Loève layer, host side (Fem/KarhunenLoeve.jl, Fem/KarhunenLoeveDomainDecomposition.jl = "KLDD.jl",
+# Fem/KarhunenLoeveDomainDecompositionHelper.jl, Fem/Covariances.jl). The covariance-heavy parts run on the device
+# (api.solve_kl, api.solve_local_kl, api.do_global_mass_covariance_reduced_assembly); what follows is index work, the small
+# dense eigenproblem and the projection. Subdomains are numbered from 0, maps are flat arrays with -1 for "absent".
+# --------------------------------------------------------------------------------------
+COV_MODELS = ("SExp", "Exp")     # the names of get_root_filename (KarhunenLoeveDomainDecompositionHelper.jl:54)
+
+
+def cov(model: str, x1, y1, x2, y2, sig2: float = 1.0, L: float = 0.1):
+    """`cov_sexp` (Covariances.jl:23-28) and the exponential model, written as the reference writes them (numpy, elementwise)."""
+    r2 = (x1 - x2) ** 2 + (y1 - y2) ** 2
+    if model == "SExp":
+        return sig2 * np.exp(-r2 / L ** 2)
+    if model == "Exp":
+        return sig2 * np.exp(-np.sqrt(r2) / L)
+    raise ValueError(f"model = {model!r}: one of {COV_MODELS} expected")
+
+
+def _element_areas(cells, points):
+    x, y = points[0][cells], points[1][cells]
+    return _element_geometry(x, y)[1]
+
+
+def _mass_triplets(cells, Area):
+    """Element mass matrices Area/12 [2 1 1; 1 2 1; 1 1 2] in the push! order of EllipticPde.jl:442-459 (element, i, j)."""
+    nel = cells.shape[1]
+    I = np.repeat(cells.T[:, :, None], 3, axis=2).reshape(-1)            # cells[i, el] for (el, i, j)
+    J = np.repeat(cells.T[:, None, :], 3, axis=1).reshape(-1)            # cells[j, el]
+    V = np.where(np.eye(3, dtype=bool)[None], (Area / 6.0)[:, None, None], (Area / 12.0)[:, None, None]).reshape(-1)
+    assert I.size == 9 * nel
+    return I.astype(np.int64), J.astype(np.int64), V
+
+
+def get_mass_matrix(cells, points) -> sp.csr_matrix:
+    """`get_mass_matrix(cells, points)` (EllipticPde.jl:412-466): the consistent P1 mass matrix, M[i, j] = ∫ ϕ_i ϕ_j."""
+    I, J, V = _mass_triplets(cells, _element_areas(cells, points))
+    n = points.shape[1]
+    return _coo_to_csr(I, J, V, (n, n))
+
+
+def kl_set_subdomain(cells, points, epart, idom: int):
+    """`set_subdomain(cells, points, epart, idom)` (KLDD.jl:40-80) -> (inds_l2g, inds_g2l, elems, center): ALL nodes of the
+    subdomain's elements in first-seen order (element by element, vertex by vertex); the centre is their mean."""
+    elems = np.flatnonzero(np.asarray(epart) == idom).astype(np.int64)
+    inds_l2g = _first_unique(cells[:, elems].T.reshape(-1)).astype(np.int64)
+    inds_g2l = np.full(points.shape[1], -1, dtype=np.int64)
+    inds_g2l[inds_l2g] = np.arange(inds_l2g.size)
+    center = np.zeros(2)
+    for inode in inds_l2g:                                   # the reference's summation order (KLDD.jl:73-77)
+        center[0] += points[0, inode]
+        center[1] += points[1, inode]
+    center /= inds_l2g.size
+    return inds_l2g, inds_g2l, elems, center
+
+
+def do_local_mass_assembly(cells, points, inds_g2l, elems) -> sp.csr_matrix:
+    """`do_local_mass_assembly` (KLDD.jl:236-293): the mass matrix of one subdomain in its local numbering."""
+    sub = cells[:, elems]
+    I, J, V = _mass_triplets(inds_g2l[sub], _element_areas(sub, points))
+    n = int((inds_g2l >= 0).sum())
+    return _coo_to_csr(I, J, V, (n, n))
+
+
+def kl_energy(cells, points, elems=None):
+    """(Area, centre) as solve_kl integrates them (KarhunenLoeve.jl:145-165): the area of the elements and the mean over
+    the elements of their centroids, accumulated vertex by vertex."""
+    sub = cells if elems is None else cells[:, elems]
+    Area = 0.0
+    for a in _element_areas(sub, points):
+        Area += a
+    center = np.zeros(2)
+    for el in range(sub.shape[1]):
+        for r in range(3):
+            center[0] += points[0, sub[r, el]] / 3
+            center[1] += points[1, sub[r, el]] / 3
+    center /= sub.shape[1]
+    return float(Area), center
+
+
+def kl_keep(λ, energy_expected: float):
+    """The keep loop of KarhunenLoeve.jl:169-180 / KLDD.jl:706-717 -> (nvec, energy_achieved): positive eigenvalues, in the
+    order given, until `energy_expected` is reached."""
+    energy_achieved, nvec = 0.0, 0
+    for λ_i in λ:
+        if λ_i > 0:
+            nvec += 1
+            energy_achieved += float(λ_i)
+        else:
+            break
+        if energy_achieved >= energy_expected:
+            break
+    return nvec, energy_achieved
+
+
+def trim_and_order(Λ, Φ):
+    """`trim_and_order` (KLDD.jl:1070-1077): drop the (leading, `eigen` is ascending) negative values, most dominant first."""
+    Λ, Φ = np.asarray(Λ), np.asarray(Φ)
+    neg_vals = int(np.sum(Λ < 0))
+    return Λ[neg_vals:][::-1].copy(), Φ[:, neg_vals:][:, ::-1].copy()
+
+
+def project_on_mesh(nnodes: int, Φ, elemsd, inds_l2gd, Φd):
+    """`project_on_mesh` (KLDD.jl:920-959): Ψ[inode, imode] = (Σ_idom Σ_α Φ[ind(idom, α), imode] Φd[idom][i, α]) / cnt[inode],
+    cnt the number of subdomains a node belongs to. Sums run in the reference's order (idom, then α, ascending)."""
+    Φ = np.asarray(Φ)
+    nmodes = Φ.shape[1]
+    Ψ = np.zeros((nnodes, nmodes))
+    cnt = np.zeros(nnodes, dtype=np.int64)
+    off = 0
+    for idom, l2g in enumerate(inds_l2gd):
+        cnt[l2g] += 1
+        md = Φd[idom].shape[1]
+        for α in range(md):
+            Ψ[l2g, :] += Φd[idom][:, α][:, None] * Φ[off + α, :][None, :]
+        off += md
+    return Ψ / cnt[:, None]
+
+
+def solve_global_reduced_kl(nnode: int, K, energy_expected: float, elemsd, inds_l2gd, Φd, relative: float = 0.99, verbose: bool = True):
+    """`solve_global_reduced_kl` (KLDD.jl:783-810): `eigen(Symmetric(K))` (the upper triangle), trim_and_order, the energy
+    truncation, project_on_mesh -> (Λ[:nvec], Ψ)."""
+    import scipy.linalg as sla
+    Λ, Φ = sla.eigh(np.asarray(K), lower=False)
+    Λ, Φ = trim_and_order(Λ, Φ)
+    energy_expected *= relative
+    energy_achieved, nvec = 0.0, 0
+    for λ_i in Λ:
+        energy_achieved += float(λ_i)
+        nvec += 1
+        if energy_achieved >= energy_expected:
+            break
+    Ψ = project_on_mesh(nnode, Φ[:, :nvec], elemsd, inds_l2gd, Φd)
+    if verbose:
+        print(f"{nvec}/{Λ.size} vectors kept for {energy_achieved / energy_expected * relative:.5f} relative energy")
+    return Λ[:nvec], Ψ
+
+
+@dataclass
+class KLSubDomain:
+    """The reference's `SubDomain` (returned by solve_local_kl, KLDD.jl:729-734) plus the local mass matrix it was solved with."""
+    inds_g2l: np.ndarray      # (nnode,) local index of a mesh node, -1 outside the subdomain
+    inds_l2g: np.ndarray      # (n_d,) mesh node of a local node, first-seen order
+    elems: np.ndarray         # elements of the subdomain
+    Φ: np.ndarray             # (n_d, nvec) kept local eigenfunctions, Φ' M Φ = I
+    center: np.ndarray        # (2,)
+    energy: float             # Area * cov(center, center)
+    M: sp.csr_matrix          # do_local_mass_assembly
+    λ: np.ndarray = None      # all nev local eigenvalues (what save_eigvals writes, KLDD.jl:680-684)
+
+
+def suggest_parameters(nnode: int):
+    """`suggest_parameters(nnode)` (KarhunenLoeveDomainDecompositionHelper.jl:35-41) -> (relative_local, relative_global)."""
+    return (.9986, .995) if nnode <= 100_000 else (.9993, .995)
+
+
+# --------------------------------------------------------------------------------------
 # One-call problem builders used by tests, smoke() and bench.py
 # --------------------------------------------------------------------------------------
 @dataclass

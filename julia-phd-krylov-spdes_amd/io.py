@@ -9,6 +9,8 @@ reference's `data/*.npz` files are NPY files; numpy.load recognises them by thei
   Fem/Mesh.jl:84-91   load_mesh:       the inverse (cells .+ 1)
   Fem/Mesh.jl:216-219 save_partition:  epart .- 1, npart .- 1
   Example07:281-285   iteration counts as a 1-D integer array
+  Example02:41-42, Example04:92-93   KL pairs: `data/<root>.kl-eigvals.npz` (nvec,), `.kl-eigvecs.npz` (nnode x nvec),
+                                     <root> = get_root_filename(model, sig2, L, tentative_nnode)
 
 In memory this package is 0-based with -1 as the boundary tag of `cell_neighbors` (fem.Mesh).
 """
@@ -86,4 +88,61 @@ def save_pcg_iters(iters, root_fname: str, ndom: int, tag: str, nreals: int, dat
     `precond="A_GG"`: Example07:423-424, `data/$root_fname.A_GG_ndom$ndom_$tag.pcg-iters.nreals$nreals.npz`."""
     path = os.path.join(data_dir, f"{root_fname}.{precond}_ndom{ndom}_{tag}.pcg-iters.nreals{nreals}.npz")
     _write(path, np.asarray(iters, dtype=np.int64))
+    return path
+
+
+def _julia_float(v: float) -> str:
+    """How Julia interpolates a Float64 into a string (`"$v"`): the shortest digits that round-trip, always with a decimal
+    point (1.0, 0.1); exponent form (`1.0e-5`, `1.0e6`) below 1e-4 and from 1e6."""
+    v = float(v)
+    if v != v:
+        return "NaN"
+    if v in (float("inf"), float("-inf")):
+        return "Inf" if v > 0 else "-Inf"
+    r = repr(v)
+    if "e" in r:
+        mant, exp = r.split("e")
+        e = int(exp)
+    elif abs(v) >= 1e6:
+        sign = "-" if r.startswith("-") else ""
+        whole, frac = r.lstrip("-").split(".")
+        e = len(whole) - 1
+        digits = (whole + frac).rstrip("0") or "0"
+        mant = sign + digits[0] + "." + (digits[1:] or "0")
+    else:
+        return r
+    if "." not in mant:
+        mant += ".0"
+    return f"{mant}e{e}"
+
+
+def get_root_filename(model: str, sig2: float, L: float, nnode: int) -> str:
+    """`get_root_filename(model, sig2, L, nnode)` (KarhunenLoeveDomainDecompositionHelper.jl:72-80):
+    "SExp_sig21.0_L0.1_DoF4000"."""
+    return f"{model}_sig2{_julia_float(sig2)}_L{_julia_float(L)}_DoF{int(nnode)}"
+
+
+def kl_paths(root_fname: str, data_dir: str = "data"):
+    root = os.path.join(data_dir, root_fname)
+    return f"{root}.kl-eigvals.npz", f"{root}.kl-eigvecs.npz"
+
+
+def save_kl(Λ, Ψ, root_fname: str, data_dir: str = "data"):
+    """Example02:41-42 / Example04:92-93: `npzwrite("data/$root_fname.kl-eigvals.npz", Λ)` and `.kl-eigvecs.npz` (nnode x nvec)."""
+    pv, pe = kl_paths(root_fname, data_dir)
+    _write(pv, np.asarray(Λ, dtype=np.float64))
+    _write(pe, np.asarray(Ψ, dtype=np.float64))
+    return pv, pe
+
+
+def load_kl(root_fname: str, data_dir: str = "data"):
+    """The inverse of save_kl -> (Λ, Ψ), as Example07:124-125 reads them with `npzread`."""
+    pv, pe = kl_paths(root_fname, data_dir)
+    return np.load(pv).astype(np.float64).ravel(), np.asfortranarray(np.load(pe).astype(np.float64))
+
+
+def save_greal(g, root_fname: str, data_dir: str = "data") -> str:
+    """Example02:46 / Example04:100: `data/$root_fname.greal.npz`, one realization on the mesh nodes."""
+    path = os.path.join(data_dir, f"{root_fname}.greal.npz")
+    _write(path, np.asarray(g, dtype=np.float64))
     return path
