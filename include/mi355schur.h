@@ -210,6 +210,49 @@ int mi_amg_create(mi_ctx_t ctx, int64_t nlevels, const int64_t *n_l, const int64
                   const double *const *a_val, const int64_t *const *p_rowptr, const int64_t *const *p_colidx, const double *const *p_val,
                   const double *omega_over_d, const double *coarse_inv, int index_base, mi_op_t *op);
 int mi_amg_stats(mi_op_t op, int64_t *n_levels, int64_t *coarse_n, int64_t *operator_nnz, int64_t *bytes_kept);
+/* mi_amg_plan_create / mi_amg_set_values — the same operator with the NUMBERS of the hierarchy made on the device, for the
+ * studies that rebuild `AMGPreconditioner{SmoothedAggregation}(A)` per realization (`Π_amg_t` of Example06:167-182;
+ * Example12:106, Example14:153, Example19:101, Example20:111; the `Π_IId` of Example07:174). The aggregation sees the values
+ * of a matrix only through `!= 0`, so on one mesh every realization has the aggregates — and every sparsity pattern of the
+ * hierarchy — of the first; the symbolic part is done once on the host (amg_plan.hpp), the numeric chain per nzval on the
+ * device (amg_setup.hpp): g_l, ω_l = 4 / (3 g_l), ω_l / d, P_l = (I - ω_l D^-1 A_l) T_l, R_l = P_l', A_{l+1} = sym(R_l A_l P_l) on
+ * the STRUCTURAL product patterns (no entry is dropped because it cancels), and the dense inverse of the last level by the
+ * SPD route of mi_nn_pinv with its certificate. No atomics, every sum in a fixed order: two refreshes give the same bits.
+ *   create    : HOST arrays, `index_base`-based. rowptr (n + 1) / colidx / val: the CSR of A_0, rows sorted without
+ *               duplicates, stored zeros are entries; n_l[nlevels]: rows per level; agg[l] (l < nlevels - 1, n_l[l] entries):
+ *               the aggregate of every node, in index_base .. index_base + n_l[l+1] - 1 (fem.prepare_amg_precond(A).agg).
+ *               The result is an AMG operator like that of mi_amg_create (apply, solvers, mi_amg_stats).
+ *               MI_ERR_BAD_ARG, the message naming the numbers: a pattern that is not sorted, has duplicates or is not
+ *               structurally symmetric; an aggregate id out of range; an empty aggregate; level sizes that do not chain; a
+ *               coarsest level above 4096 rows; a context that is one rank of several.
+ *   set_values: new `val` on the pattern of create (a new realization), host or device pointer per the context's pointer
+ *               mode. Synchronous. MI_ERR_BAD_ARG on an operator of mi_amg_create.
+ *   Both return MI_ERR_SINGULAR when a diagonal entry of a level is missing or not positive, a value is not finite, or the
+ *   certificate of the coarse inverse fails; set_values then keeps the previous hierarchy: new values are computed into a
+ *   second set of buffers and committed by device copies, the addresses the cycle and captured solve graphs read never change.
+ *   Limit: the aggregates are those handed to create. A later matrix with a different set of stored non-zeros gets a valid
+ *   hierarchy, but not the one a fresh host set-up would build.
+ * mi_amg_stats of such an operator: bytes_kept additionally counts the plan and the second buffers,
+ *   Σ_levels 4 (2 n_l + 2 nnz(A_l) + 1) + Σ_{l < nlevels-1} [4 (4 nnz(P_l) + nnz(A_l) + nnz(A_l P_l) + 3 n_l + n_{l+1} + 4) + 8 n_{l+1}]   (the plan)
+ *   + Σ_{l >= 1} 8 nnz(A_l) + Σ_{l < nlevels-1} (16 nnz(P_l) + 8 n_l) + 8 (max_l nnz(A_l P_l) + max_{l >= 1} nnz(A_l)) + 32 n_c²
+ *   + 12 nnz(A_{nlevels-1})   (candidates, product work, dense work, and the coarsest matrix kept for the read-back).
+ * Read-back (operators of either create route; HOST arrays, 0-based; any output pointer may be NULL):
+ *   mi_amg_level_sizes: rows of `level`, rows of the next (0 on the last level), nnz(A_level), nnz(P_level) (0 on the last)
+ *   mi_amg_level_get  : CSR of A_level (n + 1, nnz, nnz) and of P_level, ω_level (one double) and ω_level / d (n doubles);
+ *                       the P, ω outputs are left alone on the last level. An operator of mi_amg_create was given ω/d only:
+ *                       its ω_level is (ω/d)_0 a_00, one rounding away.
+ *   mi_amg_coarse_inverse: the n_c x n_c inverse of the last level, column-major.
+ * mi_amg_refresh_profile — diagnostic (operators of mi_amg_plan_create): one refresh on the values the operator holds, timed
+ *   by HIP events on the context's stream; ms[6] = Gershgorin bound and ω; prolongator and R; A P; R (A P) and its
+ *   symmetrisation; the coarsest level (scatter, inverse, certificate, with their host synchronisations); the commit copies. */
+int mi_amg_plan_create(mi_ctx_t ctx, int64_t n, const int64_t *rowptr, const int64_t *colidx, const double *val, int64_t nlevels,
+                       const int64_t *n_l, const int64_t *const *agg /* [nlevels - 1] */, int index_base, mi_op_t *op);
+int mi_amg_set_values(mi_op_t op, const double *val);
+int mi_amg_level_sizes(mi_op_t op, int64_t level, int64_t *n_rows, int64_t *n_cols, int64_t *a_nnz, int64_t *p_nnz);
+int mi_amg_level_get(mi_op_t op, int64_t level, int64_t *a_rowptr, int64_t *a_colidx, double *a_val, int64_t *p_rowptr,
+                     int64_t *p_colidx, double *p_val, double *omega, double *omega_over_d);
+int mi_amg_coarse_inverse(mi_op_t op, double *coarse_inv);
+int mi_amg_refresh_profile(mi_op_t op, double *ms /* 6 */);
 
 /* mi_schur_assembled_create — `apply_local_schurs(Sd, ind_Γd_Γ2l, node_Γ_cnt, x)`, EPDD.jl:761-785:
  * Sx = Σ_d R_d' S_d R_d x with dense local Schur complements.

@@ -57,6 +57,12 @@ SIGNATURES = {
     "mi_block_jacobi_stats": [vp, i64p, i64p, i64p, i64p],
     "mi_amg_create": [vp, i64, i64p, i64pp, i64pp, f64pp, i64pp, i64pp, f64pp, f64p, f64p, C.c_int, C.POINTER(vp)],
     "mi_amg_stats": [vp, i64p, i64p, i64p, i64p],
+    "mi_amg_plan_create": [vp, i64, i64p, i64p, f64p, i64, i64p, i64pp, C.c_int, C.POINTER(vp)],
+    "mi_amg_set_values": [vp, vp],
+    "mi_amg_level_sizes": [vp, i64, i64p, i64p, i64p, i64p],
+    "mi_amg_level_get": [vp, i64, i64p, i64p, f64p, i64p, i64p, f64p, f64p, f64p],
+    "mi_amg_coarse_inverse": [vp, f64p],
+    "mi_amg_refresh_profile": [vp, f64p],
     "mi_schur_assembled_create": [vp, i64, i64, i64p, i64pp, f64pp, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_nn_create": [vp, i64, i64, i64p, i64pp, f64pp, i64p, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_nn_create_stored": [vp, i64, i64, i64p, i64pp, f64pp, i64p, C.c_int, i64, i64, C.c_int, C.POINTER(vp)],

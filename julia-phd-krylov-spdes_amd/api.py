@@ -497,10 +497,47 @@ class AMGPreconditioner(Operator):
     smoothed-aggregation AMG. `A_or_hierarchy`: a scipy sparse matrix — the set-up then runs here, on the host, with
     `fem.prepare_amg_precond(A, **kw)` (`max_levels`, `max_coarse`) — or a `fem.AmgHierarchy` built before. Usable as `M`
     of pcg / defpcg / eigpcg / eigdefpcg / initpcg and through `M * r`. Deviation from the reference: damped Jacobi where it
-    smooths with symmetric Gauss-Seidel. A new matrix needs a new object (no set_values)."""
+    smooths with symmetric Gauss-Seidel.
 
-    def __init__(self, ctx: Context, A_or_hierarchy, index_base: int = 0, **kw):
+    `device_setup=True` (a matrix, not a hierarchy): `fem.prepare_amg_precond(A, **kw)` runs once, for the aggregates
+    alone; the numbers of the hierarchy are made on the device (`mi_amg_plan_create`), and `.set_values(A_or_nzval)` redoes
+    them for a new realization on the same pattern — the per-realization `Π_amg_t` of Example06:167-182 without a host
+    set-up. The aggregates stay those of the first matrix: a later matrix with a different set of stored non-zeros gets
+    a valid hierarchy, but not the one a fresh set-up would build. `aggregates=[agg_0, …]` (one 0-based array per smoothed
+    level) skips the host set-up and freezes aggregates from elsewhere. Without `device_setup` a new matrix needs a new object.
+    `.device_hierarchy()` reads the hierarchy back from the device (either kind)."""
+
+    def __init__(self, ctx: Context, A_or_hierarchy, index_base: int = 0, device_setup: bool = False, **kw):
         H = A_or_hierarchy
+        self.nnz = None
+        if device_setup:
+            if not (sp.issparse(H) or isinstance(H, np.ndarray)):
+                raise TypeError("device_setup=True takes the matrix, not a hierarchy that is already built")
+            from . import fem
+            A = sp.csr_matrix(H)
+            A.sum_duplicates()
+            A.sort_indices()
+            if "aggregates" in kw:        # frozen aggregates from elsewhere: one 0-based array per smoothed level
+                H = None
+                agg0 = [_i64(a).ravel() for a in kw.pop("aggregates")]
+                if kw:
+                    raise TypeError(f"set-up options {sorted(kw)} with aggregates that are already chosen")
+                sizes = [A.shape[0]] + [int(a.max()) + 1 if a.size else 0 for a in agg0]
+            else:
+                H = fem.prepare_amg_precond(A, **kw)
+                agg0, sizes = H.agg, H.sizes
+            aggs = [_i64(a) + index_base for a in agg0]
+            n_l = _i64(sizes)
+            ptr, idx, val = _i64(A.indptr) + index_base, _i64(A.indices) + index_base, _f64(A.data)
+            h = vp()
+            check(ctx._L.mi_amg_plan_create(ctx._h, i64(A.shape[0]), ptr.ctypes.data_as(i64p), idx.ctypes.data_as(i64p),
+                                            val.ctypes.data_as(f64p), i64(len(sizes)), n_l.ctypes.data_as(i64p),
+                                            _ptrs(aggs, i64p) if aggs else None, C.c_int(index_base), C.byref(h)))
+            super().__init__(ctx, h)
+            self.hierarchy = H            # of the matrix given here (None with `aggregates`); later values live on the device only
+            self.aggregates = list(agg0)
+            self.nnz = int(val.size)
+            return
         if sp.issparse(H) or isinstance(H, np.ndarray):
             from . import fem
             H = fem.prepare_amg_precond(sp.csr_matrix(H), **kw)
@@ -531,6 +568,59 @@ class AMGPreconditioner(Operator):
                                    inv.ctypes.data_as(f64p), C.c_int(index_base), C.byref(h)))
         super().__init__(ctx, h)
         self.hierarchy = H
+
+    def set_values(self, A_or_nzval) -> None:
+        """A new realization on the pattern of construction: a scipy sparse matrix, or its CSR values (sorted rows) as a numpy
+        array or a torch CUDA tensor (`mi_amg_set_values`): the numeric chain of the hierarchy runs again on the device.
+        Synchronous. MiError(MI_ERR_SINGULAR) — a diagonal entry of a level that is not positive, a value that is not finite,
+        a coarse inverse that fails its certificate — leaves the previous hierarchy in place. Needs `device_setup=True`."""
+        if self.nnz is None:
+            raise TypeError("set_values needs AMGPreconditioner(ctx, A, device_setup=True); this hierarchy came from the host")
+        v = A_or_nzval
+        if sp.issparse(v):
+            v = sp.csr_matrix(v)
+            v.sum_duplicates()
+            v.sort_indices()
+            v = _f64(v.data)
+        self.ctx._mode_for(v)
+        k, p = self.ctx._ptr(v, self.nnz)
+        self.ctx._order((k,), after=False)
+        check(self.ctx._L.mi_amg_set_values(self._h, p))   # synchronous
+
+    def refresh_profile(self) -> dict:
+        """Milliseconds of the kernel groups of one refresh on the values held (`mi_amg_refresh_profile`, HIP events)."""
+        ms = np.zeros(6)
+        check(self.ctx._L.mi_amg_refresh_profile(self._h, ms.ctypes.data_as(f64p)))
+        return dict(zip(("gershgorin_omega", "prolongator_R", "A_P", "R_AP_sym", "coarse_inverse", "commit"), (float(v) for v in ms)))
+
+    def device_hierarchy(self):
+        """The hierarchy as the device holds it, a `fem.AmgHierarchy` (`mi_amg_level_sizes`, `mi_amg_level_get`,
+        `mi_amg_coarse_inverse`). `agg` is that of construction when known."""
+        from . import fem
+        L = self.ctx._L
+        st = self.stats()
+        As, Ps, om, owd = [], [], [], []
+        for l in range(st["n_levels"]):
+            n, m, an, pn = i64(), i64(), i64(), i64()
+            check(L.mi_amg_level_sizes(self._h, i64(l), C.byref(n), C.byref(m), C.byref(an), C.byref(pn)))
+            n, m, an, pn = int(n.value), int(m.value), int(an.value), int(pn.value)
+            last = l == st["n_levels"] - 1
+            ap, ai, av = np.zeros(n + 1, dtype=np.int64), np.zeros(an, dtype=np.int64), np.zeros(an)
+            pp, pi, pv = np.zeros(n + 1, dtype=np.int64), np.zeros(pn, dtype=np.int64), np.zeros(pn)
+            w, wd = C.c_double(0.0), np.zeros(n)
+            check(L.mi_amg_level_get(self._h, i64(l), ap.ctypes.data_as(i64p), ai.ctypes.data_as(i64p), av.ctypes.data_as(f64p),
+                                     pp.ctypes.data_as(i64p), pi.ctypes.data_as(i64p), pv.ctypes.data_as(f64p), C.byref(w),
+                                     wd.ctypes.data_as(f64p)))   # (the P, ω outputs are left alone on the last level)
+            As.append(sp.csr_matrix((av, ai, ap), shape=(n, n)))
+            if not last:
+                Ps.append(sp.csr_matrix((pv, pi, pp), shape=(n, m)))
+                om.append(float(w.value)); owd.append(wd)
+        nc = st["coarse_n"]
+        inv = np.zeros((nc, nc), order="F")
+        check(L.mi_amg_coarse_inverse(self._h, inv.ctypes.data_as(f64p)))
+        nnz = [a.indices.size for a in As]
+        return fem.AmgHierarchy(As, Ps, om, owd, inv, [a.shape[0] for a in As], float(sum(nnz)) / float(nnz[0]),
+                                getattr(self, "aggregates", None) or getattr(self.hierarchy, "agg", None))
 
     def stats(self):
         """dict(n_levels, coarse_n, operator_nnz, bytes_kept) (`mi_amg_stats`)"""

@@ -1,7 +1,8 @@
 // Smoothed-aggregation AMG preconditioner on the full system: the reference's `AMGPreconditioner{SmoothedAggregation}(A)`
 // (Preconditioners.jl), the M of `pcg(A, b, 0, Π_amg)` in Example01:49-61 / Example10 and of Examples 06, 09, 12-20.
 // The hierarchy (A_l, P_l, ω_l / diag(A_l), the dense inverse of the coarsest level) is built on the host once per matrix
-// (fem.prepare_amg_precond); this file holds the V(1,1) cycle. Deviation from the reference: its smoother is symmetric
+// (fem.prepare_amg_precond), or its numbers are redone on the device for every new realization on frozen aggregates
+// (amg_setup.hpp, mi_amg_plan_create / mi_amg_set_values); this file holds the V(1,1) cycle. Deviation from the reference: its smoother is symmetric
 // Gauss-Seidel, a sequential sweep with no bit-reproducible device form; here one pre- and one post-sweep of Jacobi damped
 // by ω_l = 4 / (3 g_l), g_l the Gershgorin bound on ρ(D^-1 A_l) — the cycle is symmetric, so M is SPD.
 //
@@ -128,6 +129,50 @@ struct AmgOp : Operator {
   DevBuf<double> zinv, sink_x, sink_r;
   int nlev = 0, nc = 0;
   int64_t op_nnz = 0, kept = 0, alg = 0, dom = 0;
+  HostCsr coarse_h;   // A of the coarsest level as given (the cycle needs only its inverse): read back by mi_amg_level_get
+  std::vector<double> omega_h;   // ω_l of the smoothed levels, for the read-back. mi_amg_create is given ω/d only: there ω_l is
+                                 // recovered as (ω/d)_0 a_00, one rounding away (NaN without a stored a_00)
+
+  // Read-back of one level (mi_amg_level_sizes / mi_amg_level_get): HOST arrays, 0-based, any pointer may be NULL.
+  void level_sizes(int l, int64_t *nr, int64_t *ncol, int64_t *a_nnz, int64_t *p_nnz) const {
+    const Level &L = lv[(size_t)l];
+    const bool host_a = l == nlev - 1 && L.A.n_rows == 0;
+    if (nr) *nr = L.n;
+    if (ncol) *ncol = l < nlev - 1 ? lv[(size_t)l + 1].n : 0;
+    if (a_nnz) *a_nnz = host_a ? coarse_h.nnz() : L.A.nnz;
+    if (p_nnz) *p_nnz = l < nlev - 1 ? L.P.nnz : 0;
+  }
+  void level_get(int l, int64_t *a_ptr, int64_t *a_col, double *a_val, int64_t *p_ptr, int64_t *p_col, double *p_val, double *omega, double *wd_out) {
+    hipStream_t s = ctx->stream;
+    Level &L = lv[(size_t)l];
+    auto ints = [&](const int *dev, size_t cnt, int64_t *out) {
+      if (!out || !cnt) return;
+      std::vector<int> h(cnt);
+      MI_HIP(hipMemcpyAsync(h.data(), dev, cnt * sizeof(int), hipMemcpyDeviceToHost, s));
+      MI_HIP(hipStreamSynchronize(s));
+      for (size_t k = 0; k < cnt; ++k) out[k] = h[k];
+    };
+    auto vals = [&](const double *dev, size_t cnt, double *out) {
+      if (!out || !cnt) return;
+      MI_HIP(hipMemcpyAsync(out, dev, cnt * sizeof(double), hipMemcpyDeviceToHost, s));
+      MI_HIP(hipStreamSynchronize(s));
+    };
+    auto csr = [&](const CsrDev &M, int64_t *ptr, int64_t *col, double *val) {
+      ints(M.rowptr.p, (size_t)M.n_rows + 1, ptr); ints(M.col.p, (size_t)M.nnz, col); vals(M.val.p, (size_t)M.nnz, val);
+    };
+    if (l == nlev - 1 && L.A.n_rows == 0) {
+      if (a_ptr) std::copy(coarse_h.rowptr.begin(), coarse_h.rowptr.end(), a_ptr);
+      if (a_col) std::copy(coarse_h.col.begin(), coarse_h.col.end(), a_col);
+      if (a_val) std::copy(coarse_h.val.begin(), coarse_h.val.end(), a_val);
+    } else csr(L.A, a_ptr, a_col, a_val);
+    if (l == nlev - 1) return;
+    csr(L.P, p_ptr, p_col, p_val);
+    if (omega) *omega = omega_h[(size_t)l];
+    vals(L.wd.p, (size_t)L.n, wd_out);
+  }
+
+  // for amg_setup.hpp (mi_amg_plan_create), which fills the levels itself
+  AmgOp(mi_ctx_s *c, int64_t n0) : Operator(c, n0) {}
 
   static void check_finite(const char *me, const char *what, int l, const double *v, size_t cnt) {
     for (size_t k = 0; k < cnt; ++k)
@@ -161,7 +206,7 @@ struct AmgOp : Operator {
       const HostCsr ha = host_csr(L.n, L.n, a_rowptr[l], a_colidx[l], a_val[l], base);
       check_finite(me, "A", l, ha.val.data(), ha.val.size());
       op_nnz += ha.nnz();
-      if (l == nlev - 1) break;
+      if (l == nlev - 1) { coarse_h = ha; break; }
       const int n1 = (int)n_l[l + 1];
       if (!p_rowptr[l]) raise(MI_ERR_BAD_ARG, "%s: P of level %d is NULL", me, l);
       HostCsr hp;
@@ -175,6 +220,12 @@ struct AmgOp : Operator {
       check_finite(me, "omega_over_d", l, omega_over_d + woff, (size_t)L.n);
       L.A.upload(ha, s); L.P.upload(hp, s); L.R.upload(transpose(hp), s);
       L.wd.upload(omega_over_d + woff, (size_t)L.n, s);
+      {
+        double a00 = std::numeric_limits<double>::quiet_NaN();
+        for (int k = ha.rowptr[0]; k < ha.rowptr[1]; ++k)
+          if (ha.col[(size_t)k] == 0) a00 = ha.val[(size_t)k];
+        omega_h.push_back(omega_over_d[woff] * a00);
+      }
       MI_HIP(hipStreamSynchronize(s));
       woff += (size_t)L.n;
       kept += 12 * ha.nnz() + 24 * hp.nnz() + 8 * (int64_t)L.n;
@@ -187,7 +238,10 @@ struct AmgOp : Operator {
     kept += 8 * (int64_t)nc * nc;
     alg += 8 * (int64_t)nc * nc + 16 * (int64_t)nc;
     if (nlev == 1) dom = alg;
-    // level vectors, once: nothing is allocated in apply
+    alloc_vectors();
+  }
+  // level vectors, once: nothing is allocated in apply
+  void alloc_vectors() {
     for (int l = 0; l < nlev; ++l) {
       Level &L = lv[(size_t)l];
       const size_t m = (size_t)L.n + 1;

@@ -12,6 +12,7 @@
 #include "nn_induced.hpp"
 #include "block_jacobi.hpp"
 #include "amg.hpp"
+#include "amg_setup.hpp"
 #include "kl.hpp"
 
 namespace mi {
@@ -599,6 +600,66 @@ int mi_amg_stats(mi_op_t op, int64_t *n_levels, int64_t *coarse_n, int64_t *oper
   if (operator_nnz) *operator_nnz = m->op_nnz;
   if (bytes_kept) *bytes_kept = m->kept;
   return MI_OK;
+}
+int mi_amg_plan_create(mi_ctx_t ctx, int64_t n, const int64_t *rowptr, const int64_t *colidx, const double *val, int64_t nlevels,
+                       const int64_t *n_l, const int64_t *const *agg, int index_base, mi_op_t *op) {
+  if (op) *op = nullptr;
+  if (!val) return fail(MI_ERR_BAD_ARG, "mi_amg_plan_create: val is NULL");
+  MI_NEW_OP(ctx, op, new AmgPlanOp(ctx, n, rowptr, colidx, val, nlevels, n_l, agg, index_base));
+}
+int mi_amg_set_values(mi_op_t op, const double *val) {
+  AmgPlanOp *m = op && op->impl ? dynamic_cast<AmgPlanOp *>(op->impl.get()) : nullptr;
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s", as_amg(op) ?"mi_amg_set_values: the hierarchy of this operator came from the host (mi_amg_create); only an "
+                                                   "operator of mi_amg_plan_create can redo it"
+                                                 : "mi_amg_set_values: not an AMG preconditioner");
+  if (!val) return fail(MI_ERR_BAD_ARG, "mi_amg_set_values: val is NULL");
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    In vi(c, val, (size_t)m->nnz0, m->stage);
+    m->refresh(vi.dev, "mi_amg_set_values");   // synchronous: a matrix that is not positive definite is reported here
+    return MI_OK;
+  });
+}
+int mi_amg_refresh_profile(mi_op_t op, double *ms) {
+  AmgPlanOp *m = op && op->impl ? dynamic_cast<AmgPlanOp *>(op->impl.get()) : nullptr;
+  if (!m || !ms) return fail(MI_ERR_BAD_ARG, "mi_amg_refresh_profile: not an operator of mi_amg_plan_create, or NULL ms");
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    m->profile(ms);
+    return MI_OK;
+  });
+}
+int mi_amg_level_sizes(mi_op_t op, int64_t level, int64_t *n_rows, int64_t *n_cols, int64_t *a_nnz, int64_t *p_nnz) {
+  AmgOp *m = as_amg(op);
+  if (!m) return fail(MI_ERR_BAD_ARG, "mi_amg_level_sizes: not an AMG preconditioner");
+  if (level < 0 || level >= m->nlev) return fail(MI_ERR_BAD_ARG, "mi_amg_level_sizes: level = %lld of %d levels", (long long)level, m->nlev);
+  m->level_sizes((int)level, n_rows, n_cols, a_nnz, p_nnz);
+  return MI_OK;
+}
+int mi_amg_level_get(mi_op_t op, int64_t level, int64_t *a_rowptr, int64_t *a_colidx, double *a_val, int64_t *p_rowptr, int64_t *p_colidx,
+                     double *p_val, double *omega, double *omega_over_d) {
+  AmgOp *m = as_amg(op);
+  if (!m) return fail(MI_ERR_BAD_ARG, "mi_amg_level_get: not an AMG preconditioner");
+  if (level < 0 || level >= m->nlev) return fail(MI_ERR_BAD_ARG, "mi_amg_level_get: level = %lld of %d levels", (long long)level, m->nlev);
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    m->level_get((int)level, a_rowptr, a_colidx, a_val, p_rowptr, p_colidx, p_val, omega, omega_over_d);
+    return MI_OK;
+  });
+}
+int mi_amg_coarse_inverse(mi_op_t op, double *coarse_inv) {
+  AmgOp *m = as_amg(op);
+  if (!m || !coarse_inv) return fail(MI_ERR_BAD_ARG, "mi_amg_coarse_inverse: not an AMG preconditioner, or NULL coarse_inv");
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    MI_HIP(hipMemcpyAsync(coarse_inv, m->zinv.p, sizeof(double) * (size_t)m->nc * m->nc, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    return MI_OK;
+  });
 }
 
 // new values of the stacked A_IΓ blocks of either operator on the interior/Γ split (host or device pointer)

@@ -925,6 +925,7 @@ class AmgHierarchy:
     coarse_inv: np.ndarray            # n_c x n_c, symmetric, column-major
     sizes: List[int]                  # [nlevels] n_l
     operator_complexity: float        # Σ_l nnz(A_l) / nnz(A_0)
+    agg: Optional[List[np.ndarray]] = None   # [nlevels - 1] aggregate of every node of level l, 0-based (`amg_refresh`, the device set-up)
 
     @property
     def nlevels(self) -> int:
@@ -1004,7 +1005,7 @@ def prepare_amg_precond(A, max_levels: int = 10, max_coarse: int = 256) -> AmgHi
         raise ValueError(f"max_levels = {max_levels} (at least 1)")
     if not np.isfinite(A0.data).all():
         raise ValueError("the matrix holds a value that is not finite")
-    As, Ps, om, owd = [A0], [], [], []
+    As, Ps, om, owd, aggs = [A0], [], [], [], []
     while len(As) < max_levels and As[-1].shape[0] > max_coarse:
         Al = As[-1]
         n = Al.shape[0]
@@ -1024,7 +1025,7 @@ def prepare_amg_precond(A, max_levels: int = 10, max_coarse: int = 256) -> AmgHi
         P = _amg_sorted_csr(T - sp.diags(wd) @ (Al @ T))
         M = (P.T @ Al @ P).tocsr()
         As.append(_amg_sorted_csr((M + M.T) * 0.5))
-        Ps.append(P); om.append(w); owd.append(wd)
+        Ps.append(P); om.append(w); owd.append(wd); aggs.append(agg)
     nc = As[-1].shape[0]
     if nc > AMG_MAX_COARSE_ROWS:
         raise ValueError(f"the coarsest level holds {nc} rows, more than the {AMG_MAX_COARSE_ROWS} a dense inverse is kept for "
@@ -1035,7 +1036,79 @@ def prepare_amg_precond(A, max_levels: int = 10, max_coarse: int = 256) -> AmgHi
         raise ValueError("the coarsest level is singular")
     inv = np.asfortranarray((inv + inv.T) * 0.5)
     nnz = [a.nnz for a in As]
-    return AmgHierarchy(As, Ps, om, owd, inv, [a.shape[0] for a in As], float(sum(nnz)) / float(nnz[0]))
+    return AmgHierarchy(As, Ps, om, owd, inv, [a.shape[0] for a in As], float(sum(nnz)) / float(nnz[0]), aggs)
+
+
+def _amg_ones(M) -> sp.csr_matrix:
+    """the stored pattern of M as a matrix of ones (stored zeros are entries)"""
+    M = sp.csr_matrix(M)
+    return sp.csr_matrix((np.ones(M.indices.size), M.indices.copy(), M.indptr.copy()), shape=M.shape)
+
+
+def _amg_embed(V, S) -> sp.csr_matrix:
+    """The values of V on the stored pattern of S ⊇ pattern(V), zeros elsewhere; both sorted CSR."""
+    V, S = _amg_sorted_csr(V), _amg_sorted_csr(S)
+    key = lambda M: np.repeat(np.arange(M.shape[0], dtype=np.int64), np.diff(M.indptr)) * M.shape[1] + M.indices
+    kv, ks = key(V), key(S)
+    pos = np.searchsorted(ks, kv)
+    if kv.size and (pos.max(initial=0) >= ks.size or (ks[np.minimum(pos, ks.size - 1)] != kv).any()):
+        raise ValueError("a computed entry lies outside the structural pattern")
+    data = np.zeros(ks.size)
+    data[pos] = V.data
+    return sp.csr_matrix((data, S.indices.copy(), S.indptr.copy()), shape=S.shape)
+
+
+def amg_refresh(H_or_aggs, A) -> AmgHierarchy:
+    """The numeric chain of `prepare_amg_precond` for a new matrix `A` on FROZEN aggregates — `H_or_aggs`: a hierarchy with
+    `.agg`, or the list of aggregate arrays itself (one per smoothed level, 0-based). The host restatement of the device
+    set-up (`api.AMGPreconditioner(ctx, A, device_setup=True).set_values`): the same arithmetic as `prepare_amg_precond`,
+    expression for expression, but on the STRUCTURAL patterns — P_l on pattern(T) ∪ pattern(A_l T), A_{l+1} on the pattern of
+    the all-ones product P_l' A_l P_l — where scipy drops an entry whose value cancels to exactly zero. `amg_aggregate` sees a
+    matrix only through `data != 0`, so for a matrix with the stored non-zeros of the one the aggregates came from, the
+    result equals `prepare_amg_precond(A)` wherever that stores an entry (tests/test_amg_refresh_cpu.py); for any other
+    matrix it is a valid hierarchy, but not the one a fresh set-up would build."""
+    aggs = H_or_aggs.agg if isinstance(H_or_aggs, AmgHierarchy) else H_or_aggs
+    if aggs is None:
+        raise ValueError("the hierarchy carries no aggregates (built by hand, or before `agg` existed)")
+    aggs = [np.asarray(a, dtype=np.int64).ravel() for a in aggs]
+    A0 = _amg_sorted_csr(A)
+    if A0.shape[0] != A0.shape[1] or A0.shape[0] == 0:
+        raise ValueError("square, non-empty matrix expected")
+    if not np.isfinite(A0.data).all():
+        raise ValueError("the matrix holds a value that is not finite")
+    As, Ps, om, owd = [A0], [], [], []
+    for l, agg in enumerate(aggs):
+        Al = As[-1]
+        n = Al.shape[0]
+        if agg.size != n:
+            raise ValueError(f"level {l}: {agg.size} aggregate ids for {n} rows")
+        d = Al.diagonal()
+        if not (d > 0).all():
+            raise ValueError(f"level {l}: a diagonal entry is not positive")
+        nc = int(agg.max()) + 1
+        cnt = np.bincount(agg, minlength=nc).astype(np.float64)
+        if agg.min() < 0 or not (cnt > 0).all():
+            raise ValueError(f"level {l}: a negative aggregate id or an empty aggregate")
+        T = sp.csr_matrix((1.0 / np.sqrt(cnt[agg]), (np.arange(n), agg)), shape=(n, nc))
+        g = float(np.max(np.asarray(abs(Al).sum(axis=1)).ravel() / d))
+        w = 4.0 / (3.0 * g)
+        wd = w / d
+        T1, A1 = _amg_ones(T), _amg_ones(Al)
+        P = _amg_embed(T - sp.diags(wd) @ (Al @ T), T1 + A1 @ T1)
+        M = (P.T @ Al @ P).tocsr()
+        P1 = _amg_ones(P)
+        As.append(_amg_embed((M + M.T) * 0.5, sp.csr_matrix(P1.T) @ (A1 @ P1)))
+        Ps.append(P); om.append(w); owd.append(wd)
+    nc = As[-1].shape[0]
+    if nc > AMG_MAX_COARSE_ROWS:
+        raise ValueError(f"the coarsest level holds {nc} rows, more than the {AMG_MAX_COARSE_ROWS} a dense inverse is kept for")
+    Ac = As[-1].toarray()
+    inv = np.linalg.inv((Ac + Ac.T) * 0.5)
+    if not np.isfinite(inv).all():
+        raise ValueError("the coarsest level is singular")
+    inv = np.asfortranarray((inv + inv.T) * 0.5)
+    nnz = [a.nnz for a in As]
+    return AmgHierarchy(As, Ps, om, owd, inv, [a.shape[0] for a in As], float(sum(nnz)) / float(nnz[0]), aggs)
 
 
 def get_schur_rhs(b_Id, A_IId, A_IΓd, b_Γ, gather_idx=None, solvers=None):

@@ -780,6 +780,31 @@ function MiAMGPreconditioner(ctx::MiContext, ml)
   MiAMGPreconditioner(ctx, A_l, P_l, wd, (Z + Z') / 2)
 end
 
+"""`MiAMGPreconditioner(ctx, A, agg; device_setup=true)`: the hierarchy's NUMBERS made on the device (`mi_amg_plan_create`) from
+the matrix and frozen aggregates — `agg[l][i]` ∈ 1:n_{l+1}, the aggregate of node i of level l, one vector per smoothed level
+(any standard aggregation of the first realization; the aggregation sees values only through `!= 0`, so it is the same for
+every realization on one mesh). `set_values!(Π, A)` then redoes them for a new realization on the same pattern — the
+per-realization `Π_amg_t = AMGPreconditioner{SmoothedAggregation}(A)` of Example06:182 without a host set-up. A symmetric
+`A` with sorted columns is its own CSR form."""
+function MiAMGPreconditioner(ctx::MiContext, A::SparseMatrixCSC{Float64,Int}, agg::Vector{Vector{Int}}; device_setup::Bool=true)
+  device_setup || throw(ArgumentError("without device_setup pass the hierarchy itself: MiAMGPreconditioner(ctx, A_l, P_l, omega_over_d, coarse_inv)"))
+  L = length(agg) + 1
+  n_l = Int64[A.n; [maximum(a) for a in agg]]
+  cp, rv = Vector{Int64}(A.colptr), Vector{Int64}(A.rowval)
+  ag = Vector{Int64}[Vector{Int64}(a) for a in agg]
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  GC.@preserve ag begin
+    check(ccall((:mi_amg_plan_create, lib), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Ptr{Int64}}, Cint, Ref{Ptr{Cvoid}}),
+                ctx.h, A.n, cp, rv, A.nzval, L, n_l, ptrs(ag), 1, r))
+  end
+  MiAMGPreconditioner(wrap(ctx, r), L)
+end
+"""`set_values!(Π, A)`: the values of `A` (same pattern as at creation) — a new realization (`mi_amg_set_values`); needs
+the `device_setup` constructor. A matrix that is not positive definite throws and leaves the previous hierarchy in place."""
+set_values!(Π::MiAMGPreconditioner, A::SparseMatrixCSC{Float64,Int}) =
+  check(ccall((:mi_amg_set_values, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), Π.op.h, A.nzval))
+
 function amg_stats(Π::MiAMGPreconditioner)
   a, b, c, d = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
   check(ccall((:mi_amg_stats, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), Π.op.h, a, b, c, d))
