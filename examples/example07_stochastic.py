@@ -27,7 +27,11 @@ reference) runs on the GPU: the index half is prepared once (`fem.make_assembly_
 `mi_assembly_run` (0.2 ms at 1 M DoF vs ~1-3 s for the host loop); the block values come back for the dense
 elimination that builds S_d.
 
-    python examples/example07_stochastic.py [--N 200 --px 4 --py 2 --nreals 20 --device-assembly]
+With --device-setup the dense elimination, the condensed rhs and NN_t run on the device too, and with --device-field the
+coefficient itself: one api.KLField keeps Ψ on the device, per realization only the latent vector ξ is uploaded and
+a = exp(g(ξ)) goes straight into the assembly (g has the bits of fem.draw's loop, so the iteration counts do not change).
+
+    python examples/example07_stochastic.py [--N 200 --px 4 --py 2 --nreals 20 --device-assembly --device-setup --device-field]
 """
 import argparse
 import os
@@ -52,6 +56,9 @@ def main():
     ap.add_argument("--device-setup", action="store_true",
                     help="with --device-assembly: S_d, the condensed rhs and NN_t on the device too (mi_schur_setup_run, mi_nn_pinv, "
                          "mi_dense_set_blocks): nothing of a realization's set-up runs on the host")
+    ap.add_argument("--device-field", action="store_true",
+                    help="with --device-setup: the coefficient itself on the device too (api.KLField): per realization only the latent "
+                         "vector ξ (m numbers) is uploaded, a = exp(g(ξ)) goes straight into the device assembly")
     ap.add_argument("--recycle", action="store_true")
     ap.add_argument("--nn-f32", action="store_true",
                     help="run the two solves of Example07:273-277 also with fp32-STORED Neumann-Neumann blocks (storage=\"f32\": "
@@ -74,7 +81,8 @@ def main():
     else:
         kl = fem.synthetic_kl(mesh.points)
     rng = np.random.default_rng(args.seed)
-    gs = [fem.draw(kl, rng)[1] for _ in range(args.nreals)]          # Example07:140-144: all draws up front
+    draws = [fem.draw(kl, rng) for _ in range(args.nreals)]          # Example07:140-144: all draws up front
+    ξs, gs = [d[0] for d in draws], [d[1] for d in draws]
 
     ctx = api.Context(int(os.environ.get("LOCAL_RANK", "0")))
     P0 = fem.build_schur_problem(args.N, args.px, args.py, np.exp(0 * gs[0]), f, uexact)   # ξ = 0 operator (:88-137)
@@ -97,6 +105,11 @@ def main():
         setup = api.SchurSetup(ctx, P0.A_IIdd, P0.A_IΓdd, P0.A_ΓΓdd)
         S_dev = api.LocalSchurs(ctx, P0.Sd, sub.gather_idx, sub.node_Γ_cnt)
         NN_dev = api.NeumannNeumannSchurPreconditioner(ctx, P0.ΠSd, sub.gather_idx, sub.node_Γ_cnt)
+    field = None
+    if args.device_field:
+        if not args.device_setup:
+            raise SystemExit("--device-field needs --device-assembly --device-setup")
+        field = api.KLField(ctx, kl.Λ, kl.Ψ)                 # Ψ crosses once; `set!(Λ, Ψ, ξ, g)` and exp.(g) per realization on the device
     ΠSnn_0_f32 = NN_dev_f32 = None
     if args.nn_f32:
         ΠSnn_0_f32 = api.NeumannNeumannSchurPreconditioner(ctx, P0.ΠSd, sub.gather_idx, sub.node_Γ_cnt, storage="f32")
@@ -117,7 +130,8 @@ def main():
     for ireal in range(rank, args.nreals, world):
         if setup is not None:
             # the whole realization on the device: element loop -> block values -> S_d, w_d -> operators refilled
-            vals = dev_plan.run(torch.from_numpy(np.exp(gs[ireal])).cuda())
+            a_t = field.coefficient(torch.from_numpy(ξs[ireal]).cuda()) if field is not None else torch.from_numpy(np.exp(gs[ireal])).cuda()
+            vals = dev_plan.run(a_t)
             ii, ig, gg, bI, bΓ = dev_plan.block_values(vals)
             Sd, w = setup.run(ii, ig, gg, bI)                                                          # :180-187
             S_dev.set_blocks(Sd)

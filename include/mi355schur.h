@@ -663,6 +663,53 @@ int mi_cov_tiling(int64_t nt, int64_t ns, int64_t m, int64_t *row_tile, int64_t 
 int mi_kl_cov_create(mi_ctx_t ctx, int model, double sig2, double L, int64_t n, const double *points, const int64_t *m_rowptr,
                      const int64_t *m_colidx, const double *m_val, mi_op_t *op);
 
+/* ---------------------------------------------------------------- realization sampler: latent vector -> field -> coefficient
+ * The step between the KL modes and the per-realization update (mi_assembly_run, mi_schur_setup_run, mi_amg_set_values): from a
+ * latent vector ξ to g = Σ_α sqrt(Λ_α) ξ_α Ψ[:, α] and a = exp(g), on the device (csrc/kl_field.hpp). It is the field half of
+ * `draw!(Λ, Ψ, ξ, g)` (KLDD.jl:1026-1044; the loop :1037-1040), of `set!(Λ, Ψ, ξ, g)` (KLDD.jl:1150-1164) and of the samplers'
+ * `draw!` / `set!` (Fem/Samplers.jl:62-87, 165-199); the random numbers stay with the caller (m per draw).
+ *
+ * mi_kl_field_create — the dense form on Ψ (n x m, column-major, ldpsi >= n) and Λ (m): HOST arrays, copied to the device once.
+ * mi_kl_field_create_dd — the factored form of `draw(mesh, Λ, Φ, Φd, inds_l2gd)` (KLDD.jl:850-883), which never forms Ψ:
+ *   g_i = (1 / cnt_i) Σ_{d ∋ i} Σ_α Φd[d][l, α] (Φ c)[off_d + α], c_γ = sqrt(Λ_γ) ξ_γ. n_d[d] nodes and md[d] local modes per
+ *   subdomain; inds_l2gd: the ndom local-to-global maps concatenated (Σ n_d entries, `index_base` 0 or 1); Phid: the ndom
+ *   column-major n_d x md_d blocks concatenated; Phi: (Σ md) x m column-major with ldphi >= Σ md. HOST arrays. It keeps
+ *   Σ n_d md_d + m Σ md numbers instead of n m. The sums run in a fixed order of their own (γ ascending, α ascending, owners in
+ *   ascending d, a true division by cnt_i), not in the reference's (idom, α, γ) nest: equal to it within rounding, not in bits.
+ * mi_kl_field_set — G[:, r] = field of the latent vector Ξ[:, r], A[:, r] = exp(G[:, r]), r < nreal. Ξ is m x nreal with
+ *   ldxi >= m, G and A are n x nreal with ldg, lda >= n, all column-major; either of G and A may be NULL, not both; only rows
+ *   [0, m) resp. [0, n) of a column are read resp. written. The three pointers follow the context's pointer mode. With device
+ *   pointers the call only enqueues kernels on the context's stream (all workspace was allocated at creation: no allocation, no
+ *   synchronisation, legal inside a stream capture), so it can stand directly in front of mi_assembly_run; with host pointers it
+ *   returns when G and A are complete. Up to 8 realizations share one pass over the modes; more run in blocks of 8.
+ *   Dense form: the modes are summed in ascending α, each term as acc + (sqrt(Λ_α) ξ_α) Ψ_iα (product, then sum, from +0), never
+ *   split: every column of G has the bits of the host loop, whatever nreal. exp is the device library's (1 ulp). No atomics:
+ *   equal calls give equal bits. A non-finite ξ is not an error (IEEE results).
+ * mi_kl_field_coords — `get_kl_coordinates(g, Λ, Ψ, M)` (KLDD.jl:1109-1124): ξ_α = (Σ_i Ψ[i, α] (M g)[i]) / sqrt(Λ_α). M is a
+ *   mi_csr_create operator (n x n, same context); g (n) and xi (m) follow the pointer mode; device pointers: asynchronous, no
+ *   allocation. The column sums are split over row blocks (a function of n and m only) and the partial sums added in ascending
+ *   order; the sum is divided once (the reference divides every term: a rounding difference). Dense form only, and m <= 524 280 (65 535 blocks of 8 modes).
+ * mi_kl_field_tiling — pure host function: nodes per workgroup, modes per LDS chunk, realizations per pass, and the number of
+ *   row splits of the coordinates launch for these sizes. Any output pointer may be NULL.
+ * mi_kl_field_stats — bytes the handle keeps on the device (without workspace), and the bytes one set of one realization with
+ *   one output streams.
+ * MI_ERR_BAD_ARG with a mi_last_error() text, nothing written: n, m or nreal < 1 (or above 2^30); a leading dimension below its
+ *   row count; a NULL required pointer, or G and A both NULL; a Λ_α that is negative or not finite (the reference's sqrt would
+ *   throw); Λ_α == 0 in mi_kl_field_coords only; md_d < 1 or n_d < 1; an index outside [0, n) after the base shift; a node
+ *   repeated within one subdomain; a node owned by no subdomain (the reference would divide by cnt = 0); an M that is not an
+ *   n x n sparse matrix; coordinates of a factored handle or of more than 524 280 modes; a context that is one rank of several. */
+typedef struct mi_kl_field_s *mi_kl_field_t;
+int mi_kl_field_create(mi_ctx_t ctx, int64_t n, int64_t m, const double *lambda, const double *Psi, int64_t ldpsi, mi_kl_field_t *field);
+int mi_kl_field_create_dd(mi_ctx_t ctx, int64_t n, int64_t m, const double *lambda, int64_t ndom, const int64_t *n_d, const int64_t *md,
+                          const int64_t *inds_l2gd, int index_base, const double *Phid, const double *Phi, int64_t ldphi,
+                          mi_kl_field_t *field);
+int mi_kl_field_set(mi_kl_field_t field, int64_t nreal, const double *Xi, int64_t ldxi, double *G, int64_t ldg, double *A, int64_t lda);
+int mi_kl_field_coords(mi_kl_field_t field, mi_op_t M, const double *g, double *xi);
+int mi_kl_field_tiling(int64_t n, int64_t m, int64_t nreal, int64_t *row_tile, int64_t *mode_chunk, int64_t *real_block,
+                       int64_t *coord_splits);
+int mi_kl_field_stats(mi_kl_field_t field, int64_t *bytes_kept, int64_t *bytes_per_set);
+int mi_kl_field_destroy(mi_kl_field_t field);
+
 /* ---------------------------------------------------------------- timing on the context's stream */
 int mi_event_create(mi_event_t *ev);
 int mi_event_record(mi_ctx_t ctx, mi_event_t ev);

@@ -134,6 +134,13 @@ SIGNATURES = {
     "mi_cov_apply": [vp, C.c_int, C.c_double, C.c_double, i64, vp, i64, vp, i64, vp, i64, vp, i64],
     "mi_cov_tiling": [i64, i64, i64, i64p, i64p, i64p, i64p],
     "mi_kl_cov_create": [vp, C.c_int, C.c_double, C.c_double, i64, f64p, i64p, i64p, f64p, C.POINTER(vp)],
+    "mi_kl_field_create": [vp, i64, i64, f64p, f64p, i64, C.POINTER(vp)],
+    "mi_kl_field_create_dd": [vp, i64, i64, f64p, i64, i64p, i64p, i64p, C.c_int, f64p, f64p, i64, C.POINTER(vp)],
+    "mi_kl_field_set": [vp, i64, vp, i64, vp, i64, vp, i64],
+    "mi_kl_field_coords": [vp, vp, vp, vp],
+    "mi_kl_field_tiling": [i64, i64, i64, i64p, i64p, i64p, i64p],
+    "mi_kl_field_stats": [vp, i64p, i64p],
+    "mi_kl_field_destroy": [vp],
     "mi_event_create": [C.POINTER(vp)],
     "mi_event_record": [vp, vp],
     "mi_event_elapsed_ms": [vp, vp, f64p],

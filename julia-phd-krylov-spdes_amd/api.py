@@ -1605,4 +1605,241 @@ def do_global_mass_covariance_reduced_assembly(ctx: Context, points, subdomains,
     return K
 
 
+# ------------------------------------------------------------------ realization sampler: ξ -> g -> a = exp(g)
+def kl_field_tiling(n: int, m: int, nreal: int = 1):
+    """`mi_kl_field_tiling` -> (row_tile, mode_chunk, real_block, coord_splits); a pure host function, no device needed."""
+    out = [i64() for _ in range(4)]
+    check(_lib.load().mi_kl_field_tiling(i64(n), i64(m), i64(nreal), *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+class KLField:
+    """Device form of the step from a latent vector to the field and the coefficient (`mi_kl_field_t`): `set(ξ)` is
+    `set!(Λ, Ψ, ξ, g)` (KLDD.jl:1150-1164) / the field half of `draw!` (KLDD.jl:1037-1040, Samplers.jl:64-67), `coefficient(ξ)`
+    is `exp.(g)`. `KLField(ctx, Λ, Ψ)` keeps Ψ (n x m) on the device; `KLField.from_dd` keeps the factors of
+    `draw(mesh, Λ, Φ, Φd, inds_l2gd)` (KLDD.jl:850-883) instead and never forms Ψ.
+
+    ξ is a vector (m,) or a panel Ξ (m, nreal); numpy in gives numpy out, a torch CUDA tensor in gives torch CUDA tensors out
+    with no host copy (the call is then asynchronous on the context's stream, ordered with torch's current stream)."""
+
+    def __init__(self, ctx: Context, Λ, Ψ):
+        Λ, Ψ = _f64(Λ), np.asfortranarray(Ψ, dtype=np.float64)
+        if Ψ.ndim != 2 or Ψ.shape[1] != Λ.size:
+            raise ValueError(f"Ψ is {Ψ.shape}, Λ has {Λ.size} entries")
+        h = vp()
+        check(ctx._L.mi_kl_field_create(ctx._h, i64(Ψ.shape[0]), i64(Λ.size), Λ.ctypes.data_as(f64p), Ψ.ctypes.data_as(f64p),
+                                        i64(Ψ.shape[0]), C.byref(h)))
+        self.ctx, self._h, self.n, self.m, self.factored = ctx, h, Ψ.shape[0], Λ.size, False
+
+    @classmethod
+    def from_dd(cls, ctx: Context, nnode: int, Λ, Φ, Φd, inds_l2gd, index_base: int = 0):
+        """`inds_l2gd` is 0-based whatever `index_base`: the base is added to the maps on the way to the C call and passed with
+        them, so `index_base=1` only sends the arrays as Julia would hold them (the tests use it to reach the C side's shift)."""
+        Λ, Φ = _f64(Λ), np.asfortranarray(Φ, dtype=np.float64)
+        blocks = [np.asfortranarray(P, dtype=np.float64) for P in Φd]
+        maps = [_i64(l2g) + index_base for l2g in inds_l2gd]
+        if len(blocks) != len(maps) or any(P.ndim != 2 or P.shape[0] != l.size for P, l in zip(blocks, maps)):
+            raise ValueError("Φd[d] must be n_d x md_d with n_d = len(inds_l2gd[d])")
+        n_d, md = _i64([P.shape[0] for P in blocks]), _i64([P.shape[1] for P in blocks])
+        if Φ.ndim != 2 or Φ.shape != (int(md.sum()), Λ.size):
+            raise ValueError(f"Φ is {Φ.shape}, expected {(int(md.sum()), Λ.size)}")
+        inds = _i64(np.concatenate(maps)) if maps else _i64([])
+        flat = _f64(np.concatenate([P.reshape(-1, order="F") for P in blocks])) if blocks else _f64([])
+        h = vp()
+        check(ctx._L.mi_kl_field_create_dd(ctx._h, i64(nnode), i64(Λ.size), Λ.ctypes.data_as(f64p), i64(len(blocks)), n_d.ctypes.data_as(i64p),
+                                           md.ctypes.data_as(i64p), inds.ctypes.data_as(i64p), C.c_int(index_base), flat.ctypes.data_as(f64p),
+                                           Φ.ctypes.data_as(f64p), i64(Φ.shape[0]), C.byref(h)))
+        self = cls.__new__(cls)
+        self.ctx, self._h, self.n, self.m, self.factored = ctx, h, int(nnode), Λ.size, True
+        return self
+
+    def _run(self, ξ, want_g: bool, want_a: bool):
+        ctx, n, m = self.ctx, self.n, self.m
+        if _is_torch(ξ):
+            import torch
+            if ξ.dtype != torch.float64 or not ξ.is_cuda:
+                raise TypeError("device latent vectors must be float64 CUDA tensors")
+            vec = ξ.dim() == 1
+            Ξ = ξ.reshape(m, 1) if vec else ξ
+            if Ξ.dim() != 2 or Ξ.shape[0] != m:
+                raise ValueError(f"ξ is {tuple(ξ.shape)}, expected ({m},) or ({m}, nreal)")
+            Ξt = Ξ.t().contiguous()                                    # row r = realization r: column-major (m, nreal)
+            nreal = Ξt.shape[0]
+            outs = [torch.empty((nreal, n), dtype=torch.float64, device=ξ.device) if w else None for w in (want_g, want_a)]
+            check(ctx._L.mi_ctx_set_pointer_mode(ctx._h, _lib.MI_PTR_DEVICE))
+            ctx._order((Ξt, *outs), after=False)
+            check(ctx._L.mi_kl_field_set(self._h, i64(nreal), vp(Ξt.data_ptr()), i64(m), *[x for o in outs for x in
+                                                                                         (vp(o.data_ptr()) if o is not None else None, i64(n))]))
+            ctx._order((Ξt, *outs), after=True)
+            return [None if o is None else (o[0] if vec else o.t()) for o in outs]
+        Ξ = np.asarray(ξ, dtype=np.float64)
+        vec = Ξ.ndim == 1
+        if Ξ.ndim not in (1, 2) or Ξ.shape[0] != m:
+            raise ValueError(f"ξ is {Ξ.shape}, expected ({m},) or ({m}, nreal)")
+        Ξ = np.asfortranarray(Ξ.reshape(m, -1))
+        nreal = Ξ.shape[1]
+        outs = [np.empty((n, nreal), order="F") if w else None for w in (want_g, want_a)]
+        check(ctx._L.mi_ctx_set_pointer_mode(ctx._h, _lib.MI_PTR_HOST))
+        check(ctx._L.mi_kl_field_set(self._h, i64(nreal), vp(Ξ.ctypes.data), i64(m), *[x for o in outs for x in
+                                                                                      (vp(o.ctypes.data) if o is not None else None, i64(n))]))
+        return [None if o is None else (o[:, 0].copy() if vec else o) for o in outs]
+
+    def set(self, ξ):
+        """g (n,) or G (n, nreal)"""
+        return self._run(ξ, True, False)[0]
+
+    def coefficient(self, ξ):
+        """a = exp(g)"""
+        return self._run(ξ, False, True)[1]
+
+    def set_and_coefficient(self, ξ):
+        """(g, a) from one pass over the modes"""
+        return tuple(self._run(ξ, True, True))
+
+    def coords(self, M: Operator, g):
+        """`get_kl_coordinates(g, Λ, Ψ, M)` (KLDD.jl:1109-1124); `M`: the mass matrix as `SparseMatrixCSC(ctx, M)`. Dense form only."""
+        ctx = self.ctx
+        ctx._mode_for(g)
+        kg, pg = ctx._ptr(g, self.n)
+        if _is_torch(g):
+            import torch
+            out = torch.empty(self.m, dtype=torch.float64, device=g.device)
+            po = vp(out.data_ptr())
+        else:
+            out = np.empty(self.m)
+            po = vp(out.ctypes.data)
+        ctx._order((kg, out), after=False)
+        check(ctx._L.mi_kl_field_coords(self._h, M._h, pg, po))
+        ctx._order((kg, out), after=True)
+        return out
+
+    def stats(self):
+        """{"bytes_kept", "bytes_per_set"}: what the handle keeps on the device, and what one set of one realization streams"""
+        a, b = i64(), i64()
+        check(self.ctx._L.mi_kl_field_stats(self._h, C.byref(a), C.byref(b)))
+        return {"bytes_kept": int(a.value), "bytes_per_set": int(b.value)}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self.ctx._L.mi_kl_field_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class McSampler:
+    """`McSampler` / `prepare_mc_sampler` / `draw!` / `set!` (Fem/Samplers.jl:1-87). Fields ξ, g, a = exp(g).
+
+    `rng` is a `numpy.random.Generator` (or anything with its `standard_normal(m)` and `random()`); the calls are, in order:
+    at construction `standard_normal(m)` for ξ; per `draw()` one `standard_normal(m)`.
+    With `field=None` the field is `fem.set_field` on the host (Ψ is needed then); with a `KLField` only ξ crosses to the
+    device and g, a come back as numpy arrays (Ψ may be None)."""
+
+    def __init__(self, Λ, Ψ, rng, field: Optional[KLField] = None):
+        self.Λ, self.Ψ, self.rng, self.field = _f64(Λ), Ψ, rng, field
+        self.m = self.Λ.size
+        if field is None and Ψ is None:
+            raise ValueError("either Ψ or a KLField is needed")
+        self.n = field.n if field is not None else np.asarray(Ψ).shape[0]
+        self._init_latent()
+        self._field()
+
+    def _init_latent(self):
+        self.ξ = np.asarray(self.rng.standard_normal(self.m), dtype=np.float64)
+
+    def _field(self):
+        if self.field is not None:
+            self.g, self.a = self.field.set_and_coefficient(self.ξ)
+        else:
+            from . import fem
+            self.g = fem.set_field(self.Λ, self.Ψ, self.ξ)
+            with np.errstate(over="ignore", invalid="ignore"):
+                self.a = np.exp(self.g)
+
+    def draw(self):
+        self.ξ = np.asarray(self.rng.standard_normal(self.m), dtype=np.float64)
+        self._field()
+
+    def set(self, ξ):
+        self.ξ = np.array(ξ, dtype=np.float64).reshape(self.m)
+        self._field()
+
+
+class McmcSampler(McSampler):
+    """`McmcSampler` / `prepare_mcmc_sampler` / `draw!` (Fem/Samplers.jl:93-199): random-walk Metropolis on ξ ~ N(0, σ² I) with
+    σ² = 1, proposal χ = ξ + ϑ N(0, I), ϑ² = 2.38² σ² / m; α = exp((‖ξ‖² − ‖χ‖²) / 2 / σ²) when ‖ξ‖² < ‖χ‖², else 1; proposals are
+    redrawn while u > α and the accepted χ becomes ξ. `draw()` returns cnt, the proposals made. Fields ξ, χ, g, a, σ2, ϑ2.
+
+    Calls of `rng`, in order: at construction `standard_normal(m)` for ξ, then `standard_normal(m)` for χ; per proposal
+    `standard_normal(m)`, then `random()` — so a scripted generator reproduces a chain."""
+
+    def _scale(self):
+        return self.m
+
+    def _init_latent(self):
+        self.σ2 = 1.0
+        self.ξ = np.sqrt(self.σ2) * np.asarray(self.rng.standard_normal(self.m), dtype=np.float64)
+        k = self._scale()
+        self.ϑ2 = 2.38 ** 2 * self.σ2 / k
+        self.χ = self.ξ[:k] + np.sqrt(self.ϑ2) * np.asarray(self.rng.standard_normal(k), dtype=np.float64)
+
+    def _metropolis(self, ξ):
+        """the loop of Samplers.jl:167-191 on the coordinates ξ -> (accepted χ, cnt)"""
+        sq_norm_of_ξ = float(ξ @ ξ)
+        cnt = 0
+        while True:
+            χ = ξ + np.sqrt(self.ϑ2) * np.asarray(self.rng.standard_normal(ξ.size), dtype=np.float64)
+            sq_norm_of_χ = float(χ @ χ)
+            cnt += 1
+            α = float(np.exp((sq_norm_of_ξ - sq_norm_of_χ) / 2 / self.σ2)) if sq_norm_of_ξ < sq_norm_of_χ else 1.0
+            u = float(self.rng.random())
+            if not u > α:
+                return χ, cnt
+
+    def draw(self) -> int:
+        self.χ, cnt = self._metropolis(self.ξ)
+        self.ξ = self.χ.copy()
+        self._field()
+        return cnt
+
+
+class HybridSampler(McmcSampler):
+    """`HybridSampler` / `prepare_hybrid_sampler` (Fem/Samplers.jl:208-274): Metropolis on the first m_mcmc coordinates
+    (ϑ² = 2.38² σ² / m_mcmc), plain Monte Carlo on the rest. The reference's `draw!` (Samplers.jl:287-322) cannot run as
+    written — it reads `smp.n_mcmc`, a field the struct does not have, and the bare names `m` and `m_mcmc` — so this mirrors its
+    evident intent: the Metropolis loop on ξ[:m_mcmc], then fresh N(0, 1) numbers for ξ[m_mcmc:]. `draw()` returns cnt.
+
+    Calls of `rng`, in order: at construction `standard_normal(m_mcmc)` and `standard_normal(m - m_mcmc)` for ξ, then
+    `standard_normal(m_mcmc)` for χ; per proposal `standard_normal(m_mcmc)`, then `random()`; after the acceptance one
+    `standard_normal(m - m_mcmc)`."""
+
+    def __init__(self, Λ, Ψ, rng, m_mcmc: int, field: Optional[KLField] = None):
+        if not 1 <= m_mcmc <= _f64(Λ).size:
+            raise ValueError(f"m_mcmc = {m_mcmc}: between 1 and m = {_f64(Λ).size} expected")
+        self.m_mcmc = int(m_mcmc)
+        super().__init__(Λ, Ψ, rng, field)
+
+    def _scale(self):
+        return self.m_mcmc
+
+    def _init_latent(self):
+        self.σ2 = 1.0
+        head = np.sqrt(self.σ2) * np.asarray(self.rng.standard_normal(self.m_mcmc), dtype=np.float64)
+        tail = np.asarray(self.rng.standard_normal(self.m - self.m_mcmc), dtype=np.float64)
+        self.ξ = np.concatenate([head, tail])
+        self.ϑ2 = 2.38 ** 2 * self.σ2 / self.m_mcmc
+        self.χ = head + np.sqrt(self.ϑ2) * np.asarray(self.rng.standard_normal(self.m_mcmc), dtype=np.float64)
+
+    def draw(self) -> int:
+        self.χ, cnt = self._metropolis(self.ξ[:self.m_mcmc])
+        tail = np.asarray(self.rng.standard_normal(self.m - self.m_mcmc), dtype=np.float64)
+        self.ξ = np.concatenate([self.χ, tail])
+        self._field()
+        return cnt
+
+
 GlobalSchur.use_level_solver = _use_level_solver

@@ -14,6 +14,7 @@
 #include "amg.hpp"
 #include "amg_setup.hpp"
 #include "kl.hpp"
+#include "kl_field.hpp"
 
 namespace mi {
 
@@ -1143,6 +1144,179 @@ int mi_kl_cov_create(mi_ctx_t ctx, int model, double sig2, double L, int64_t n, 
       if (!std::isfinite(v)) raise(MI_ERR_BAD_ARG, "%s: M holds %g (not finite)", me, v);
     return new KlCovOp(ctx, model, sig2, L, n, points, hm);
   })());
+}
+
+// ---------------------------------------------------------------- realization sampler: ξ -> g -> a = exp(g) (kl_field.hpp)
+int mi_kl_field_tiling(int64_t n, int64_t m, int64_t nreal, int64_t *row_tile, int64_t *mode_chunk, int64_t *real_block, int64_t *coord_splits) {
+  if (n < 1 || m < 1 || nreal < 1 || n > KLF_MAX_N || m > KLF_MAX_N || nreal > KLF_MAX_N)
+    return fail(MI_ERR_BAD_ARG, "mi_kl_field_tiling: n = %lld, m = %lld, nreal = %lld: each at least 1 and at most 2^30", (long long)n, (long long)m, (long long)nreal);
+  if (row_tile) *row_tile = KLF_ROW_TILE;
+  if (mode_chunk) *mode_chunk = KLF_MODE_CHUNK;
+  if (real_block) *real_block = KLF_RB;
+  if (coord_splits) *coord_splits = klf_tiling(n, m, nreal).coord_splits;
+  return MI_OK;
+}
+
+// the checks both constructors share; NULL after a refusal (mi_last_error is set)
+static mi_kl_field_s *klf_new(const char *me, mi_ctx_t ctx, int64_t n, int64_t m, const double *lam, int *rc) {
+  *rc = MI_ERR_BAD_ARG;
+  if (!ctx || !lam) { fail(MI_ERR_BAD_ARG, "%s: ctx or Lambda is NULL", me); return nullptr; }
+  if (n < 1 || m < 1 || n > KLF_MAX_N || m > KLF_MAX_N) {
+    fail(MI_ERR_BAD_ARG, "%s: n = %lld, m = %lld: each at least 1 and at most 2^30", me, (long long)n, (long long)m);
+    return nullptr;
+  }
+  if (ctx->has_comm()) { fail(MI_ERR_BAD_ARG, "%s: the context is one rank of several; sharded KL fields are not provided", me); return nullptr; }
+  for (int64_t a = 0; a < m; ++a)
+    if (!(lam[a] >= 0.0) || !std::isfinite(lam[a])) {
+      fail(MI_ERR_BAD_ARG, "%s: Lambda[%lld] = %g is negative or not finite (the reference's sqrt would throw)", me, (long long)a, lam[a]);
+      return nullptr;
+    }
+  *rc = MI_OK;
+  mi_kl_field_s *f = new mi_kl_field_s;
+  f->ctx = ctx; f->n = (int)n; f->m = (int)m;
+  f->lam.assign(lam, lam + m);
+  return f;
+}
+static void klf_upload_common(mi_kl_field_s *f) {
+  std::vector<double> sq(f->lam.size());
+  for (size_t a = 0; a < sq.size(); ++a) sq[a] = std::sqrt(f->lam[a]);   // correctly rounded, as the host's sqrt(Λ[α])
+  f->sqrt_lam.upload(sq, f->ctx->stream);
+  f->c.alloc((size_t)f->m * KLF_RB);
+}
+// column-major host matrix (rows x cols, leading dimension ld) -> compact device matrix; blocking
+static void klf_upload_matrix(mi_ctx_s *c, DevBuf<double> &dst, const double *src, size_t rows, size_t cols, size_t ld) {
+  dst.alloc(rows * cols);
+  MI_HIP(hipMemcpy2DAsync(dst.p, sizeof(double) * rows, src, sizeof(double) * ld, sizeof(double) * rows, cols, hipMemcpyHostToDevice, c->stream));
+  MI_HIP(hipStreamSynchronize(c->stream));
+}
+
+int mi_kl_field_create(mi_ctx_t ctx, int64_t n, int64_t m, const double *lambda, const double *Psi, int64_t ldpsi, mi_kl_field_t *field) {
+  const char *me = "mi_kl_field_create";
+  if (!field) return fail(MI_ERR_BAD_ARG, "%s: field is NULL", me);
+  *field = nullptr;
+  if (!Psi) return fail(MI_ERR_BAD_ARG, "%s: Psi is NULL", me);
+  if (ldpsi < n) return fail(MI_ERR_BAD_ARG, "%s: ldpsi = %lld < n = %lld", me, (long long)ldpsi, (long long)n);
+  return guarded([&]() -> int {
+    int rc;
+    std::unique_ptr<mi_kl_field_s> f(klf_new(me, ctx, n, m, lambda, &rc));
+    if (!f) return rc;
+    ctx->use();
+    klf_upload_common(f.get());
+    klf_upload_matrix(ctx, f->Psi, Psi, (size_t)n, (size_t)m, (size_t)ldpsi);
+    f->w.alloc((size_t)n);
+    f->part.alloc((size_t)klf_tiling(n, m, 1).coord_splits * (size_t)m);
+    f->bytes_kept = 8 * (n * m + m);
+    f->bytes_per_set = 8 * (n * m + 4 * m + n);   // Ψ; sqrt(Λ) and ξ in, c out and in; one output
+    *field = f.release();
+    return MI_OK;
+  });
+}
+
+int mi_kl_field_create_dd(mi_ctx_t ctx, int64_t n, int64_t m, const double *lambda, int64_t ndom, const int64_t *n_d, const int64_t *md,
+                          const int64_t *inds_l2gd, int index_base, const double *Phid, const double *Phi, int64_t ldphi,
+                          mi_kl_field_t *field) {
+  const char *me = "mi_kl_field_create_dd";
+  if (!field) return fail(MI_ERR_BAD_ARG, "%s: field is NULL", me);
+  *field = nullptr;
+  if (!n_d || !md || !inds_l2gd || !Phid || !Phi) return fail(MI_ERR_BAD_ARG, "%s: n_d, md, inds_l2gd, Phid or Phi is NULL", me);
+  return guarded([&]() -> int {
+    int rc;
+    std::unique_ptr<mi_kl_field_s> f(klf_new(me, ctx, n, m, lambda, &rc));
+    if (!f) return rc;
+    std::string err;
+    if (klfp::make_dd_plan(n, ndom, n_d, md, inds_l2gd, index_base, f->plan, err) != klfp::OK) return fail(MI_ERR_BAD_ARG, "%s: %s", me, err.c_str());
+    const klfp::Plan &pl = f->plan;
+    if (ldphi < pl.nred) return fail(MI_ERR_BAD_ARG, "%s: ldphi = %lld < the %lld rows of Phi (the sum of md)", me, (long long)ldphi, (long long)pl.nred);
+    f->dd = true;
+    ctx->use();
+    hipStream_t s = ctx->stream;
+    klf_upload_common(f.get());
+    klf_upload_matrix(ctx, f->Phi, Phi, (size_t)pl.nred, (size_t)m, (size_t)ldphi);
+    f->Phid.upload(Phid, (size_t)pl.phid_off.back(), s);
+    MI_HIP(hipStreamSynchronize(s));
+    f->tiles.upload(pl.tiles, s); f->n_d.upload(pl.n_d, s); f->md.upload(pl.md, s); f->y_off.upload(pl.y_off, s); f->t_off.upload(pl.t_off, s);
+    f->phid_off.upload(pl.phid_off, s); f->own_ptr.upload(pl.own_ptr, s); f->own_pos.upload(pl.own_pos, s);
+    f->y.alloc((size_t)pl.nred * KLF_RB);
+    f->t.alloc((size_t)pl.nloc * KLF_RB);
+    const int64_t factors = 8 * ((int64_t)pl.phid_off.back() + (int64_t)pl.nred * m);
+    f->bytes_kept = factors + 8 * m + pl.bytes();
+    // the factors, c, y written and read, t written and read, the owner lists, one output
+    f->bytes_per_set = factors + 8 * 4 * m + 16 * (int64_t)pl.nred + 16 * (int64_t)pl.nloc + 4 * ((int64_t)n + 1 + pl.nloc) + 8 * n;
+    *field = f.release();
+    return MI_OK;
+  });
+}
+
+int mi_kl_field_set(mi_kl_field_t field, int64_t nreal, const double *Xi, int64_t ldxi, double *G, int64_t ldg, double *A, int64_t lda) {
+  const char *me = "mi_kl_field_set";
+  if (!field || !Xi) return fail(MI_ERR_BAD_ARG, "%s: field or Xi is NULL", me);
+  if (!G && !A) return fail(MI_ERR_BAD_ARG, "%s: G and A are both NULL", me);
+  if (nreal < 1 || nreal > KLF_MAX_N) return fail(MI_ERR_BAD_ARG, "%s: nreal = %lld (1 <= nreal <= 2^30)", me, (long long)nreal);
+  const int64_t n = field->n, m = field->m;
+  if (ldxi < m || (G && ldg < n) || (A && lda < n))
+    return fail(MI_ERR_BAD_ARG, "%s: ldxi = %lld < m = %lld, or ldg = %lld or lda = %lld < n = %lld", me, (long long)ldxi, (long long)m, (long long)ldg,
+                (long long)lda, (long long)n);
+  mi_ctx_s *c = field->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    auto blocks = [&](const double *xi, int64_t ldx, double *g, int64_t lg, double *a, int64_t la) {
+      for (int64_t r0 = 0; r0 < nreal; r0 += KLF_RB)
+        field->launch_set((int)std::min<int64_t>(KLF_RB, nreal - r0), xi + (size_t)r0 * ldx, ldx, g ? g + (size_t)r0 * lg : nullptr, lg,
+                          a ? a + (size_t)r0 * la : nullptr, la);
+    };
+    if (c->ptr_mode == MI_PTR_DEVICE) { blocks(Xi, ldxi, G, ldg, A, lda); return MI_OK; }
+    hipStream_t s = c->stream;
+    const size_t row = sizeof(double);
+    DevBuf<double> dXi((size_t)m * nreal), dG, dA;
+    MI_HIP(hipMemcpy2DAsync(dXi.p, row * m, Xi, row * ldxi, row * m, (size_t)nreal, hipMemcpyHostToDevice, s));
+    if (G) dG.alloc((size_t)n * nreal);
+    if (A) dA.alloc((size_t)n * nreal);
+    blocks(dXi.p, m, G ? dG.p : nullptr, n, A ? dA.p : nullptr, n);
+    if (G) MI_HIP(hipMemcpy2DAsync(G, row * ldg, dG.p, row * n, row * n, (size_t)nreal, hipMemcpyDeviceToHost, s));
+    if (A) MI_HIP(hipMemcpy2DAsync(A, row * lda, dA.p, row * n, row * n, (size_t)nreal, hipMemcpyDeviceToHost, s));
+    MI_HIP(hipStreamSynchronize(s));
+    return MI_OK;
+  });
+}
+
+int mi_kl_field_coords(mi_kl_field_t field, mi_op_t M, const double *g, double *xi) {
+  const char *me = "mi_kl_field_coords";
+  if (!field || !M || !M->impl || !g || !xi) return fail(MI_ERR_BAD_ARG, "%s: field, M, g or xi is NULL", me);
+  if (field->dd) return fail(MI_ERR_BAD_ARG, "%s: coordinates are not provided for the factored form (no Psi is kept)", me);
+  if (field->m > KLF_COORD_MAX_M) return fail(MI_ERR_BAD_ARG, "%s: m = %d modes (at most %lld for the coordinates)", me, field->m, (long long)KLF_COORD_MAX_M);
+  CsrDev *csr = M->impl->as_csr();
+  if (!csr || csr->n_rows != field->n || csr->n_cols != field->n || M->impl->ctx != field->ctx)
+    return fail(MI_ERR_BAD_ARG, "%s: M is not a %d x %d sparse matrix (mi_csr_create) of the field's context", me, field->n, field->n);
+  for (size_t a = 0; a < field->lam.size(); ++a)
+    if (field->lam[a] == 0.0) return fail(MI_ERR_BAD_ARG, "%s: Lambda[%lld] = 0: the coordinate divides by sqrt(Lambda)", me, (long long)a);
+  mi_ctx_s *c = field->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    if (c->ptr_mode == MI_PTR_DEVICE) { field->launch_coords(*csr, g, xi); return MI_OK; }
+    DevBuf<double> gs, xs;
+    In gi(c, g, (size_t)field->n, gs);
+    InOut xo(c, xi, (size_t)field->m, xs, false);
+    field->launch_coords(*csr, gi.dev, xo.dev);
+    xo.finish();
+    return MI_OK;
+  });
+}
+
+int mi_kl_field_stats(mi_kl_field_t field, int64_t *bytes_kept, int64_t *bytes_per_set) {
+  if (!field) return fail(MI_ERR_BAD_ARG, "mi_kl_field_stats: field is NULL");
+  if (bytes_kept) *bytes_kept = field->bytes_kept;
+  if (bytes_per_set) *bytes_per_set = field->bytes_per_set;
+  return MI_OK;
+}
+
+int mi_kl_field_destroy(mi_kl_field_t field) {
+  if (!field) return MI_OK;
+  return guarded([&]() -> int {
+    field->ctx->use();
+    (void)hipStreamSynchronize(field->ctx->stream);
+    delete field;
+    return MI_OK;
+  });
 }
 
 // ---------------------------------------------------------------- on-device block assembly

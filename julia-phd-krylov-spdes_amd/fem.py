@@ -1177,6 +1177,48 @@ def draw(kl: SyntheticKL, rng: np.random.Generator):
     return ξ, g
 
 
+def set_field(Λ, Ψ, ξ):
+    """The loop of `draw` without the random numbers (`set!`, KLDD.jl:1150-1164; Samplers.jl:81-87):
+    g = Σ_α (sqrt(Λ_α) ξ_α) Ψ[:, α], mode by mode from zero. A non-finite ξ gives IEEE results, not an error."""
+    Λ, Ψ, ξ = np.asarray(Λ, dtype=np.float64), np.asarray(Ψ, dtype=np.float64), np.asarray(ξ, dtype=np.float64)
+    g = np.zeros(Ψ.shape[0])
+    with np.errstate(invalid="ignore", over="ignore"):
+        for α in range(Λ.size):
+            g += (np.sqrt(Λ[α]) * ξ[α]) * Ψ[:, α]
+    return g
+
+
+def draw_dd_field(nnode: int, Λ, Φ, Φd, inds_l2gd, ξ):
+    """The field of `draw(mesh, Λ, Φ, Φd, inds_l2gd)` (KLDD.jl:850-883) for a given ξ, in the reference's own loop order:
+    g[inode] += sqrt(Λ_γ) ξ_γ Φ[ind(idom, α), γ] Φd[idom][i, α] over (idom, α, γ), then g ./= cnt. Ψ is never formed."""
+    Λ, Φ, ξ = np.asarray(Λ, dtype=np.float64), np.asarray(Φ, dtype=np.float64), np.asarray(ξ, dtype=np.float64)
+    g = np.zeros(nnode)
+    cnt = np.zeros(nnode, dtype=np.int64)
+    c = np.sqrt(Λ) * ξ
+    off = 0
+    for idom, l2g in enumerate(inds_l2gd):
+        cnt[l2g] += 1
+        P = np.asarray(Φd[idom], dtype=np.float64)
+        for α in range(P.shape[1]):
+            for γ in range(Λ.size):
+                g[l2g] += c[γ] * Φ[off + α, γ] * P[:, α]
+        off += P.shape[1]
+    return g / cnt
+
+
+def get_kl_coordinates(g, Λ, Φ, M):
+    """`get_kl_coordinates(g, Λ, Φ, M)` (KLDD.jl:1109-1124): ξ_α = Σ_i Φ[i, α] (M g)[i] / sqrt(Λ_α), every term divided,
+    rows ascending."""
+    Λ, Φ = np.asarray(Λ, dtype=np.float64), np.asarray(Φ, dtype=np.float64)
+    w = M @ np.asarray(g, dtype=np.float64)
+    ξ = np.zeros(Λ.size)
+    for α in range(Λ.size):
+        terms = Φ[:, α] * w / np.sqrt(Λ[α])
+        for t in terms:
+            ξ[α] += t
+    return ξ
+
+
 # --------------------------------------------------------------------------------------
 # Karhunen-Loève layer, host side (Fem/KarhunenLoeve.jl, Fem/KarhunenLoeveDomainDecomposition.jl = "KLDD.jl",
 # Fem/KarhunenLoeveDomainDecompositionHelper.jl, Fem/Covariances.jl). The covariance-heavy parts run on the device

@@ -36,7 +36,8 @@ export MiContext, MiOperator, MiPrecond,
        AssemblyPlan, assemble!, set_values!, SchurSetup, set_blocks!, interior_precond!, interior_iterations,
        keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!,
        SparseDirectPreconditioner, spd_direct_stats, bj_set_values!, MiLorasc, set_correction!, MiNNInduced, set_coupling!,
-       mi_eigsolve, mi_geneigsolve, MiAMGPreconditioner, amg_stats
+       mi_eigsolve, mi_geneigsolve, MiAMGPreconditioner, amg_stats,
+       MiKlField, MiMcmcSampler, coefficient!, klfield_stats
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -822,5 +823,108 @@ eigpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditi
 eigdefpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditioner, W::Matrix{Float64}, spdim::Int; maxit=0) =
   eigsolve(:eigdefpcg, A, M.op, b, x, W, size(W, 2), spdim, maxit)
 initpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditioner, W::Matrix{Float64}; maxit=0) = initsolve(A, M.op, b, x, W, maxit)
+
+# ---------------------------------------------------------------- realization sampler (Example06:160, Example09 `draw!(sampler)`)
+"""`MiKlField`: the step from a latent vector ξ to the field g = Σ_α sqrt(Λ_α) ξ_α Ψ[:, α] on the device (`mi_kl_field_t`).
+`MiKlField(ctx, Λ, Ψ)` keeps Ψ; `MiKlField(ctx, nnode, Λ, Φ, Φd, inds_l2gd)` keeps the factors of
+`draw(mesh, Λ, Φ, Φd, inds_l2gd)` (KLDD.jl:850-883) and never forms Ψ. The methods below are ADDED to Fem's `set!`, `draw!` and
+`get_kl_coordinates` (exports at Fem/Fem.jl:101-104); they take the handle first, so they cannot collide with the reference's
+`(Λ, Ψ, ξ, g)` methods. The calls of this section are written with `@ccall`, argument and C type side by side;
+tests/test_julia_shim_klfield_cpu.py checks them against include/mi355schur.h."""
+mutable struct MiKlField
+  h::Ptr{Cvoid}; n::Int; m::Int; ctx::MiContext
+end
+function klfield_wrap(ctx::MiContext, r::Ref{Ptr{Cvoid}}, n::Int, m::Int)
+  f = MiKlField(r[], n, m, ctx)
+  finalizer(q -> @ccall(lib.mi_kl_field_destroy(q.h::Ptr{Cvoid})::Cint), f)
+end
+function MiKlField(ctx::MiContext, Λ::Vector{Float64}, Ψ::Matrix{Float64})
+  n, m = size(Ψ)
+  length(Λ) == m || throw(ArgumentError("Ψ has $m columns, Λ $(length(Λ)) entries"))
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  check(@ccall lib.mi_kl_field_create(ctx.h::Ptr{Cvoid}, n::Int64, m::Int64, Λ::Ptr{Float64}, Ψ::Ptr{Float64}, n::Int64, r::Ref{Ptr{Cvoid}})::Cint)
+  klfield_wrap(ctx, r, n, m)
+end
+function MiKlField(ctx::MiContext, nnode::Int, Λ::Vector{Float64}, Φ::Matrix{Float64}, Φd::Vector{Matrix{Float64}}, inds_l2gd::Vector{Vector{Int}})
+  ndom, m = length(Φd), length(Λ)
+  n_d, md = Int64[size(P, 1) for P in Φd], Int64[size(P, 2) for P in Φd]
+  (length(inds_l2gd) == ndom && all(length(inds_l2gd[d]) == n_d[d] for d in 1:ndom)) || throw(ArgumentError("Φd[d] must have length(inds_l2gd[d]) rows"))
+  size(Φ) == (sum(md), m) || throw(ArgumentError("Φ is $(size(Φ)), expected $((sum(md), m))"))
+  inds = Vector{Int64}(reduce(vcat, inds_l2gd))
+  blocks = reduce(vcat, [vec(P) for P in Φd])                          # column-major blocks, one after the other
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  check(@ccall lib.mi_kl_field_create_dd(ctx.h::Ptr{Cvoid}, nnode::Int64, m::Int64, Λ::Ptr{Float64}, ndom::Int64, n_d::Ptr{Int64}, md::Ptr{Int64},
+                                         inds::Ptr{Int64}, 1::Cint, blocks::Ptr{Float64}, Φ::Ptr{Float64}, size(Φ, 1)::Int64, r::Ref{Ptr{Cvoid}})::Cint)
+  klfield_wrap(ctx, r, nnode, m)
+end
+
+"""`set!(f, ξ, g)`: `set!(Λ, Ψ, ξ, g)` (KLDD.jl:1150-1164) on the device; g has the bits of the host loop (dense form)."""
+function Fem.set!(f::MiKlField, ξ::Vector{Float64}, g::Vector{Float64})
+  (length(ξ) == f.m && length(g) == f.n) || throw(DimensionMismatch("ξ needs $(f.m) entries, g $(f.n)"))
+  check(@ccall lib.mi_kl_field_set(f.h::Ptr{Cvoid}, 1::Int64, ξ::Ptr{Float64}, f.m::Int64, g::Ptr{Float64}, f.n::Int64, C_NULL::Ptr{Float64}, f.n::Int64)::Cint)
+  return g
+end
+"""`draw!(f, ξ, g)`: `draw!(Λ, Ψ, ξ, g)` (KLDD.jl:1026-1044, Example06:160): ξ .= N(0, I) on the host (m numbers), the field on
+the device."""
+function Fem.draw!(f::MiKlField, ξ::Vector{Float64}, g::Vector{Float64})
+  ξ .= randn(f.m)
+  Fem.set!(f, ξ, g)
+  return
+end
+"""`coefficient!(a, f, ξ)`: a = exp.(g(ξ)) without the field crossing to the host (the `exp.(g)` of Example06:161)."""
+function coefficient!(a::Vector{Float64}, f::MiKlField, ξ::Vector{Float64})
+  (length(ξ) == f.m && length(a) == f.n) || throw(DimensionMismatch("ξ needs $(f.m) entries, a $(f.n)"))
+  check(@ccall lib.mi_kl_field_set(f.h::Ptr{Cvoid}, 1::Int64, ξ::Ptr{Float64}, f.m::Int64, C_NULL::Ptr{Float64}, f.n::Int64, a::Ptr{Float64}, f.n::Int64)::Cint)
+  return a
+end
+"""`get_kl_coordinates(f, g, M)`: `get_kl_coordinates(g, Λ, Ψ, M)` (KLDD.jl:1109-1124); `M = MiOperator(ctx, mass_matrix)`."""
+function Fem.get_kl_coordinates(f::MiKlField, g::Vector{Float64}, M::MiOperator)
+  ξ = Vector{Float64}(undef, f.m)
+  check(@ccall lib.mi_kl_field_coords(f.h::Ptr{Cvoid}, M.h::Ptr{Cvoid}, g::Ptr{Float64}, ξ::Ptr{Float64})::Cint)
+  return ξ
+end
+function klfield_stats(f::MiKlField)
+  a, b = Ref{Int64}(0), Ref{Int64}(0)
+  check(@ccall lib.mi_kl_field_stats(f.h::Ptr{Cvoid}, a::Ref{Int64}, b::Ref{Int64})::Cint)
+  (bytes_kept=Int(a[]), bytes_per_set=Int(b[]))
+end
+
+"""`MiMcmcSampler(f)`: `prepare_mcmc_sampler(Λ, Ψ)` (Samplers.jl:130-152) on a `MiKlField`; `draw!(smp)` is the reference's
+(Samplers.jl:165-199) with the field on the device and returns `cnt`; `smp.g`, `smp.a = exp.(smp.g)` as Example09 reads them."""
+mutable struct MiMcmcSampler
+  n::Int; m::Int
+  σ2::Float64; ξ::Vector{Float64}
+  ϑ2::Float64; χ::Vector{Float64}
+  field::MiKlField
+  g::Vector{Float64}; a::Vector{Float64}
+end
+function MiMcmcSampler(f::MiKlField)
+  σ2 = 1.
+  ξ = sqrt(σ2) .* randn(f.m)
+  ϑ2 = 2.38^2 * σ2 / f.m
+  χ = ξ .+ sqrt(ϑ2) .* randn(f.m)
+  smp = MiMcmcSampler(f.n, f.m, σ2, ξ, ϑ2, χ, f, zeros(f.n), zeros(f.n))
+  Fem.set!(smp, ξ)
+  return smp
+end
+function Fem.set!(smp::MiMcmcSampler, ξ::Vector{Float64})
+  smp.ξ .= ξ
+  Fem.set!(smp.field, smp.ξ, smp.g)
+  smp.a .= exp.(smp.g)
+  return
+end
+function Fem.draw!(smp::MiMcmcSampler)
+  sq_norm_of_ξ = smp.ξ'smp.ξ
+  cnt = 0
+  while true
+    smp.χ .= smp.ξ .+ sqrt(smp.ϑ2) .* randn(smp.m)
+    sq_norm_of_χ = smp.χ'smp.χ
+    cnt += 1
+    α = sq_norm_of_ξ < sq_norm_of_χ ? exp((sq_norm_of_ξ - sq_norm_of_χ) / 2 / smp.σ2) : 1.
+    rand() > α || break
+  end
+  Fem.set!(smp, smp.χ)
+  return cnt
+end
 
 end # module
