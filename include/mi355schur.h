@@ -110,7 +110,7 @@ int mi_ctx_set_exchange(mi_ctx_t ctx, int use_peer_exchange);
 #define MI_QUERY_PEER_EXCHANGE 1
 #define MI_QUERY_GRAPH_REPLAYS 2
 #define MI_QUERY_EXCHANGES 3
-#define MI_QUERY_EXPERIMENTAL 5    /* 1: built with `make EXPERIMENTAL=1` (persistent on-chip PCG, rocBLAS/rocSOLVER set-up route) */
+#define MI_QUERY_EXPERIMENTAL 5    /* always 0: the EXPERIMENTAL build (persistent on-chip PCG, rocBLAS/rocSOLVER set-up route) was removed */
 #define MI_QUERY_SPECTRAL_PINV 4   /* blocks of mi_nn_pinv that went to the eigen-decomposition (rocSOLVER) so far, process-wide */
 #define MI_QUERY_FOLDED_PCG 6      /* launches of the folded PCG kernel issued (captured or direct) so far, process-wide */
 int mi_ctx_query(mi_ctx_t ctx, int what, int64_t *out);
@@ -435,8 +435,7 @@ int mi_schur_matfree_interior_solutions(mi_op_t op, const double *u_gamma, const
  * the reference's semantics: tests/test_gpu_setup.py::test_device_setup_against_the_reference_semantics). Break-down: an
  * interior block that is singular or not positive definite (the reference's CHOLMOD paths would throw PosDefException)
  * shows as Inf / NaN in S_d: host-pointer mode returns MI_ERR_SINGULAR from run; device-pointer mode is asynchronous and
- * the next mi_nn_pinv on such blocks returns MI_ERR_SINGULAR. (MI355_SETUP_LIB=1 in an EXPERIMENTAL build selects a
- * rocBLAS / rocSOLVER block-Cholesky route instead; there potrf's info is what host-pointer mode reports.)
+ * the next mi_nn_pinv on such blocks returns MI_ERR_SINGULAR.
  *   create: the sparsity of the blocks (CSC colptr / rowval as for mi_schur_matfree_device_create), once per mesh / partition
  *   run   : one realization. ii_val / ig_val / gg_val: the concatenations over the subdomains of the blocks' CSC nzval arrays
  *           (the layout mi_assembly_run produces and mi_schur_matfree_set_values takes); b_I: concatenated b_Id or NULL.

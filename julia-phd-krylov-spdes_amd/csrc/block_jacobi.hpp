@@ -332,17 +332,8 @@ struct BlockJacobiOp : Operator {
     const GjState &G = *plan->gj;
     for (int d = 0; d < nb; ++d) {
       const SetupDom &D = plan->dom[d];
-      const int n0 = D.nlev ? D.lev_off[1] : 0;
-      const int *cp = plan->c_ptr_h.data() + D.bptr_off;
-      std::vector<std::vector<std::pair<int, int>>> rows(n0);
-      for (int j = 0; j < D.n_g && n0; ++j)
-        for (int p = cp[j]; p < cp[j + 1]; ++p) rows[plan->c_row_h[p]].push_back({j, plan->c_src_h[p]});
       bo[d] = (int)bp.size();
-      for (int i = 0; i < n0; ++i) {
-        bp.push_back((int)bc.size());
-        for (auto &e : rows[i]) { bc.push_back(e.first); bs.push_back(e.second); }
-      }
-      bp.push_back((int)bc.size());
+      setup::row_form(D.nlev ? D.lev_off[1] : 0, D.n_g, plan->c_ptr_h.data() + D.bptr_off, plan->c_row_h.data(), plan->c_src_h.data(), bp, bc, bs);
       for (int k = 0; k < D.nlev; ++k) { const int64_t w = D.lev_off[k + 1] - D.lev_off[k]; kept += 8 * w * w; }
       sg += 8 * ng_h[d] * ng_h[d];
     }

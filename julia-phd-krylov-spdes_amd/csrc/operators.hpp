@@ -19,6 +19,7 @@ inline int vec_grid(int64_t n) {
   int64_t g = (n + (int64_t)NT * 4 - 1) / ((int64_t)NT * 4);
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, MAX_PARTS));
 }
+inline int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + NT - 1) / NT, 4096)); }
 inline int env_int(const char *name, int dflt) {
   const char *s = std::getenv(name);
   return s && *s ? std::atoi(s) : dflt;
@@ -423,8 +424,8 @@ struct DenseBlockOp : Operator {
       if (owned(dl)) alg_bytes += (f32() ? 4ll : 8ll) * maps.nd[dl] * maps.nd[dl] + 16ll * maps.nd[dl] + 4ll * maps.nd[dl];
     moff_h = moff; ld_h = ldv;
     for (int dl = 0; dl < maps.ndl; ++dl) owned_h.push_back(owned(dl) ? 1 : 0);
-    // (+ one zeroed panel behind the last block: the persistent kernel reads whole 128-double groups of a row without
-    // clamping, so a read may run past a row's end — into the next row, or into this tail — and meets a zero operand there)
+    // (+ one zeroed panel behind the last block: a reader of whole 128-double groups of a row that does not clamp may run
+    // past a row's end — into the next row, or into this tail — and meets a zero operand there)
     if (f32()) {
       // Refuse before anything is stored: a block entry that fp32 cannot hold would sit in the preconditioner as a silent inf.
       for (int dl = 0; dl < maps.ndl; ++dl) {

@@ -1,9 +1,9 @@
-// The level elimination of setup_dense.hpp with kernels of this library only, batched over the subdomains and replayed
-// from one hipGraph per realization (the library path issues ~250 levels x dozens of small rocSOLVER / rocBLAS kernels
-// per subdomain from the host: ~3 s per realization at config 3, bound by the host's launch rate; rocSOLVER cannot be
-// captured into a graph).
+// The level elimination of setup_plan.hpp on the device: kernels of this library only, batched over the subdomains and
+// replayed from one hipGraph per realization (a chain of library BLAS-3 / LAPACK calls per level was measured and not
+// adopted, profiles/NOTES.md: ~250 levels x dozens of small kernels per subdomain issued from the host, ~3 s per
+// realization at config 3, bound by the host's launch rate; rocSOLVER cannot be captured into a graph).
 //
-// Formulation. With Z_k = T_k^{-1} kept explicitly (dense, symmetric) the recursion of setup_dense.hpp reads
+// Formulation. With Z_k = T_k^{-1} kept explicitly (dense, symmetric) the recursion of setup_plan.hpp reads
 //     T_k = A_kk - C_k' Z_{k+1} C_k,     g_k = b_k - C_k' (Z_{k+1} g_{k+1}),     Z_k = T_k^{-1},
 //     S_d = A_ΓΓ - B' Z_0 B,             w_d = B' (Z_0 g_0),
 // where C_k = A_{k+1,k} and B = A_IΓ[L_0, :] are SPARSE (a P1 node has <= 3-4 neighbours in the adjacent level), so every
@@ -20,9 +20,12 @@
 #include <atomic>
 #include <limits>
 
-#include "setup_dense.hpp"
+#include "operators.hpp"
+#include "setup_plan.hpp"
 
 namespace mi {
+
+using SetupDom = setup::Dom;
 
 #ifndef MI355_GJ_B
 #define MI355_GJ_B 64
@@ -78,6 +81,35 @@ struct GjState {
     if (solve_graph) (void)hipGraphExecDestroy(solve_graph);
   }
 };
+}  // namespace mi
+
+// The plan of mi_schur_setup_create: the host plan, its arrays on the device, and the state of the elimination
+struct mi_setup_s : mi::setup::Plan {
+  mi_ctx_s *ctx = nullptr;
+  mi::DevBuf<int> src, dst, perm;        // entry lists of A_kk and A_ΓΓ of all subdomains; interior permutation (concatenated)
+  mi::DevBuf<int> c_ptr, c_row, c_src;   // column form of the coupling blocks
+  mi::DevBuf<double> st_ii, st_ig, st_gg, st_bi, st_S, st_w;   // staging for host-pointer calls
+  std::unique_ptr<mi::GjState> gj;       // block Gauss-Jordan elimination, batched over the subdomains, replayed from a hipGraph
+  int bound = 0;                         // operators that borrow this plan (lorasc.hpp): mi_schur_setup_destroy is refused while > 0
+  int bound_nni = 0;                     // ... and the Neumann-Neumann induced operators that do (nn_induced.hpp)
+};
+
+namespace mi {
+
+inline void setup_plan_build(mi_setup_s &P, mi_ctx_s *c, int64_t ndom, const int64_t *n_gamma_d, const int64_t *n_i,
+                             const int64_t *const *ii_ptr, const int64_t *const *ii_idx, const int64_t *const *ig_ptr,
+                             const int64_t *const *ig_idx, const int64_t *const *gg_ptr, const int64_t *const *gg_idx, int base) {
+  setup::Input in;
+  in.ndom = ndom; in.base = base; in.n_gamma_d = n_gamma_d; in.n_i = n_i;
+  in.ii_ptr = ii_ptr; in.ii_idx = ii_idx; in.ig_ptr = ig_ptr; in.ig_idx = ig_idx; in.gg_ptr = gg_ptr; in.gg_idx = gg_idx;
+  std::string err;
+  if (setup::make_plan(in, P, err) != setup::OK) raise(MI_ERR_BAD_ARG, "%s", err.c_str());
+  P.ctx = c;
+  hipStream_t s = c->stream;
+  P.src.upload(P.src_h, s); P.dst.upload(P.dst_h, s); P.perm.upload(P.perm_h, s);
+  P.c_ptr.upload(P.c_ptr_h, s); P.c_row.upload(P.c_row_h, s); P.c_src.upload(P.c_src_h, s);
+  for (auto *v : {&P.src_h, &P.dst_h, &P.perm_h}) std::vector<int>().swap(*v);   // read on the device only; the column form keeps its host copy (row_form)
+}
 
 #pragma clang fp contract(fast)
 
@@ -996,17 +1028,8 @@ inline void gj_set_keep(mi_setup_s &P, bool on) {
       st.rptr = 0;
       if (k == 0) continue;
       // rows of C_{k-1} = A_{k, k-1}: from its column form (columns = nodes of level k-1)
-      const int nr = st.n0, nc = D.lev_off[k] - D.lev_off[k - 1];
-      const int *cp = P.c_ptr_h.data() + D.cptr_off[k - 1];
-      std::vector<std::vector<std::pair<int, int>>> rows(nr);
-      for (int j = 0; j < nc; ++j)
-        for (int p = cp[j]; p < cp[j + 1]; ++p) rows[P.c_row_h[p]].push_back({j, P.c_src_h[p]});
       st.rptr = (int)rp.size();
-      for (int i = 0; i < nr; ++i) {
-        rp.push_back((int)rc.size());
-        for (auto &e : rows[i]) { rc.push_back(e.first); rs.push_back(e.second); }
-      }
-      rp.push_back((int)rc.size());
+      setup::row_form(st.n0, D.lev_off[k] - D.lev_off[k - 1], P.c_ptr_h.data() + D.cptr_off[k - 1], P.c_row_h.data(), P.c_src_h.data(), rp, rc, rs);
     }
   }
   hipStream_t s = P.ctx->stream;
@@ -1190,6 +1213,7 @@ __global__ __launch_bounds__(256) void k_add_const(long long n, double *__restri
 __global__ __launch_bounds__(256) void k_copy_add_const(long long n, const double *__restrict__ src, double *__restrict__ dst, double c) {
   for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) dst[e] = src[e] + c;
 }
+inline void pinv_blocks(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, const double *Sd, double rtol, double *Pi);   // the spectral route: pinv_spectral.hpp
 inline std::atomic<long long> &spectral_pinv_calls() { static std::atomic<long long> n{0}; return n; }   // blocks sent to the eigen-decomposition (mi_ctx_query)
 
 // `spd_only` (block_jacobi.hpp: the Schur complements of an SPD matrix are SPD): the plain inverse with its certificate or
@@ -1317,5 +1341,3 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
 }
 
 }  // namespace mi
-
-inline mi_setup_s::~mi_setup_s() { release_lanes(); }

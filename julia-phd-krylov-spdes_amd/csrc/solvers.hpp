@@ -20,12 +20,8 @@
 
 #include "eig_kernels.hpp"
 #include "operators.hpp"
-#ifdef MI355_EXPERIMENTAL
-#include "resident.hpp"   // persistent on-chip PCG: measured and not adopted (profiles/NOTES.md); `make EXPERIMENTAL=1`
-#endif
 
 namespace mi {
-
 
 constexpr int64_t RES_STAGE = 8192;
 constexpr int CF_VEC_GRID = 256;  // workgroups of the vector half of the 2-launch sparse pcg (8 XCDs x 32) = partials per dot (<= NT)
@@ -38,93 +34,6 @@ struct GraphKey {
     return std::tie(A, M, nvec, chunk, tag) < std::tie(o.A, o.M, o.nvec, o.chunk, o.tag);
   }
 };
-
-#ifdef MI355_EXPERIMENTAL
-// Host side of the persistent on-chip PCG (resident.hpp): which rows of which subdomain every workgroup owns, how many
-// of them fit into registers / LDS, and the hand-off buffers of the grid barrier.
-struct ResidentPlan {
-  int G = 0, max_rows = 0;
-  double resident_frac = 0.0;   // share of the matrix elements held in registers or LDS or passing through the streaming slot
-  bool usable = false;
-  unsigned long long epoch = 16;   // records are zero-initialised: epochs start above 0
-  DevBuf<ResTile> tiles;
-  DevBuf<ResRec> recs;
-  DevBuf<int> abort;
-  std::vector<ResTile> tiles_h;
-
-  ResidentPlan(mi_ctx_s *c, const DenseBlockOp &A, const DenseBlockOp &M) {
-    hipDeviceProp_t prop;
-    MI_HIP(hipGetDeviceProperties(&prop, c->device));
-    G = env_int("MI355_RES_G", prop.multiProcessorCount);
-    const int ndl = A.maps.ndl;
-    if (G < 1 || ndl < 1 || ndl > G || G > RES_NTH) return;   // one published record per thread when polling
-    // workgroups per subdomain in proportion to its elements, at least one each, G in all
-    std::vector<double> wgt(ndl);
-    double tot = 0.0;
-    for (int d = 0; d < ndl; ++d) { wgt[d] = (double)A.maps.nd[d] * A.ld_h[d]; tot += wgt[d]; }
-    if (tot <= 0.0) return;
-    std::vector<int> gd(ndl);
-    int used = 0;
-    for (int d = 0; d < ndl; ++d) { gd[d] = std::max(1, (int)(G * wgt[d] / tot)); used += gd[d]; }
-    while (used > G) {   // over-subscribed by the "at least one" rule: take from the subdomain with the fewest rows per workgroup
-      int best = -1; double v = 1e300;
-      for (int d = 0; d < ndl; ++d) if (gd[d] > 1 && wgt[d] / gd[d] < v) { v = wgt[d] / gd[d]; best = d; }
-      if (best < 0) return;
-      --gd[best]; --used;
-    }
-    while (used < G) {   // hand the spare workgroups to the subdomains with the most elements per workgroup
-      int best = 0; double v = -1.0;
-      for (int d = 0; d < ndl; ++d) if (wgt[d] / gd[d] > v) { v = wgt[d] / gd[d]; best = d; }
-      ++gd[best]; ++used;
-    }
-    for (int d = 0; d < ndl; ++d) {
-      const int n_d = A.maps.nd[d], ld = A.ld_h[d];
-      if (ld != M.ld_h[d] || (ld + 127) / 128 > RES_MAX_U) return;
-      const int rpw = (n_d + gd[d] - 1) / gd[d];
-      for (int k = 0; k < gd[d]; ++k) {
-        ResTile t{};
-        t.matS = A.moff_h[d]; t.matP = M.moff_h[d];
-        t.n = n_d; t.ld = ld; t.loc_off = A.maps.loc_off[d];
-        t.row0 = std::min(k * rpw, n_d);
-        t.nrows = std::max(0, std::min(rpw, n_d - t.row0));
-        t.U = res_variant(std::max(1, (ld + 127) / 128));
-        max_rows = std::max(max_rows, t.nrows);
-        tiles_h.push_back(t);
-      }
-    }
-    max_rows = std::max(8, (max_rows + 7) / 8 * 8);
-    double res_el = 0.0, all_el = 0.0;
-    for (auto &t : tiles_h) {
-      const long long fixed = (long long)res_lds_fixed(t.U, max_rows), rowb = (long long)t.U * 128 * 8;
-      if (fixed > RES_LDS_BYTES) return;
-      const int cap = (int)((RES_LDS_BYTES - fixed) / rowb);
-      const int needS = std::max(0, t.nrows - res_reg_rows_S(t.U)), needP = std::max(0, t.nrows - res_reg_rows_P(t.U));
-      t.ldsS = std::min(needS, cap / 2);
-      t.ldsP = std::min(needP, cap - t.ldsS);
-      t.ldsS = std::min(needS, cap - t.ldsP);
-      res_el += (double)(std::min(t.nrows, res_reg_rows_S(t.U) + t.ldsS) + std::min(t.nrows, res_reg_rows_P(t.U) + t.ldsP)) * t.ld;
-      all_el += 2.0 * t.nrows * t.ld;
-    }
-    resident_frac = all_el > 0 ? res_el / all_el : 0.0;
-    tiles.upload(tiles_h, c->stream);
-    recs.alloc((size_t)4 * G); recs.zero(c->stream);
-    abort.alloc(1); abort.zero(c->stream);
-    static bool attr_set = false;
-    if (!attr_set) {
-      MI_HIP(hipFuncSetAttribute((const void *)k_pcg_resident, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES));
-      attr_set = true;
-    }
-    MI_HIP(hipStreamSynchronize(c->stream));
-    usable = resident_frac * 100.0 >= env_int("MI355_RES_MIN_PCT", 50);
-  }
-  void reset(hipStream_t s) {  // after an aborted launch
-    abort.zero(s);
-    epoch += 1u << 20;
-  }
-};
-#else
-struct ResidentPlan { bool usable = false; };   // (EXPERIMENTAL builds only)
-#endif
 
 struct SolverWorkspace {
   int64_t n = 0;
@@ -176,7 +85,6 @@ struct SolverWorkspace {
   std::map<GraphKey, hipGraphExec_t> graphs;
   std::map<GraphKey, int> predicted;  // loop iterations the last solve with this (A, M, nvec) took
   std::map<GraphKey, bool> zero_x0;   // ... and whether its initial guess was identically zero (whole-solve graphs)
-  std::map<std::pair<const Operator *, const Operator *>, std::unique_ptr<ResidentPlan>> resident;  // per (S, ΠS) pair
 
   explicit SolverWorkspace(int64_t n_) : n(n_), g(vec_grid(n_)) {
     auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
@@ -219,9 +127,6 @@ struct SolverWorkspace {
       else ++it;
     for (auto it = zero_x0.begin(); it != zero_x0.end();)
       if (it->first.A == op || it->first.M == op) it = zero_x0.erase(it);
-      else ++it;
-    for (auto it = resident.begin(); it != resident.end();)
-      if (it->first.first == op || it->first.second == op) it = resident.erase(it);
       else ++it;
   }
   void ensure_deflation(int nvec) {
@@ -319,18 +224,6 @@ struct Krylov {
     const double *dv = nullptr;
     if (!fused && nvec == 0 && A->as_csr() && A->as_csr()->nblocks > 0 && (!M || M->diag_kind(&dv) != 0) && !env_int("MI355_NO_CSRFOLD", 0))
       Ac = A->as_csr();
-  }
-  // pcg on one GPU with both operators dense on the same maps: the whole solve as one persistent launch with the blocks
-  // held in registers / LDS (resident.hpp), when enough of them fit on the chip. nullptr: not applicable.
-  ResidentPlan *resident_plan() {
-#ifndef MI355_EXPERIMENTAL
-    return nullptr;
-#else
-    if (!fold || Md->f32() || nvec > 0 || eig.tag || ctx->has_comm() || Ad->reduce_over_ranks || !env_int("MI355_RESIDENT", 0) || env_int("MI355_NO_RESIDENT", 0)) return nullptr;
-    auto &slot = ws.resident[{A, M}];
-    if (!slot) slot.reset(new ResidentPlan(ctx, *Ad, *Md));
-    return slot->usable ? slot.get() : nullptr;
-#endif
   }
   // peer exchange with the waits inside the launches: every sharded operator of the loop stores into the arenas itself
   bool inwait() const {
@@ -729,7 +622,7 @@ struct Krylov {
     // Undeflated solves on one GPU: entry kernel, set-up, iterations and exit kernel are ONE graph replay whose per-call
     // arguments travel through a pinned block, and the host waits for the exit kernel's last store instead of the stream.
     const bool whole_on = !env_int("MI355_NO_WHOLE_GRAPH", 0);
-    const bool whole = whole_on && use_graph && nvec == 0 && !eig.tag && !ctx->has_comm() && !resident_plan();
+    const bool whole = whole_on && use_graph && nvec == 0 && !eig.tag && !ctx->has_comm();
     if (whole) prepare(maxit, eps, cap_dev);
     else begin(b_in, x_io, W_in, maxit, eps, cap_dev);
 
@@ -741,45 +634,6 @@ struct Krylov {
                          spec_res ? ws.res_stage : (double *)nullptr, (long long)ncap, &ws.flags[slot], &ws.st->x0_zero);
       MI_HIP(hipGetLastError());
     };
-    bool ran_resident = false;
-#ifdef MI355_EXPERIMENTAL
-    if (ResidentPlan *rp = resident_plan()) {
-      // One persistent launch for the whole solve. It clears `done` itself only by setting it at the end: an aborted
-      // launch (bounded spin expired: the workgroups were not all resident) leaves done = 0 and the loops below take over.
-      ResArgs ra{};
-      ra.MS = Ad->M.p; ra.MP = Md->M.p; ra.tiles = rp->tiles.p; ra.gidx = Ad->maps.gidx.p; ra.cnt = Md->cnt.p;
-      ra.tgt = Ad->maps.tgt.p; ra.jrank = Ad->maps.jrank.p; ra.conS = Ad->fold_con(); ra.conP = Md->fold_con();
-      ra.recs = rp->recs.p; ra.abort = rp->abort.p; ra.st = ws.st; ra.res_norm = ws.res_norm.p;
-      ra.x = ws.x; ra.b = ws.b; ra.epoch0 = rp->epoch; ra.W = Ad->maps.slot_width; ra.G = rp->G; ra.max_rows = rp->max_rows;
-      DevBuf<long long> dbg;
-      const bool debug = env_int("MI355_RES_DEBUG", 0) != 0;
-      if (debug) { dbg.alloc(512); dbg.zero(s); ra.dbg = dbg.p; ra.dbg_wg = env_int("MI355_RES_DEBUG_WG", 0); }
-      hipLaunchKernelGGL(k_pcg_resident, dim3(rp->G), dim3(RES_NTH), RES_LDS_BYTES, s, ra);
-      MI_HIP(hipGetLastError());
-      enqueue_results(0);
-      MI_HIP(hipStreamSynchronize(s));
-      if (debug) {  // wall-clock stamps (100 MHz) of one workgroup: 5 for the set-up, then 8 per iteration
-        std::vector<long long> h(512);
-        memcpy_sync(h.data(), dbg.p, 512 * sizeof(long long), hipMemcpyDeviceToHost);
-        const ResTile &tt = rp->tiles_h[ra.dbg_wg];
-        std::fprintf(stderr, "[resident] wg %d: n=%d ld=%d rows=%d U=%d regS=%d regP=%d ldsS=%d ldsP=%d resident_frac=%.3f\n", ra.dbg_wg, tt.n,
-                     tt.ld, tt.nrows, tt.U, RES_WAVES * res_slots_S(tt.U), RES_WAVES * res_slots_P(tt.U), tt.ldsS, tt.ldsP, rp->resident_frac);   // (+8 rows per operator in the streaming slot)
-        std::fprintf(stderr, "[resident] stamps (us since start):");
-        for (int k = 0; k < 512 && h[k]; ++k) std::fprintf(stderr, "%s%.2f", (k >= 5 && (k - 5) % 8 == 0) ? "\n  " : " ", (h[k] - h[0]) * 0.01);
-        std::fprintf(stderr, "\n");
-      }
-      if (ws.flags[0].done) {
-        rp->epoch += (unsigned long long)(2 * ws.flags[0].it + 4);
-        ran_resident = true;
-        use_graph = false;
-      } else {
-        rp->reset(s);
-        rp->usable = false;   // this context does not get all the CUs: stay with the graph loop from now on
-        int64_t mx = maxit, cd = 0; double e = eps;
-        begin(b_in, x_io, W_in, mx, e, cd);   // x0, b and the state block as they were
-      }
-    }
-#endif
     if (use_graph) {
       const GraphKey pk{A, M, nvec, 0};
       int &predicted = ws.predicted[pk];
@@ -857,7 +711,7 @@ struct Krylov {
       predicted = (int)std::max<long long>(1, ws.flags[0].it - ((fold || csrfold()) ? 0 : 1));  // the folded pairs check the stop rule one launch later
       }
     }
-    if (!use_graph && !ran_resident) {
+    if (!use_graph) {
       setup_tail();
       for (int64_t l = 0; l < maxit + 2; ++l) {
         fetch_flags(0);

@@ -40,7 +40,7 @@ def _csc(M, n, m):
 
 
 def bfs_levels(A_II, A_IΓ):
-    """The plan's breadth-first levels (setup_dense.hpp): seeds = rows of A_IΓ holding an entry, each level sorted."""
+    """The plan's breadth-first levels (setup_plan.hpp): seeds = rows of A_IΓ holding an entry, each level sorted."""
     A = sp.csr_matrix(A_II)
     seen = np.full(A.shape[0], -1)
     front = np.unique(sp.csc_matrix(A_IΓ).indices)

@@ -4,6 +4,7 @@
 __device__ long long gj_stamps[16 * 8];
 #define GJ_STAMP(i) do { if (threadIdx.x == 0) gj_stamps[s * 8 + (i)] = wall_clock64(); } while (0)
 #include "../../julia-phd-krylov-spdes_amd/csrc/setup_gj.hpp"
+#include "../../julia-phd-krylov-spdes_amd/csrc/pinv_spectral.hpp"
 #include <cstdio>
 using namespace mi;
 __global__ __launch_bounds__(256) void k_probe(const double *A, double *out, long long *stamps) {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device set-up of the assembled mode at config 3: time per realization for several stream counts, and which of the two
+"""Device set-up of the assembled mode at config 3: time per realization, and which of the two
 dense eliminations (device level recursion, host level recursion through torch) is closer to an independent reference
 (S_d v computed with sparse direct interior solves)."""
 import os
@@ -24,22 +24,20 @@ P = fem.build_schur_problem(N, 4, 2, np.exp(g), lambda x, y: -1.0 + 0 * x, lambd
 print(f"host build_schur_problem: {time.perf_counter() - t0:.1f} s", flush=True)
 sub = P.sub
 ctx = api.Context(0)
-for lanes in (1,):
-    os.environ["MI355_SETUP_STREAMS"] = str(lanes)
+t0 = time.perf_counter()
+setup = api.SchurSetup(ctx, P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd)
+tp = time.perf_counter() - t0
+vals = [torch.from_numpy(v).cuda() for v in setup._vals]
+bI = torch.from_numpy(np.concatenate(P.b_Id)).cuda()
+t0 = time.perf_counter(); setup.run(*vals, bI); ctx.synchronize()
+print(f"  first (eager) run {time.perf_counter() - t0:.2f} s", flush=True)
+ts = []
+for _ in range(3):
     t0 = time.perf_counter()
-    setup = api.SchurSetup(ctx, P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd)
-    tp = time.perf_counter() - t0
-    vals = [torch.from_numpy(v).cuda() for v in setup._vals]
-    bI = torch.from_numpy(np.concatenate(P.b_Id)).cuda()
-    t0 = time.perf_counter(); setup.run(*vals, bI); ctx.synchronize()
-    print(f"  first (eager) run {time.perf_counter() - t0:.2f} s", flush=True)
-    ts = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        Sd, w = setup.run(*vals, bI)
-        ctx.synchronize()
-        ts.append(time.perf_counter() - t0)
-    print(f"lanes={lanes}: plan {tp:.2f} s, S_d + w_d {min(ts) * 1e3:.1f} ms per realization", flush=True)
+    Sd, w = setup.run(*vals, bI)
+    ctx.synchronize()
+    ts.append(time.perf_counter() - t0)
+print(f"plan {tp:.2f} s, S_d + w_d {min(ts) * 1e3:.1f} ms per realization", flush=True)
 t0 = time.perf_counter()
 Pi = api.nn_pinv(ctx, sub.n_Γd, Sd); ctx.synchronize()
 print(f"pinv: {(time.perf_counter() - t0) * 1e3:.1f} ms", flush=True)
