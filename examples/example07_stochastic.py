@@ -19,6 +19,11 @@ and record the iteration counts. With --gg, also the second loop's solves precon
     pcg(S, b_schur, 0, A_ΓΓ_t)        (Example07:416)   A_ΓΓ of this realization
 with `M \\ r` by the device sparse direct solve (api.SparseDirectPreconditioner, refilled per realization by set_values:
 from `prepare_global_schur` on the host, or with --device-setup from the device assembly through fem.gamma_gather_map).
+With --matrix-free-amg, also
+    pcg(S_t, b_schur, 0, ΠSnn_0)      S_t matrix-free: apply_local_schurs with `cg(A_IId, rhs; Pl = Π_IId, reltol)` inside
+                                      (EPDD.jl:648-650), Π_IId the AMG preconditioner Example07:174 rebuilds per
+                                      realization — here one hierarchy of blockdiag(A_IIdd) on the device
+                                      (MatrixFreeLocalSchurs.interior_amg), its numbers redone by set_values
 Realizations are independent: under torch.distributed.run each rank takes
 realizations rank, rank+world, ... on its own GPU (replicas only, no collective in the solve).
 
@@ -66,6 +71,9 @@ def main():
     ap.add_argument("--kl", default="", help="root file name of KL modes written by examples/example04_kl.py (Example07:124-125 reads "
                                              "data/$root_fname.kl-eigvals.npz / .kl-eigvecs.npz); default: fem.synthetic_kl")
     ap.add_argument("--kl-dir", default="data")
+    ap.add_argument("--matrix-free-amg", action="store_true",
+                    help="also pcg(S_t, b_schur, 0, ΠSnn_0) with S_t matrix-free, its interior CG preconditioned by the AMG `Pl` "
+                         "(interior_amg; set_values refreshes the hierarchy on the device every realization)")
     ap.add_argument("--gg", action="store_true", help="also pcg(S, b_schur, 0, A_ΓΓ_0) and pcg(S, b_schur, 0, A_ΓΓ_t) (Example07:412, 416)")
     args = ap.parse_args()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -125,6 +133,14 @@ def main():
         if args.device_setup:
             gmap = fem.gamma_gather_map(plan.patterns["ΓΓ"], sub.gather_idx, n_Γ, offsets=[o for o, _ in plan.layout["ΓΓ"]])
             assert np.array_equal(gmap.indptr, A_gg0.indptr) and np.array_equal(gmap.indices, A_gg0.indices)
+    S_mf, iters_mf = None, []
+    if args.matrix_free_amg:
+        S_mf = api.MatrixFreeLocalSchurs(ctx, P0.A_IIdd, P0.A_IΓdd, P0.A_ΓΓdd, sub.gather_idx, sub.node_Γ_cnt, None, reltol=1e-9)
+        print(f"[rank {rank}] interior AMG: {S_mf.interior_amg(P0.A_IIdd)}", flush=True)
+
+    def csc_values(mats):
+        return np.concatenate([np.asarray(sp.csc_matrix(A).sorted_indices().data, dtype=np.float64) for A in mats])
+
     iters_0, iters_t, iters_def, iters_rec, iters_gg0, iters_ggt = [], [], [], [], [], []
     W_rec, nvec, spdim = None, int(1.25 * ndom), 3 * ndom
     for ireal in range(rank, args.nreals, world):
@@ -147,6 +163,8 @@ def main():
             S, ΠSnn_t, ΠSnn_t_f32 = S_dev, NN_dev, NN_dev_f32
             if M_ggt is not None:
                 M_ggt.set_values(gmap.values(vals))                                                    # A_ΓΓ_t = Σ_d R_d' A_ΓΓdd R_d
+            if S_mf is not None:
+                S_mf.set_values(ii, ig, gg)                                                            # :162-174 without a host trip
         else:
             blocks = plan.blocks(dev_plan.run(np.exp(gs[ireal]))) if plan else None                   # :162-171 on the GPU
             P = fem.build_schur_problem(args.N, args.px, args.py, np.exp(gs[ireal]), f, uexact, mesh=mesh,
@@ -160,10 +178,17 @@ def main():
                 A_ggt = sp.csc_matrix(fem.prepare_global_schur(mesh.cells, mesh.points, P0.epart, sub, np.exp(gs[ireal]), f, uexact)[2])
                 A_ggt.sort_indices()
                 M_ggt.set_values(A_ggt.data)
+            if S_mf is not None:
+                S_mf.set_values(csc_values(P.A_IIdd), csc_values(P.A_IΓdd), csc_values(P.A_ΓΓdd))
         x0 = np.zeros(n_Γ)
         iters_0.append(api.pcg(S, b_schur, x0, ΠSnn_0)[1])                                            # :273
         iters_t.append(api.pcg(S, b_schur, x0, ΠSnn_t)[1])                                            # :277
         iters_def.append(api.defpcg(S, b_schur, x0, W_0, ΠSnn_0)[1])
+        mf = ""
+        if S_mf is not None:
+            i0 = S_mf.interior_iterations()
+            iters_mf.append(api.pcg(S_mf, b_schur, x0, ΠSnn_0)[1])
+            mf = f"  matrix-free S_t, AMG Pl: pcg(NN_0) it={iters_mf[-1]} ({S_mf.interior_iterations() - i0} interior iterations)"
         f32 = ""
         if args.nn_f32:
             iters_0_f32.append(api.pcg(S, b_schur, x0, ΠSnn_0_f32)[1])
@@ -189,10 +214,10 @@ def main():
             iters_ggt.append(api.pcg(S, b_schur, x0, M_ggt)[1])                                       # :416
             gg = f"  pcg(A_GG_0) it={iters_gg0[-1]}  pcg(A_GG_t) it={iters_ggt[-1]}"
         print(f"[rank {rank}] realization {ireal}: pcg(NN_0) it={iters_0[-1]}  pcg(NN_t) it={iters_t[-1]}  "
-              f"defpcg(W_0, NN_0) it={iters_def[-1]}{f32}{rec}{gg}", flush=True)
+              f"defpcg(W_0, NN_0) it={iters_def[-1]}{mf}{f32}{rec}{gg}", flush=True)
     if args.out:                                                                                       # :281-285 npz of iteration counts
         np.savez(args.out.format(rank=rank), iters_0=iters_0, iters_t=iters_t, iters_def=iters_def, iters_rec=iters_rec,
-                 iters_gg0=iters_gg0, iters_ggt=iters_ggt)                                          # (:423-424: io.save_pcg_iters(..., precond="A_GG"))
+                 iters_gg0=iters_gg0, iters_ggt=iters_ggt, iters_mf=iters_mf)                                          # (:423-424: io.save_pcg_iters(..., precond="A_GG"))
     if args.nn_f32:
         for tag, i64_, i32_ in (("NN_0", iters_0, iters_0_f32), ("NN_t", iters_t, iters_t_f32)):
             print(f"nn-f32 {tag}: fp64 [{' '.join(map(str, i64_))}] fp32 [{' '.join(map(str, i32_))}]")

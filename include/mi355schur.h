@@ -353,6 +353,28 @@ int mi_schur_global_device_create(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, c
 int mi_schur_interior_precond(mi_op_t op, int kind);
 /* Diagnostic: iterations the interior CG of such an operator has run so far (slowest subdomain, rounded up to replays). */
 int mi_schur_interior_iterations(mi_op_t op, int64_t *iterations);
+/* mi_schur_interior_amg — Pl = smoothed-aggregation AMG in that interior CG: the reference's own choice, the Π_IId of
+ * `IterativeSolvers.cg(A_IId, rhs; Pl = Π_IId, reltol)` (EPDD.jl:609-619, 648-650, 813-815, 1021; Example07:174), for an operator
+ * of mi_schur_matfree_device_create or mi_schur_global_device_create. ONE hierarchy of the stacked block-diagonal matrix
+ * A_II = blockdiag(A_IIdd) of the operator's subdomains, built on the device from the operator's own pattern and current values
+ * by the machinery of mi_amg_plan_create: n_l[nlevels] the level sizes (n_l[0] = Σ_d n_i[d]), agg[l] (n_l[l] entries,
+ * l < nlevels - 1) the aggregate of every stacked node of level l, `index_base`-based. ω_l is the Gershgorin maximum over all
+ * subdomains and the coarsest level has one dense inverse: the result is a block-diagonal SPD operator, so the subdomains'
+ * iterations stay independent (it differs from a hierarchy per subdomain in ω_l and in the level count). One V(1,1) cycle per
+ * iteration on the whole stacked vector; the loop always has three launches plus the cycle's per iteration (MI355_ICG_FUSED is
+ * ignored meanwhile) and 4 iterations per graph replay unless MI355_ICG_CHUNK says otherwise.
+ *   MI_ERR_BAD_ARG: a host-callback operator, a sharded operator, a context with a communicator, everything
+ *                   mi_amg_plan_create refuses (level sizes, aggregate ids, an A_II pattern that is not sorted or not
+ *                   structurally symmetric), an aggregate that holds nodes of two subdomains.
+ *   MI_ERR_SINGULAR: as mi_amg_plan_create. Either way the `Pl` selected before stays.
+ * A later mi_schur_interior_precond(op, 0 | 1) deselects it and releases the hierarchy.
+ * mi_schur_matfree_set_values(ii_val != NULL) then redoes the numbers of the hierarchy on the device for the new values (host
+ * or device pointer, as the context's pointer mode says) BEFORE it stores anything: when the refresh fails (MI_ERR_SINGULAR:
+ * a diagonal entry of a level that is not positive, a value that is not finite, a coarse inverse that fails its certificate)
+ * the call returns the error and the operator — matrices, diagonal, hierarchy — is the one of before.
+ * mi_schur_interior_amg_stats: levels, rows of the coarsest level, bytes the hierarchy keeps (any pointer may be NULL). */
+int mi_schur_interior_amg(mi_op_t op, int64_t nlevels, const int64_t *n_l, const int64_t *const *agg, int index_base);
+int mi_schur_interior_amg_stats(mi_op_t op, int64_t *levels, int64_t *coarse_n, int64_t *bytes_kept);
 
 int mi_op_size(mi_op_t op, int64_t *n);
 /* y = A*x (operator) or y = M \ x (preconditioner); x and y must not alias. */

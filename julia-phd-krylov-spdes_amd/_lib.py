@@ -124,6 +124,8 @@ SIGNATURES = {
     "mi_schur_matfree_interior_solutions": [vp, vp, vp, vp],
     "mi_schur_interior_precond": [vp, C.c_int],
     "mi_schur_interior_iterations": [vp, i64p],
+    "mi_schur_interior_amg": [vp, i64, i64p, i64pp, C.c_int],
+    "mi_schur_interior_amg_stats": [vp, i64p, i64p, i64p],
     "mi_eigcg": [vp, vp, vp, i64, i64, i64, C.c_double, f64p, i64, i64p, vp],
     "mi_eigpcg": [vp, vp, vp, vp, i64, i64, i64, C.c_double, f64p, i64, i64p, vp],
     "mi_eigdefcg": [vp, vp, vp, vp, i64, i64, i64, C.c_double, f64p, i64, i64p, vp],

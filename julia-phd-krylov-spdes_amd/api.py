@@ -914,6 +914,7 @@ class MatrixFreeLocalSchurs(Operator):
         ndom = len(A_IΓdd)
         n_Γ = len(node_Γ_cnt)
         lo, hi = _dom_slice(ctx, ndom, dom_slice)
+        self._dom = (lo, hi)
         g = [_i64(a) for a in ind_Γd_Γ2l]
         nd = _i64([a.size for a in g])
         ni = _i64([A.shape[0] for A in A_IIdd])
@@ -1003,8 +1004,42 @@ def _interior_iterations(self) -> int:
     return int(out.value)
 
 
+def _interior_amg(self, A_IIdd=None, max_levels: int = 10, max_coarse: int = 256, sizes=None, aggregates=None, index_base: int = 0):
+    """`Pl` = smoothed-aggregation AMG for the device interior CG (`mi_schur_interior_amg`): the reference's own `Pl`, the
+    Π_IId of `IterativeSolvers.cg(A_IId, rhs; Pl = Π_IId, reltol)` (Example07:174). `A_IIdd`: the blocks the operator was
+    made from — `fem.prepare_interior_amg(A_IIdd, max_levels, max_coarse)` aggregates their stacked pattern on the host,
+    the numbers of the ONE hierarchy of blockdiag(A_IIdd) are made on the device from the operator's current values, and
+    `set_values(ii_val=...)` redoes them for every realization. `sizes=, aggregates=` (0-based) instead of `A_IIdd` freeze
+    aggregates from elsewhere; `index_base=1` sends them 1-based, as the Julia shim does. `interior_precond(None |
+    "diagonal")` switches back and releases the hierarchy. Returns `interior_amg_stats()`."""
+    if aggregates is None:
+        if A_IIdd is None:
+            raise TypeError("interior_amg: the blocks A_IIdd, or sizes= and aggregates=")
+        from . import fem
+        lo, hi = getattr(self, "_dom", (0, len(A_IIdd)))
+        sizes, aggregates = fem.prepare_interior_amg(list(A_IIdd)[lo:hi], max_levels=max_levels, max_coarse=max_coarse)
+    elif sizes is None:
+        raise TypeError("interior_amg: aggregates= needs sizes= (the level sizes)")
+    aggs = [_i64(a).ravel() + index_base for a in aggregates]
+    n_l = _i64(sizes)
+    if len(aggs) != len(n_l) - 1 or any(a.size != n for a, n in zip(aggs, n_l)):
+        raise ValueError("interior_amg: one aggregate array per smoothed level, one id per node of the level")
+    check(self.ctx._L.mi_schur_interior_amg(self._h, i64(len(n_l)), n_l.ctypes.data_as(i64p), _ptrs(aggs, i64p) if aggs else None,
+                                            C.c_int(index_base)))
+    return self.interior_amg_stats()
+
+
+def _interior_amg_stats(self) -> dict:
+    """dict(levels, coarse_n, bytes_kept) of the AMG `Pl` selected (`mi_schur_interior_amg_stats`)."""
+    a, b, c = i64(), i64(), i64()
+    check(self.ctx._L.mi_schur_interior_amg_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+    return dict(levels=int(a.value), coarse_n=int(b.value), bytes_kept=int(c.value))
+
+
 MatrixFreeLocalSchurs.interior_precond = _interior_precond
 MatrixFreeLocalSchurs.interior_iterations = _interior_iterations
+MatrixFreeLocalSchurs.interior_amg = _interior_amg
+MatrixFreeLocalSchurs.interior_amg_stats = _interior_amg_stats
 
 
 class LocalSchur(MatrixFreeLocalSchurs):
@@ -1251,6 +1286,8 @@ GlobalSchur.interior_solutions = _interior_solutions      # `get_subdomain_solut
 GlobalSchur.schur_rhs = MatrixFreeLocalSchurs.schur_rhs   # `get_schur_rhs` (EPDD.jl:798-821)
 GlobalSchur.interior_precond = _interior_precond
 GlobalSchur.interior_iterations = _interior_iterations
+GlobalSchur.interior_amg = _interior_amg
+GlobalSchur.interior_amg_stats = _interior_amg_stats
 
 
 # reference-named free functions

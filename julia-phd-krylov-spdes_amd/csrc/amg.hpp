@@ -103,6 +103,23 @@ __global__ __launch_bounds__(NT) void k_amg_post(MI_AMG_CSR_ARGS, const double *
   amg_block_rows(nblocks, blk, rowptr, col, val, prod, [&](int c) { return x[c]; },
                  [&](int i, double s) { y[i] = x[i] + wd[i] * (b[i] - s); });
 }
+// the level-0 post-smoothing of a cycle inside the interior CG (interior_amg.hpp): as k_amg_post, and the row epilogue also
+// sums b_i y_i = r_i z_i over the rows of the block, thread by thread in ascending row, then the fixed tree of block_sum:
+// part[block]. The row blocks are cut at subdomain boundaries, so a subdomain's r'z is a run of these partials.
+__global__ __launch_bounds__(NT) void k_amg_post_dot(MI_AMG_CSR_ARGS, const double *__restrict__ wd, const double *__restrict__ b,
+                                                     const double *__restrict__ x, double *__restrict__ y, double *__restrict__ part,
+                                                     const int *done) {
+  if (done && *done) return;
+  __shared__ __attribute__((aligned(16))) double prod[SPMV_TILE];
+  __shared__ double sm[NT / 64 + 1];
+  double by = 0.0;
+  amg_block_rows(nblocks, blk, rowptr, col, val, prod, [&](int c) { return x[c]; },
+                 [&](int i, double s) { const double bi = b[i], yi = x[i] + wd[i] * (bi - s); y[i] = yi; by += bi * yi; });
+  const int bl = (int)(blockIdx.x & 7) * ((nblocks + 7) >> 3) + (int)(blockIdx.x >> 3);   // the block amg_block_rows worked on
+  if (bl >= nblocks) return;
+  by = block_sum(by, sm);
+  if (threadIdx.x == 0) part[bl] = by;
+}
 #undef MI_AMG_CSR_ARGS
 // y = Z b for the symmetric n x n inverse of the coarsest level (column j of the column-major Z is its row j): one wave per
 // row, lane q sums the columns q, q + 64, ... in ascending order, then the fixed shuffle tree.
@@ -118,6 +135,24 @@ __global__ __launch_bounds__(NT) void k_amg_coarse(int n, const double *__restri
   if (lane == 0) y[row] = s;
 }
 
+// The same for the inverse of a block-diagonal coarsest level (the stacked A_II of the interior CG): row i takes the columns
+// of its own subdomain only, dom[j] == dom[i]. The entries left out are the zeros of the inverse, and a value that is not
+// finite in one subdomain's right-hand side stays in that subdomain. With `rz`: rz[i] = b_i y_i (a one-level hierarchy has
+// no post-smoothing launch to leave the partials of r'z; the interior CG then sums these row by row).
+__global__ __launch_bounds__(NT) void k_amg_coarse_dom(int n, const double *__restrict__ Z, const int *__restrict__ dom, const double *__restrict__ b,
+                                                       double *__restrict__ y, double *__restrict__ rz, const int *done) {
+  if (done && *done) return;
+  const int row = (int)blockIdx.x * (NT / 64) + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= n) return;
+  const double *z = Z + (size_t)row * n;
+  const int dr = dom[row];
+  double s = 0.0;
+  for (int j = lane; j < n; j += 64)
+    if (dom[j] == dr) s += z[j] * b[j];
+  s = wave_sum(s);
+  if (lane == 0) { y[row] = s; if (rz) rz[row] = b[row] * s; }
+}
+
 struct AmgOp : Operator {
   struct Level {
     CsrDev A, P, R;          // P, R = P' and the smoother only below the coarsest level
@@ -127,6 +162,7 @@ struct AmgOp : Operator {
   };
   std::vector<Level> lv;
   DevBuf<double> zinv, sink_x, sink_r;
+  DevBuf<int> coarse_dom;   // interior_amg.hpp: the subdomain of every row of the coarsest level (empty: one dense inverse)
   int nlev = 0, nc = 0;
   int64_t op_nnz = 0, kept = 0, alg = 0, dom = 0;
   HostCsr coarse_h;   // A of the coarsest level as given (the cycle needs only its inverse): read back by mi_amg_level_get
@@ -253,12 +289,17 @@ struct AmgOp : Operator {
 
   static int grid_of(const CsrDev &M) { return ((M.nblocks + 7) / 8) * 8; }
 #define MI_AMG_CSR(M) (M).nblocks, (const SpmvBlock *)(M).blk.p, (const int *)(M).rowptr.p, (const int *)(M).col.p, (const double *)(M).val.p
-  void coarse(const double *b, double *y, const int *done) {
-    hipLaunchKernelGGL(k_amg_coarse, dim3((nc + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, ctx->stream, nc, (const double *)zinv.p, b, y, done);
+  void coarse(const double *b, double *y, const int *done, double *rz = nullptr) {
+    const dim3 grid((nc + NT / 64 - 1) / (NT / 64));
+    if (coarse_dom.p) hipLaunchKernelGGL(k_amg_coarse_dom, grid, dim3(NT), 0, ctx->stream, nc, (const double *)zinv.p, (const int *)coarse_dom.p, b, y, rz, done);
+    else hipLaunchKernelGGL(k_amg_coarse, grid, dim3(NT), 0, ctx->stream, nc, (const double *)zinv.p, b, y, done);
   }
-  void apply(const double *r, double *z, const int *done) override {
+  void apply(const double *r, double *z, const int *done) override { cycle(r, z, done, nullptr); }
+  // one cycle; `rz_part` (interior_amg.hpp, needs coarse_dom): also the partials of r'z — per row block of A_0, or per row of
+  // a one-level hierarchy
+  void cycle(const double *r, double *z, const int *done, double *rz_part) {
     hipStream_t s = ctx->stream;
-    if (nlev == 1) { coarse(r, z, done); MI_HIP(hipGetLastError()); return; }
+    if (nlev == 1) { coarse(r, z, done, rz_part); MI_HIP(hipGetLastError()); return; }
     for (int l = 0; l < nlev - 1; ++l) {
       Level &L = lv[(size_t)l], &N = lv[(size_t)l + 1];
       const double *b = l ? L.b.p : r;
@@ -271,8 +312,12 @@ struct AmgOp : Operator {
       Level &L = lv[(size_t)l], &N = lv[(size_t)l + 1];
       const double *b = l ? L.b.p : r;
       hipLaunchKernelGGL(k_amg_prolong, dim3(grid_of(L.P)), dim3(NT), 0, s, MI_AMG_CSR(L.P), (const double *)N.y.p, L.x.p, done);
-      hipLaunchKernelGGL(k_amg_post, dim3(grid_of(L.A)), dim3(NT), 0, s, MI_AMG_CSR(L.A), (const double *)L.wd.p, b, (const double *)L.x.p,
-                         l ? L.y.p : z, done);
+      if (l == 0 && rz_part)
+        hipLaunchKernelGGL(k_amg_post_dot, dim3(grid_of(L.A)), dim3(NT), 0, s, MI_AMG_CSR(L.A), (const double *)L.wd.p, b, (const double *)L.x.p, z,
+                           rz_part, done);
+      else
+        hipLaunchKernelGGL(k_amg_post, dim3(grid_of(L.A)), dim3(NT), 0, s, MI_AMG_CSR(L.A), (const double *)L.wd.p, b, (const double *)L.x.p,
+                           l ? L.y.p : z, done);
     }
     MI_HIP(hipGetLastError());
   }

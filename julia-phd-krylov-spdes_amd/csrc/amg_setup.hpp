@@ -159,8 +159,8 @@ struct AmgPlanOp : AmgOp {
   static int grid(int64_t m) { return (int)((std::max<int64_t>(m, 1) + AS_NT - 1) / AS_NT); }
 
   AmgPlanOp(mi_ctx_s *c, int64_t n0, const int64_t *rowptr, const int64_t *colidx, const double *val, int64_t nlevels, const int64_t *n_l,
-            const int64_t *const *agg, int base)
-      : AmgOp(c, n0) {
+            const int64_t *const *agg, int base, const std::vector<int> *breaks0 = nullptr)
+      : AmgOp(c, n0) {   // breaks0 (interior_amg.hpp): rows the row blocks of A_0 do not cross
     std::string err;
     if (n0 < 1 || n0 >= INT32_MAX) raise(MI_ERR_BAD_ARG, "mi_amg_plan_create: n = %lld rows", (long long)n0);
     if (amgp::make_plan(n0, rowptr, colidx, nlevels, n_l, agg, base, c->rank, c->n_ranks, plan, err) != amgp::OK) raise(MI_ERR_BAD_ARG, "%s", err.c_str());
@@ -184,7 +184,7 @@ struct AmgPlanOp : AmgOp {
       L.n = H.n;
       nmax = std::max(nmax, (size_t)H.n);
       op_nnz += H.a_nnz();
-      L.A.upload(pattern(H.n, H.n, H.a_ptr, H.a_col), s);
+      L.A.upload(pattern(H.n, H.n, H.a_ptr, H.a_col), s, l == 0 ? breaks0 : nullptr);
       up(D.diag, H.diag); up(D.sym, H.sym);
       if (l) { D.cA.alloc((size_t)H.a_nnz() + 1); second += 8 * H.a_nnz(); }
       if (l == nlev - 1) break;

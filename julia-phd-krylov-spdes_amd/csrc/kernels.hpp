@@ -630,6 +630,137 @@ __global__ __launch_bounds__(NT) void k_icg_direction(IcgMeta m, const IcgPiece 
   }
 }
 
+// ---- `Pl` = a preconditioner applied by launches of its own between k_icg_update and the direction kernel (the AMG V-cycle
+// of the stacked A_II, interior_amg.hpp): z = Pl \ r lies in memory as a vector over all subdomains, and the launches that
+// make it also leave partial sums of r'z, a fixed run of them per subdomain. The recurrences are those of the diagonal `Pl`
+// above. `all_done` is 1 once every subdomain has stopped: the `done` word of the SpMV and of the preconditioner's launches,
+// so the rest of a graph replay returns at once. It is written by workgroup 0 of k_icg_update_z from the flags the direction
+// kernel of the iteration before left, i.e. never by the launch that reads it.
+struct IcgZ {
+  const double *z;        // z = Pl \ r, all subdomains
+  const double *p_rz;     // partials of r'z left by the preconditioner's launches
+  const int *q0, *q1;     // their range per subdomain, summed in icg_dom_sum's fixed order
+  int *all_done;
+  int ndl;
+};
+// r = rhs; x = 0; partials of r'r; all_done = 0 (the first z = Pl \ b always runs)
+__global__ __launch_bounds__(NT) void k_icg_init_z(IcgZ zz, const IcgPiece *__restrict__ pieces, const double *__restrict__ rhs,
+                                                   double *__restrict__ x, double *__restrict__ r, double *__restrict__ p_rr) {
+  __shared__ double sm[NT / 64 + 1];
+  if (blockIdx.x == 0 && threadIdx.x == 0) *zz.all_done = 0;
+  const IcgPiece pc = pieces[blockIdx.x];
+  if (pc.hi <= pc.lo) return;
+  double s = 0.0;
+  for (int i = pc.lo + threadIdx.x; i < pc.hi; i += NT) {
+    const double v = rhs[i];
+    r[i] = v; x[i] = 0.0;
+    s += v * v;
+  }
+  s = block_sum(s, sm);
+  if (threadIdx.x == 0) p_rr[pc.slot] = s;
+}
+// after z_0 = Pl \ b: workgroups [0, npieces): u = z_0 on the piece; workgroups npieces + d: the scalars of subdomain d
+// (residual = ||b||, rho = b'z_0, tol, flags), as k_icg_start
+__global__ __launch_bounds__(NT) void k_icg_start_z(IcgMeta m, IcgZ zz, int npieces, const IcgPiece *__restrict__ pieces,
+                                                    const double *p_rr, double reltol, double *__restrict__ u) {
+  __shared__ double sm[NT / 64 + 1];
+  if ((int)blockIdx.x < npieces) {
+    const IcgPiece pc = pieces[blockIdx.x];
+    for (int i = pc.lo + threadIdx.x; i < pc.hi; i += NT) u[i] = zz.z[i];
+    return;
+  }
+  const int d = (int)blockIdx.x - npieces;
+  const double rr = icg_dom_sum(p_rr, m.dom_p0[d], m.dom_p1[d], sm);
+  const double rz = icg_dom_sum(zz.p_rz, zz.q0[d], zz.q1[d], sm);
+  if (threadIdx.x == 0) {
+    const double res = sqrt(rr);
+    m.res_cur[d] = res; m.res_nxt[d] = res;
+    m.rho_cur[d] = rz; m.rho_nxt[d] = rz;
+    m.tol[d] = reltol * res;
+    m.iters[d] = 0;
+    const int dn = !(res > m.tol[d]);
+    m.done_cur[d] = dn; m.done_nxt[d] = dn;
+  }
+}
+// alpha = rho / (u'c); x += alpha u; r -= alpha c; partials of r'r (r'z comes from the preconditioner's launches)
+__global__ __launch_bounds__(NT) void k_icg_update_z(IcgMeta m, IcgZ zz, const IcgPiece *__restrict__ pieces, const double *__restrict__ p_uc,
+                                                     const double *__restrict__ u, const double *__restrict__ c, double *__restrict__ x,
+                                                     double *__restrict__ r, double *__restrict__ p_rr) {
+  __shared__ double sm[NT / 64 + 1];
+  if (blockIdx.x == 0) {
+    int a = 1;
+    for (int i = threadIdx.x; i < zz.ndl; i += NT) a &= m.done_nxt[i] != 0;
+    a = __syncthreads_and(a);
+    if (threadIdx.x == 0) *zz.all_done = a;
+  }
+  const IcgPiece pc = pieces[blockIdx.x];
+  if (pc.hi <= pc.lo) return;
+  const int d = pc.dom;
+  const bool lead = pc.lead && threadIdx.x == 0;
+  const int dn = m.done_nxt[d];
+  const double res = m.res_nxt[d], rho = m.rho_nxt[d];
+  double uv[4], cv[4], xv[4], rv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int rw = pc.lo + k * NT + (int)threadIdx.x;
+    const bool ok = rw < pc.hi;
+    uv[k] = ok ? u[rw] : 0.0; cv[k] = ok ? c[rw] : 0.0; xv[k] = ok ? x[rw] : 0.0; rv[k] = ok ? r[rw] : 0.0;
+  }
+  if (dn) { if (lead) m.done_cur[d] = 1; return; }
+  const double uc = icg_dom_sum(p_uc, pc.b0, pc.b1, sm);
+  const double alpha = rho / uc;
+  double s = 0.0;
+  for (int rw = pc.lo + (int)threadIdx.x, i = 0; rw < pc.hi; rw += NT, ++i) {
+    double u_, c_, x_, r_;
+    if (i < 4) { u_ = uv[i]; c_ = cv[i]; x_ = xv[i]; r_ = rv[i]; }
+    else { u_ = u[rw]; c_ = c[rw]; x_ = x[rw]; r_ = r[rw]; }
+    x[rw] = x_ + alpha * u_;
+    const double ri = r_ - alpha * c_;
+    r[rw] = ri;
+    s += ri * ri;
+  }
+  s = block_sum(s, sm);
+  if (threadIdx.x == 0) p_rr[pc.slot] = s;
+  if (lead) { m.res_cur[d] = res; m.rho_cur[d] = rho; m.done_cur[d] = 0; }
+}
+// residual = ||r||; rho = r'z from the partials; beta = rho / rho_prev; u = z + beta u; iteration count and stop test
+__global__ __launch_bounds__(NT) void k_icg_direction_z(IcgMeta m, IcgZ zz, const IcgPiece *__restrict__ pieces, const double *__restrict__ p_rr,
+                                                        double *__restrict__ u, const int *__restrict__ n_i) {
+  __shared__ double sm[NT / 64 + 1];
+  const IcgPiece pc = pieces[blockIdx.x];
+  if (pc.hi <= pc.lo) return;
+  const int d = pc.dom;
+  const int dc = m.done_cur[d];
+  const double rho_c = m.rho_cur[d];
+  const int q0 = zz.q0[d], q1 = zz.q1[d];
+  double zv[4], uv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int rw = pc.lo + k * NT + (int)threadIdx.x;
+    const bool ok = rw < pc.hi;
+    zv[k] = ok ? zz.z[rw] : 0.0; uv[k] = ok ? u[rw] : 0.0;
+  }
+  if (dc) return;
+  const double rr = icg_dom_sum(p_rr, pc.p0, pc.p1, sm);
+  const double res = sqrt(rr);
+  const double rho = icg_dom_sum(zz.p_rz, q0, q1, sm);
+  const double beta = rho / rho_c;
+  for (int rw = pc.lo + (int)threadIdx.x, i = 0; rw < pc.hi; rw += NT, ++i) {
+    double z_, u_;
+    if (i < 4) { z_ = zv[i]; u_ = uv[i]; }
+    else { z_ = zz.z[rw]; u_ = u[rw]; }
+    u[rw] = z_ + beta * u_;
+  }
+  if (pc.lead && threadIdx.x == 0) {
+    const int it = m.iters[d] + 1;
+    m.iters[d] = it;
+    m.res_nxt[d] = res;
+    m.rho_nxt[d] = rho;
+    const int maxiter = m.maxiter_cap > 0 ? m.maxiter_cap : n_i[d];
+    m.done_nxt[d] = !(res > m.tol[d]) || (it >= maxiter);
+  }
+}
+
 // ---- the same interior CG in 2 launches per iteration (round 2): the config-2 loop above with per-subdomain scalars.
 //   k_icg_spmv  : per subdomain: r'r (and r'z) from the partials -> residual, stop test, beta; the CSR-stream SpMV of the NEW
 //                 direction u = z + beta u_old computed on the fly from the gathered (u_old, z) pairs; the row owner stores

@@ -14,6 +14,7 @@
 #include "block_jacobi.hpp"
 #include "amg.hpp"
 #include "amg_setup.hpp"
+#include "interior_amg.hpp"
 #include "kl.hpp"
 #include "kl_field.hpp"
 
@@ -1410,6 +1411,30 @@ int mi_schur_interior_precond(mi_op_t op, int kind) {
     icg->set_jacobi(kind == 1);
     return MI_OK;
   });
+}
+int mi_schur_interior_amg(mi_op_t op, int64_t nlevels, const int64_t *n_l, const int64_t *const *agg, int index_base) {
+  MatfreeSchurOp *m = as_matfree(op);
+  GlobalSchurOp *gl = as_global(op);
+  InteriorCg *icg = m ? m->icg.get() : gl ? gl->icg.get() : nullptr;
+  if (!icg) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_amg: not a Schur operator with the interior solve on the device");
+  if (m && m->maps.sharded) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_amg: a sharded operator (the hierarchy is built on one device only)");
+  mi_ctx_s *c = op->impl->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    interior_amg_select(c, *icg, nlevels, n_l, agg, index_base);
+    return MI_OK;
+  });
+}
+int mi_schur_interior_amg_stats(mi_op_t op, int64_t *levels, int64_t *coarse_n, int64_t *bytes_kept) {
+  MatfreeSchurOp *m = as_matfree(op);
+  GlobalSchurOp *gl = as_global(op);
+  InteriorCg *icg = m ? m->icg.get() : gl ? gl->icg.get() : nullptr;
+  InteriorAmgStats st{};
+  if (!icg || !interior_amg_stats(*icg, &st)) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_amg_stats: no AMG `Pl` is selected on this operator");
+  if (levels) *levels = st.levels;
+  if (coarse_n) *coarse_n = st.coarse_n;
+  if (bytes_kept) *bytes_kept = st.bytes_kept;
+  return MI_OK;
 }
 int mi_schur_interior_iterations(mi_op_t op, int64_t *iterations) {
   MatfreeSchurOp *m = as_matfree(op);

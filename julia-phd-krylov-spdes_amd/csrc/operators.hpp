@@ -692,6 +692,20 @@ struct InteriorCg {
   std::vector<int> ioff_h;
   int npieces_grid = 0;
   bool jacobi = false;       // `Pl` = Diagonal(A_II) (mi_schur_matfree_interior_precond)
+  // `Pl` = the AMG hierarchy of the stacked A_II (mi_schur_interior_amg; interior_amg.hpp fills these). While pl_op is set:
+  // the 3-launch loop with the z-kernels of kernels.hpp (IcgZ) whatever MI355_ICG_FUSED says, and a chunk of its own.
+  std::unique_ptr<Operator> pl_op;                                     // owns the hierarchy
+  std::function<void(const double *, double *, double *, const int *)> pl_cycle;   // z = Pl \ r with the partials of r'z
+  std::function<void(const double *)> pl_refresh;                      // the hierarchy for new device values of A_II; raises, keeps the old one
+  DevBuf<double> zv, p_rzq;
+  DevBuf<int> dom_q0, dom_q1, all_done;
+  IcgZ zm{};
+  int chunk_plain = 64, chunk_pl = ICG_CHUNK_PL;
+  // iterations per replay with the AMG `Pl`: a solve takes 10 to 30 iterations; a replay costs one host wait (~16 us), an
+  // iteration launched after all subdomains have stopped ~40 us of empty launches. Tried 2 / 4 / 8 / 16 / 32 at config 3:
+  // 6.61 / 6.50 / 6.63 / 6.57 / 6.58 ms per S-apply, 2 % apart at most and inside the noise of a second run (DESIGN §6g
+  // "Interior `Pl`"): 4 by that cost model
+  static constexpr int ICG_CHUNK_PL = 4;
 
   void build(mi_ctx_s *c_, const HostCsr &a, const std::vector<int> &ioff, const std::vector<int> &ni, double reltol_) {
     ctx = c_; reltol = reltol_; ndl = (int)ni.size(); n = a.n_rows;
@@ -713,7 +727,9 @@ struct InteriorCg {
     res_cur.alloc(ndl + 1); res_nxt.alloc(ndl + 1); tol.alloc(ndl + 1);
     done_cur.alloc(ndl + 1); done_nxt.alloc(ndl + 1); iters.alloc(ndl + 1);
     MI_HIP(hipHostMalloc((void **)&done_host, sizeof(int) * (ndl + 1)));
-    chunk = std::max(1, env_int("MI355_ICG_CHUNK", 64));
+    chunk_plain = std::max(1, env_int("MI355_ICG_CHUNK", 64));
+    chunk_pl = std::max(1, env_int("MI355_ICG_CHUNK", ICG_CHUNK_PL));
+    chunk = chunk_plain;
     rho.alloc(2 * (size_t)ndl + 2); part_rz.alloc((size_t)A.nblocks + 1);
     meta = IcgMeta{A.blk.p, blk_dom.p, dom_b0.p, dom_b1.p, res_cur.p, res_nxt.p, tol.p, done_cur.p, done_nxt.p, iters.p, 0,
                    nullptr, rho.p, rho.p + ndl + 1, part_rz.p, nullptr, nullptr};
@@ -794,8 +810,36 @@ struct InteriorCg {
     if (done_host) (void)hipHostFree(done_host);
     if (dst_host) (void)hipHostFree(dst_host);
   }
+  void drop_graph() {
+    if (graph) { (void)hipGraphExecDestroy(graph); graph = nullptr; }
+  }
+  // deselects the AMG `Pl` and releases its hierarchy (the stream is idle: every solve ends with a host synchronisation)
+  void drop_pl() {
+    if (!pl_op) return;
+    drop_graph();
+    pl_cycle = nullptr; pl_refresh = nullptr;
+    pl_op.reset();
+    zv.release(); p_rzq.release(); dom_q0.release(); dom_q1.release(); all_done.release();
+    zm = IcgZ{};
+    chunk = chunk_plain;
+  }
+  // selects it: the partials of r'z of subdomain d are p_rzq[q0[d] .. q1[d])
+  void select_pl(std::unique_ptr<Operator> op, std::function<void(const double *, double *, double *, const int *)> cyc,
+                 std::function<void(const double *)> refresh, const std::vector<int> &q0, const std::vector<int> &q1, size_t nparts) {
+    drop_pl();
+    drop_graph();
+    set_jacobi(false);
+    hipStream_t s = ctx->stream;
+    zv.alloc((size_t)n + 1); p_rzq.alloc(nparts + 1); all_done.alloc(1);
+    zv.zero(s); p_rzq.zero(s); all_done.zero(s);
+    dom_q0.upload(q0, s); dom_q1.upload(q1, s);
+    zm = IcgZ{zv.p, p_rzq.p, dom_q0.p, dom_q1.p, all_done.p, ndl};
+    pl_op = std::move(op); pl_cycle = std::move(cyc); pl_refresh = std::move(refresh);
+    chunk = chunk_pl;
+  }
   void set_jacobi(bool on) {
-    if (on != jacobi && graph) { (void)hipGraphExecDestroy(graph); graph = nullptr; }   // kernel arguments are captured
+    drop_pl();
+    if (on != jacobi) drop_graph();   // kernel arguments are captured
     jacobi = on;
     fm.dinv = on ? dinv.p : nullptr;
     meta.dinv = on ? dinv.p : nullptr;
@@ -808,6 +852,15 @@ struct InteriorCg {
   }
   void iteration(double *x) {
     hipStream_t s = ctx->stream;
+    if (pl_op) {
+      A.launch(0, u.p, nullptr, c.p, all_done.p, s, u.p, p_uc.p);  // c = A u, partial u'c
+      hipLaunchKernelGGL(k_icg_update_z, dim3(npieces_grid), dim3(NT), 0, s, meta, zm, pieces.p, p_uc.p, u.p, c.p, x, r.p, p_rr.p);
+      MI_HIP(hipGetLastError());
+      pl_cycle(r.p, zv.p, p_rzq.p, all_done.p);
+      hipLaunchKernelGGL(k_icg_direction_z, dim3(npieces_grid), dim3(NT), 0, s, meta, zm, pieces.p, p_rr.p, u.p, n_i.p);
+      MI_HIP(hipGetLastError());
+      return;
+    }
     if (folded) {
       const int grid = ((A.nblocks + 7) / 8) * 8;
       hipLaunchKernelGGL(k_icg_spmv, dim3(grid), dim3(NT), 0, s, A.nblocks, fm, A.rowptr.p, A.col.p, A.val.p);
@@ -824,7 +877,13 @@ struct InteriorCg {
   void solve(const double *rhs, double *x) {
     if (A.nblocks == 0) return;
     hipStream_t s = ctx->stream;
-    if (folded) {
+    const bool folded = this->folded && !pl_op;   // the AMG `Pl` has the 3-launch form only
+    if (pl_op) {
+      hipLaunchKernelGGL(k_icg_init_z, dim3(npieces_grid), dim3(NT), 0, s, zm, pieces.p, rhs, x, r.p, p_rr.p);
+      MI_HIP(hipGetLastError());
+      pl_cycle(r.p, zv.p, p_rzq.p, nullptr);
+      hipLaunchKernelGGL(k_icg_start_z, dim3(npieces_grid + ndl), dim3(NT), 0, s, meta, zm, npieces_grid, pieces.p, p_rr.p, reltol, u.p);
+    } else if (folded) {
       hipLaunchKernelGGL(k_icg_fold_init, dim3(npieces_grid), dim3(NT), 0, s, fm, pieces.p, rhs, x);
     } else {
       hipLaunchKernelGGL(k_icg_init, dim3(npieces_grid), dim3(NT), 0, s, meta, pieces.p, rhs, x, r.p, u.p, p_rr.p);
@@ -973,6 +1032,9 @@ struct MatfreeSchurOp : Operator {
     hipStream_t s = ctx->stream;
     if (ii_val) {
       if (!icg) raise(MI_ERR_BAD_ARG, "set_values: A_II lives in the interior-solve callback of this operator");
+      // AMG `Pl`: its hierarchy first, from the caller's values. A refusal (MI_ERR_SINGULAR) leaves this call before anything of
+      // the operator has changed: matrices, diagonal and hierarchy are those of the call before.
+      if (icg->pl_refresh) icg->pl_refresh(ii_val);
       if (icg->A.nnz) MI_HIP(hipMemcpyAsync(icg->A.val.p, ii_val, sizeof(double) * icg->A.nnz, hipMemcpyDeviceToDevice, s));
       icg->refresh_diagonal();
     }

@@ -1111,6 +1111,22 @@ def amg_refresh(H_or_aggs, A) -> AmgHierarchy:
     return AmgHierarchy(As, Ps, om, owd, inv, [a.shape[0] for a in As], float(sum(nnz)) / float(nnz[0]), aggs)
 
 
+def prepare_interior_amg(A_IIdd, max_levels: int = 10, max_coarse: int = 256):
+    """The aggregates of the AMG `Pl` of the device interior CG (`api.MatrixFreeLocalSchurs.interior_amg`,
+    `mi_schur_interior_amg`): `prepare_amg_precond` on the stacked block-diagonal matrix blockdiag(A_IIdd), for its
+    aggregation alone — the numbers of the hierarchy are made on the device from the operator's own values. Returns
+    (sizes, aggs): the level sizes (sizes[0] = Σ_d n_Id) and one 0-based aggregate array per smoothed level, over the stacked
+    nodes. `amg_aggregate` looks at neighbours only, so every block gets exactly the aggregates it would get alone
+    (renumbered); the stop rule `n_l <= max_coarse` counts stacked rows. Raises the ValueErrors of `prepare_amg_precond`
+    (no interior node at all, max_levels < 1, a diagonal entry that is not positive, a stalled aggregation, a coarsest level
+    above 4096 rows)."""
+    blocks = [sp.csr_matrix(A) for A in A_IIdd]
+    if not blocks or sum(A.shape[0] for A in blocks) == 0:
+        raise ValueError("square, non-empty matrix expected")
+    H = prepare_amg_precond(sp.block_diag(blocks, format="csr"), max_levels=max_levels, max_coarse=max_coarse)
+    return list(H.sizes), [np.asarray(a, dtype=np.int64) for a in H.agg]
+
+
 def get_schur_rhs(b_Id, A_IId, A_IΓd, b_Γ, gather_idx=None, solvers=None):
     """`get_schur_rhs` (EPDD.jl:798-821 global columns; :835-864 local columns + scatter)."""
     b = np.array(b_Γ, dtype=np.float64, copy=True)

@@ -415,6 +415,24 @@ set_values!(S::MiOperator, ii, ig, gg) =
 for the device interior CG — `:none` (default, plain CG) or `:diagonal` (`Pl = Diagonal(A_IIdd)`)."""
 interior_precond!(S::MiOperator, kind::Symbol) =
   check(ccall((:mi_schur_interior_precond, lib), Cint, (Ptr{Cvoid}, Cint), S.h, kind === :diagonal ? 1 : 0))
+"""`interior_amg!(S, n_l, agg)`: `Pl` = smoothed-aggregation AMG for the device interior CG (`mi_schur_interior_amg`), the
+reference's `cg(A_IId, rhs; Pl = Π_IId, reltol)`. One hierarchy of blockdiag(A_IIdd): `n_l` the level sizes, `agg[l]` the
+1-based aggregate of every stacked node of level `l`; the numbers are made on the device from the operator's values and
+redone by `set_values!(S, ii, ...)`. `interior_precond!(S, :none | :diagonal)` switches back."""
+function interior_amg!(S::MiOperator, n_l::Vector{Int64}, agg::Vector{Vector{Int64}})
+  length(agg) == length(n_l) - 1 || error("interior_amg!: one aggregate array per smoothed level")
+  GC.@preserve agg begin
+    ptrs = Ptr{Int64}[pointer(a) for a in agg]
+    check(ccall((:mi_schur_interior_amg, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Ptr{Int64}}, Cint),
+                S.h, length(n_l), n_l, isempty(ptrs) ? C_NULL : ptrs, 1))
+  end
+  S
+end
+function interior_amg_stats(S::MiOperator)
+  l, c, b = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+  check(ccall((:mi_schur_interior_amg_stats, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), S.h, l, c, b))
+  (levels = l[], coarse_n = c[], bytes_kept = b[])
+end
 function interior_iterations(S::MiOperator)
   it = Ref{Int64}(0)
   check(ccall((:mi_schur_interior_iterations, lib), Cint, (Ptr{Cvoid}, Ref{Int64}), S.h, it)); it[]
