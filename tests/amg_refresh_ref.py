@@ -97,3 +97,37 @@ def level_bounds(Al, P, agg):
     M = sp.csr_matrix(P.T @ Al @ P)
     Gb = sp.csr_matrix((kR + kA + 4) * U * (abs(P).T @ abs(Al) @ abs(P)))
     return dict(kA=kA, kR=kR, g=g, omega=w, wd=wd, rel=(kA + 2) * U, P=Ph, P_bound=Pb, G=sp.csr_matrix((M + M.T) * 0.5), G_bound=Gb)
+
+
+def check_levels(H, aggs, tag):
+    """every smoothed level of a hierarchy read back from the device within `level_bounds`; prints the fractions used"""
+    for l in range(H.nlevels - 1):
+        Al, P, An = H.A[l], H.P[l], H.A[l + 1]
+        B = level_bounds(Al, P, aggs[l])
+        g_dev = 4.0 / (3.0 * H.omega[l])
+        e_w, e_g = abs(H.omega[l] - B["omega"]) / B["omega"], abs(g_dev - B["g"]) / B["g"]
+        e_wd = np.max(np.abs(H.omega_over_d[l] - B["wd"]) / np.abs(B["wd"]))
+        dP = np.abs(P.data - on_pattern(B["P"], P))
+        bP = on_pattern(B["P_bound"], P)
+        dA = np.abs(An.data - on_pattern(B["G"], An))
+        bA = on_pattern(B["G_bound"], An)
+        use = lambda d, b: np.max(np.divide(d, b, out=np.zeros_like(d), where=b > 0), initial=0.0)
+        print(f"{tag} level {l}: n = {Al.shape[0]}, kA = {B['kA']}, kR = {B['kR']}; ω rel. {e_w:.2e}, g rel. {e_g:.2e}, ω/d rel. {e_wd:.2e} "
+              f"(bar {B['rel']:.2e}); P: {use(dP, bP):.3f} of its bound; A_{l + 1}: {use(dA, bA):.3f} of its bound")
+        assert e_w <= B["rel"] and e_g <= B["rel"] and e_wd <= B["rel"], (tag, l)
+        assert (dP <= bP).all(), (tag, l, "P")
+        assert (dA <= bA).all(), (tag, l, "A_next")
+        assert abs(An - An.T).max() == 0.0, (tag, l, "A_next is not exactly symmetric")
+
+
+def check_coarse(H, tag):
+    """the coarse inverse read back against numpy's of the device's own A_L: ||I - Z A||_F <= 8 ||I - Z_np A||_F + n_c u"""
+    Ac = H.A[-1].toarray()
+    nc = Ac.shape[0]
+    Zn = np.linalg.inv((Ac + Ac.T) * 0.5)
+    Zn = (Zn + Zn.T) * 0.5
+    r_dev, r_np = np.linalg.norm(np.eye(nc) - H.coarse_inv @ Ac), np.linalg.norm(np.eye(nc) - Zn @ Ac)
+    print(f"{tag} coarse inverse: n_c = {nc}, cond = {np.linalg.cond(Ac):.1f}, ||I - Z A||_F device {r_dev:.3e}, numpy {r_np:.3e}, "
+          f"ratio {r_dev / r_np:.2f}")
+    assert np.array_equal(H.coarse_inv, H.coarse_inv.T)
+    assert r_dev <= 8 * r_np + nc * U, (tag, r_dev, r_np)

@@ -21,6 +21,7 @@ import scipy.sparse as sp
 
 import amg_ref as ar
 import amg_refresh_ref as rr
+from amg_refresh_ref import check_coarse as _check_coarse, check_levels as _check_levels
 from test_gpu_amg import APPLY_BAR, _assert_solve, _rel, _rhs
 
 pytestmark = pytest.mark.gpu
@@ -47,38 +48,6 @@ def _same_hierarchy(Ha, Hb):
     return (Ha.sizes == Hb.sizes and all(same(a, b) for a, b in zip(Ha.A, Hb.A)) and all(same(a, b) for a, b in zip(Ha.P, Hb.P))
             and Ha.omega == Hb.omega and all(np.array_equal(a, b) for a, b in zip(Ha.omega_over_d, Hb.omega_over_d))
             and np.array_equal(Ha.coarse_inv, Hb.coarse_inv))
-
-
-def _check_levels(H, aggs, tag):
-    for l in range(H.nlevels - 1):
-        Al, P, An = H.A[l], H.P[l], H.A[l + 1]
-        B = rr.level_bounds(Al, P, aggs[l])
-        g_dev = 4.0 / (3.0 * H.omega[l])
-        e_w, e_g = abs(H.omega[l] - B["omega"]) / B["omega"], abs(g_dev - B["g"]) / B["g"]
-        e_wd = np.max(np.abs(H.omega_over_d[l] - B["wd"]) / np.abs(B["wd"]))
-        dP = np.abs(P.data - rr.on_pattern(B["P"], P))
-        bP = rr.on_pattern(B["P_bound"], P)
-        dA = np.abs(An.data - rr.on_pattern(B["G"], An))
-        bA = rr.on_pattern(B["G_bound"], An)
-        use = lambda d, b: np.max(np.divide(d, b, out=np.zeros_like(d), where=b > 0), initial=0.0)
-        print(f"{tag} level {l}: n = {Al.shape[0]}, kA = {B['kA']}, kR = {B['kR']}; ω rel. {e_w:.2e}, g rel. {e_g:.2e}, ω/d rel. {e_wd:.2e} "
-              f"(bar {B['rel']:.2e}); P: {use(dP, bP):.3f} of its bound; A_{l + 1}: {use(dA, bA):.3f} of its bound")
-        assert e_w <= B["rel"] and e_g <= B["rel"] and e_wd <= B["rel"], (tag, l)
-        assert (dP <= bP).all(), (tag, l, "P")
-        assert (dA <= bA).all(), (tag, l, "A_next")
-        assert abs(An - An.T).max() == 0.0, (tag, l, "A_next is not exactly symmetric")
-
-
-def _check_coarse(H, tag):
-    Ac = H.A[-1].toarray()
-    nc = Ac.shape[0]
-    Zn = np.linalg.inv((Ac + Ac.T) * 0.5)
-    Zn = (Zn + Zn.T) * 0.5
-    r_dev, r_np = np.linalg.norm(np.eye(nc) - H.coarse_inv @ Ac), np.linalg.norm(np.eye(nc) - Zn @ Ac)
-    print(f"{tag} coarse inverse: n_c = {nc}, cond = {np.linalg.cond(Ac):.1f}, ||I - Z A||_F device {r_dev:.3e}, numpy {r_np:.3e}, "
-          f"ratio {r_dev / r_np:.2f}")
-    assert np.array_equal(H.coarse_inv, H.coarse_inv.T)
-    assert r_dev <= 8 * r_np + nc * U, (tag, r_dev, r_np)
 
 
 def _check_apply(M, H, tag):

@@ -12,31 +12,9 @@ import pytest
 import scipy.sparse as sp
 
 import interior_amg_ref as ir
+from interior_amg_ref import close as _close, new_values as _new_values, op as _op, residuals as _residuals
 
 pytestmark = pytest.mark.gpu
-
-
-def _op(api, ctx, C, second=False, **kw):
-    A_II, A_IΓ, A_ΓΓ = C.blocks(second)
-    return api.MatrixFreeLocalSchurs(ctx, A_II, A_IΓ, A_ΓΓ, C.gather_idx, C.node_Γ_cnt, None, reltol=ir.RELTOL, **kw)
-
-
-def _new_values(C):
-    """set_values arguments for the case's second values (None where the case keeps the first ones)"""
-    ig = None if C.A_IΓ2 is C.A_IΓ else ir.csc_values(C.A_IΓ2)
-    gg = None if C.A_ΓΓ2 is C.A_ΓΓ else ir.csc_values(C.A_ΓΓ2)
-    return ir.csc_values(C.A_II2), ig, gg
-
-
-def _residuals(C, u, b, second=False, blocks=None):
-    A, offs = C.stacked(second) if blocks is None else ir.stack(blocks)
-    r = b - A @ u
-    return [(np.linalg.norm(r[offs[d]:offs[d + 1]]), np.linalg.norm(b[offs[d]:offs[d + 1]])) for d in range(offs.size - 1)]
-
-
-def _close(y, exact):
-    err = np.abs(y - exact).max() / np.abs(exact).max()
-    return err
 
 
 @pytest.mark.parametrize("name", ir.NAMES)

@@ -61,9 +61,10 @@ def test_restated_s_apply_on_ragged_and_fewer_iterations_than_diagonal(fem):
 
 
 @pytest.mark.parametrize("second", [False, True], ids=["first", "after_set_values"])
-@pytest.mark.parametrize("name", ir.NAMES)
+@pytest.mark.parametrize("name", ir.NAMES + ir.EDGE_NAMES)
 def test_counts_are_not_marginal(fem, name, second):
-    """Every case the GPU suite uses for an iteration-count equality: in the restatement each subdomain stops with
+    """Every case the GPU suites use for an iteration-count equality (tests/test_gpu_interior_amg.py; the edge cases of
+    tests/test_gpu_amg_edges.py): in the restatement each subdomain stops with
     ‖r‖ <= 0.95 tol, after a step that left ‖r‖ >= 1.05 tol. The true residual meets the cap 2 reltol ‖b‖_d."""
     C = ir.case(fem, name)
     x = C.x(second)
@@ -89,6 +90,14 @@ def test_counts_are_not_marginal(fem, name, second):
         for d in range(offs.size - 1):
             s = slice(offs[d], offs[d + 1])
             assert np.linalg.norm(rb[s]) <= 2.0 * ir.RELTOL * np.linalg.norm(bI[s]), (name, d)
+        if name in ir.EDGE_NAMES:   # ... and on the edge cases its iteration count is compared too: the same margins
+            _, its_b, hist_b, tol_b = C.solve_b(fem)
+            mb = ir.margins(hist_b, tol_b)
+            print(f"{name} interior_solutions(0, b_I): iterations {its_b.tolist()}, (stop, before) / tol "
+                  f"{[(float(f'{a:.3g}'), float(f'{b:.3g}')) for a, b in mb]}")
+            assert len(mb) == sum(A.shape[0] > 0 for A in C.A_II)
+            for a, b in mb:
+                assert a <= 0.95 and b >= 1.05, (name, a, b)
 
 
 def test_level_counts_of_the_cases(fem):
