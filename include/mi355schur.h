@@ -491,7 +491,11 @@ int mi_schur_setup_run(mi_setup_t plan, const double *ii_val, const double *ig_v
  * `IterativeSolvers.cg(A_IIdd, rhs; reltol)` (EPDD.jl:609-619, 648-650, 813-815, 1021) and of its thousands of A_II SpMVs.
  * mi_schur_matfree_interior_levels(op, plan): a matrix-free or global Schur operator built on the same subdomains uses
  * these solves for every interior solve (apply, get_schur_rhs, get_subdomain_solutions); plan = NULL restores its own
- * (callback / interior CG). The plan must outlive the operator's use of it; values are those of the plan's last run. */
+ * (callback / interior CG). Values are those of the plan's last run. The plan counts the operators bound to it: up here,
+ * down when the operator is given plan = NULL or another plan, or is destroyed. While the count is above 0
+ * mi_schur_setup_destroy returns MI_ERR_BAD_ARG ("... live matrix-free Schur operator(s) solve with this plan; destroy them
+ * first"). mi_schur_setup_keep_levels(plan, 0) is not refused for these users: their next interior solve raises
+ * MI_ERR_BAD_ARG ("level solves need ...") until the levels are kept and run again. */
 int mi_schur_setup_keep_levels(mi_setup_t plan, int on);
 int mi_schur_setup_interior_solve(mi_setup_t plan, const double *f, double *u);
 int mi_schur_matfree_interior_levels(mi_op_t op, mi_setup_t plan);

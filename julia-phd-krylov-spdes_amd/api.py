@@ -901,7 +901,98 @@ def _csc_parts(mats, lo, hi, base: int = 0):
     return ptr, idx, val
 
 
-class MatrixFreeLocalSchurs(Operator):
+class _InteriorSolve:
+    """What `MatrixFreeLocalSchurs` and `GlobalSchur` share: the calls built on the operator's interior solve (host callback,
+    device interior CG or the level inverses of a `SchurSetup`) and the choice of that solve."""
+
+    def schur_rhs(self, b_I, b_Γ):
+        """`get_schur_rhs(b_Id, A_IIdd, A_IΓdd, b_Γ, ind_Γd_Γ2l; preconds)` (EPDD.jl:835-864) with this operator's
+        interior solve; `b_I` is the concatenation of the b_Id of this operator's subdomains."""
+        self.ctx._mode_for(b_I, b_Γ)
+        k1, p1 = self.ctx._ptr(b_I)
+        k2, p2 = self.ctx._ptr(b_Γ, self.n)
+        if _is_torch(b_Γ):
+            import torch
+            out = torch.empty_like(b_Γ)
+            po = vp(out.data_ptr())
+        else:
+            out = np.empty(self.n)
+            po = vp(out.ctypes.data)
+        self.ctx._order((k1, k2, out), after=False)
+        check(self.ctx._L.mi_schur_matfree_rhs(self._h, p1, p2, po))
+        self.ctx._order((k1, k2, out), after=True)
+        return out
+
+    def interior_solutions(self, u_Γ, b_I):
+        """`get_subdomain_solutions(u_Γ, A_IId, A_IΓd, b_Id)` (EPDD.jl:1014-1025) with this operator's interior solve:
+        the concatenation of u_Id = A_IIdd \\ (b_Id - A_IΓdd u_Γd) over this operator's subdomains."""
+        self.ctx._mode_for(u_Γ, b_I)
+        k1, p1 = self.ctx._ptr(u_Γ, self.n)
+        k2, p2 = self.ctx._ptr(b_I)
+        if _is_torch(b_I):
+            import torch
+            out = torch.empty_like(b_I)
+            po = vp(out.data_ptr())
+        else:
+            out = np.empty(np.asarray(b_I).size)
+            po = vp(out.ctypes.data)
+        self.ctx._order((k1, k2, out), after=False)
+        check(self.ctx._L.mi_schur_matfree_interior_solutions(self._h, p1, p2, po))
+        self.ctx._order((k1, k2, out), after=True)
+        return out
+
+    def interior_precond(self, kind) -> None:
+        """The `precond(s)` keyword of `apply_local_schur(s)` / `apply_global_schur` (EPDD.jl:648-650, 609-619) for the device
+        interior CG: None / "none": plain CG (the default); "diagonal": `Pl = Diagonal(A_IIdd)`."""
+        k = {None: 0, "none": 0, 0: 0, "diagonal": 1, "jacobi": 1, 1: 1}.get(kind)
+        if k is None:
+            raise ValueError("interior preconditioner: None or 'diagonal'")
+        check(self.ctx._L.mi_schur_interior_precond(self._h, C.c_int(k)))
+
+    def interior_iterations(self) -> int:
+        """Diagnostic: iterations the device interior CG has run so far (slowest subdomain, rounded up to whole replays)."""
+        out = i64(0)
+        check(self.ctx._L.mi_schur_interior_iterations(self._h, C.byref(out)))
+        return int(out.value)
+
+    def interior_amg(self, A_IIdd=None, max_levels: int = 10, max_coarse: int = 256, sizes=None, aggregates=None, index_base: int = 0):
+        """`Pl` = smoothed-aggregation AMG for the device interior CG (`mi_schur_interior_amg`): the reference's own `Pl`, the
+        Π_IId of `IterativeSolvers.cg(A_IId, rhs; Pl = Π_IId, reltol)` (Example07:174). `A_IIdd`: the blocks the operator was
+        made from — `fem.prepare_interior_amg(A_IIdd, max_levels, max_coarse)` aggregates their stacked pattern on the host,
+        the numbers of the ONE hierarchy of blockdiag(A_IIdd) are made on the device from the operator's current values, and
+        `set_values(ii_val=...)` redoes them for every realization. `sizes=, aggregates=` (0-based) instead of `A_IIdd` freeze
+        aggregates from elsewhere; `index_base=1` sends them 1-based, as the Julia shim does. `interior_precond(None |
+        "diagonal")` switches back and releases the hierarchy. Returns `interior_amg_stats()`."""
+        if aggregates is None:
+            if A_IIdd is None:
+                raise TypeError("interior_amg: the blocks A_IIdd, or sizes= and aggregates=")
+            from . import fem
+            lo, hi = getattr(self, "_dom", (0, len(A_IIdd)))
+            sizes, aggregates = fem.prepare_interior_amg(list(A_IIdd)[lo:hi], max_levels=max_levels, max_coarse=max_coarse)
+        elif sizes is None:
+            raise TypeError("interior_amg: aggregates= needs sizes= (the level sizes)")
+        aggs = [_i64(a).ravel() + index_base for a in aggregates]
+        n_l = _i64(sizes)
+        if len(aggs) != len(n_l) - 1 or any(a.size != n for a, n in zip(aggs, n_l)):
+            raise ValueError("interior_amg: one aggregate array per smoothed level, one id per node of the level")
+        check(self.ctx._L.mi_schur_interior_amg(self._h, i64(len(n_l)), n_l.ctypes.data_as(i64p), _ptrs(aggs, i64p) if aggs else None,
+                                                C.c_int(index_base)))
+        return self.interior_amg_stats()
+
+    def interior_amg_stats(self) -> dict:
+        """dict(levels, coarse_n, bytes_kept) of the AMG `Pl` selected (`mi_schur_interior_amg_stats`)."""
+        a, b, c = i64(), i64(), i64()
+        check(self.ctx._L.mi_schur_interior_amg_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(levels=int(a.value), coarse_n=int(b.value), bytes_kept=int(c.value))
+
+    def use_level_solver(self, setup: "SchurSetup" = None):
+        """Interior solves of this matrix-free / global Schur operator through the level inverses `setup` keeps (exact, device;
+        `mi_schur_matfree_interior_levels`); None: back to the operator's own callback / interior CG."""
+        check(self.ctx._L.mi_schur_matfree_interior_levels(self._h, setup._h if setup is not None else None))
+        self._level_setup = setup      # keep the plan alive
+
+
+class MatrixFreeLocalSchurs(_InteriorSolve, Operator):
     """`x -> apply_local_schurs(A_IIdd, A_IΓdd, A_ΓΓdd, ind_Γd_Γ2l, node_Γ_cnt, x; preconds, reltol)` (EPDD.jl:711-747),
     the closure of Example03:143-150. Sparse products on the device; `A_IIdd^{-1}` either through
     `interior_solvers[d](rhs)` on the host, or — `interior_solvers=None` — by the device CG that restates the
@@ -946,100 +1037,6 @@ class MatrixFreeLocalSchurs(Operator):
         k2, p2 = self.ctx._ptr(ig_val)
         k3, p3 = self.ctx._ptr(gg_val)
         check(self.ctx._L.mi_schur_matfree_set_values(self._h, p1, p2, p3))
-
-    def schur_rhs(self, b_I, b_Γ):
-        """`get_schur_rhs(b_Id, A_IIdd, A_IΓdd, b_Γ, ind_Γd_Γ2l; preconds)` (EPDD.jl:835-864) with this operator's
-        interior solve; `b_I` is the concatenation of the b_Id of this operator's subdomains."""
-        self.ctx._mode_for(b_I, b_Γ)
-        k1, p1 = self.ctx._ptr(b_I)
-        k2, p2 = self.ctx._ptr(b_Γ, self.n)
-        if _is_torch(b_Γ):
-            import torch
-            out = torch.empty_like(b_Γ)
-            po = vp(out.data_ptr())
-        else:
-            out = np.empty(self.n)
-            po = vp(out.ctypes.data)
-        self.ctx._order((k1, k2, out), after=False)
-        check(self.ctx._L.mi_schur_matfree_rhs(self._h, p1, p2, po))
-        self.ctx._order((k1, k2, out), after=True)
-        return out
-
-
-def _interior_solutions(self, u_Γ, b_I):
-    """`get_subdomain_solutions(u_Γ, A_IId, A_IΓd, b_Id)` (EPDD.jl:1014-1025) with this operator's interior solve:
-    the concatenation of u_Id = A_IIdd \\ (b_Id - A_IΓdd u_Γd) over this operator's subdomains."""
-    self.ctx._mode_for(u_Γ, b_I)
-    k1, p1 = self.ctx._ptr(u_Γ, self.n)
-    k2, p2 = self.ctx._ptr(b_I)
-    if _is_torch(b_I):
-        import torch
-        out = torch.empty_like(b_I)
-        po = vp(out.data_ptr())
-    else:
-        out = np.empty(np.asarray(b_I).size)
-        po = vp(out.ctypes.data)
-    self.ctx._order((k1, k2, out), after=False)
-    check(self.ctx._L.mi_schur_matfree_interior_solutions(self._h, p1, p2, po))
-    self.ctx._order((k1, k2, out), after=True)
-    return out
-
-
-MatrixFreeLocalSchurs.interior_solutions = _interior_solutions
-
-
-def _interior_precond(self, kind) -> None:
-    """The `precond(s)` keyword of `apply_local_schur(s)` / `apply_global_schur` (EPDD.jl:648-650, 609-619) for the device
-    interior CG: None / "none": plain CG (the default); "diagonal": `Pl = Diagonal(A_IIdd)`."""
-    k = {None: 0, "none": 0, 0: 0, "diagonal": 1, "jacobi": 1, 1: 1}.get(kind)
-    if k is None:
-        raise ValueError("interior preconditioner: None or 'diagonal'")
-    check(self.ctx._L.mi_schur_interior_precond(self._h, C.c_int(k)))
-
-
-def _interior_iterations(self) -> int:
-    """Diagnostic: iterations the device interior CG has run so far (slowest subdomain, rounded up to whole replays)."""
-    out = i64(0)
-    check(self.ctx._L.mi_schur_interior_iterations(self._h, C.byref(out)))
-    return int(out.value)
-
-
-def _interior_amg(self, A_IIdd=None, max_levels: int = 10, max_coarse: int = 256, sizes=None, aggregates=None, index_base: int = 0):
-    """`Pl` = smoothed-aggregation AMG for the device interior CG (`mi_schur_interior_amg`): the reference's own `Pl`, the
-    Π_IId of `IterativeSolvers.cg(A_IId, rhs; Pl = Π_IId, reltol)` (Example07:174). `A_IIdd`: the blocks the operator was
-    made from — `fem.prepare_interior_amg(A_IIdd, max_levels, max_coarse)` aggregates their stacked pattern on the host,
-    the numbers of the ONE hierarchy of blockdiag(A_IIdd) are made on the device from the operator's current values, and
-    `set_values(ii_val=...)` redoes them for every realization. `sizes=, aggregates=` (0-based) instead of `A_IIdd` freeze
-    aggregates from elsewhere; `index_base=1` sends them 1-based, as the Julia shim does. `interior_precond(None |
-    "diagonal")` switches back and releases the hierarchy. Returns `interior_amg_stats()`."""
-    if aggregates is None:
-        if A_IIdd is None:
-            raise TypeError("interior_amg: the blocks A_IIdd, or sizes= and aggregates=")
-        from . import fem
-        lo, hi = getattr(self, "_dom", (0, len(A_IIdd)))
-        sizes, aggregates = fem.prepare_interior_amg(list(A_IIdd)[lo:hi], max_levels=max_levels, max_coarse=max_coarse)
-    elif sizes is None:
-        raise TypeError("interior_amg: aggregates= needs sizes= (the level sizes)")
-    aggs = [_i64(a).ravel() + index_base for a in aggregates]
-    n_l = _i64(sizes)
-    if len(aggs) != len(n_l) - 1 or any(a.size != n for a, n in zip(aggs, n_l)):
-        raise ValueError("interior_amg: one aggregate array per smoothed level, one id per node of the level")
-    check(self.ctx._L.mi_schur_interior_amg(self._h, i64(len(n_l)), n_l.ctypes.data_as(i64p), _ptrs(aggs, i64p) if aggs else None,
-                                            C.c_int(index_base)))
-    return self.interior_amg_stats()
-
-
-def _interior_amg_stats(self) -> dict:
-    """dict(levels, coarse_n, bytes_kept) of the AMG `Pl` selected (`mi_schur_interior_amg_stats`)."""
-    a, b, c = i64(), i64(), i64()
-    check(self.ctx._L.mi_schur_interior_amg_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
-    return dict(levels=int(a.value), coarse_n=int(b.value), bytes_kept=int(c.value))
-
-
-MatrixFreeLocalSchurs.interior_precond = _interior_precond
-MatrixFreeLocalSchurs.interior_iterations = _interior_iterations
-MatrixFreeLocalSchurs.interior_amg = _interior_amg
-MatrixFreeLocalSchurs.interior_amg_stats = _interior_amg_stats
 
 
 class LocalSchur(MatrixFreeLocalSchurs):
@@ -1242,19 +1239,11 @@ def _set_blocks(self, blocks):
     self.ctx._record(blocks)
 
 
-def _use_level_solver(self, setup: "SchurSetup" = None):
-    """Interior solves of this matrix-free / global Schur operator through the level inverses `setup` keeps (exact, device;
-    `mi_schur_matfree_interior_levels`); None: back to the operator's own callback / interior CG."""
-    check(self.ctx._L.mi_schur_matfree_interior_levels(self._h, setup._h if setup is not None else None))
-    self._level_setup = setup      # keep the plan alive
-
-
 LocalSchurs.set_blocks = _set_blocks
 NeumannNeumannSchurPreconditioner.set_blocks = _set_blocks
-MatrixFreeLocalSchurs.use_level_solver = _use_level_solver
 
 
-class GlobalSchur(Operator):
+class GlobalSchur(_InteriorSolve, Operator):
     """`x -> apply_global_schur(A_IId, A_IΓd, A_ΓΓ, x; preconds)` (EPDD.jl:596-625), the closure of Example03:101.
     `interior_solvers[d](rhs)` on the host, or — `interior_solvers=None` — the device CG that restates the reference's
     `IterativeSolvers.cg(A_IId[idom], A_IΓd[idom]*x)` (EPDD.jl:609-619; package default reltol = sqrt(eps))."""
@@ -1280,14 +1269,6 @@ class GlobalSchur(Operator):
             ctx._h, i64(ndom), i64(n_Γ), ni.ctypes.data_as(i64p), _ptrs(igp, i64p), _ptrs(igi, i64p), _ptrs(igv, f64p),
             ggp.ctypes.data_as(i64p), ggi.ctypes.data_as(i64p), ggv.ctypes.data_as(f64p), cb, None, C.c_int(index_base), C.byref(h)))
         super().__init__(ctx, h, keep=(cb, interior_solvers))
-
-
-GlobalSchur.interior_solutions = _interior_solutions      # `get_subdomain_solutions` (EPDD.jl:1014-1025), Γ-global columns
-GlobalSchur.schur_rhs = MatrixFreeLocalSchurs.schur_rhs   # `get_schur_rhs` (EPDD.jl:798-821)
-GlobalSchur.interior_precond = _interior_precond
-GlobalSchur.interior_iterations = _interior_iterations
-GlobalSchur.interior_amg = _interior_amg
-GlobalSchur.interior_amg_stats = _interior_amg_stats
 
 
 # reference-named free functions
@@ -1877,6 +1858,3 @@ class HybridSampler(McmcSampler):
         self.ξ = np.concatenate([self.χ, tail])
         self._field()
         return cnt
-
-
-GlobalSchur.use_level_solver = _use_level_solver

@@ -68,6 +68,28 @@ inline int guarded(F &&f) {
   }
 }
 
+// ------------------------------------------------------------------ stream capture
+// What `body` enqueues on `s`, captured and instantiated. A throw of the body ends the capture and goes on to the caller;
+// `what` ("" or a short name) leads the error text of a failed instantiation.
+template <class F>
+inline hipGraphExec_t capture_graph(hipStream_t s, const char *what, F &&body) {
+  hipGraph_t gr = nullptr;
+  MI_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  try {
+    body();
+  } catch (...) {
+    (void)hipStreamEndCapture(s, &gr);
+    if (gr) (void)hipGraphDestroy(gr);
+    throw;
+  }
+  MI_HIP(hipStreamEndCapture(s, &gr));
+  hipGraphExec_t ex = nullptr;
+  hipError_t e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(gr);
+  if (e != hipSuccess) raise(MI_ERR_HIP, "%s%shipGraphInstantiate failed: %s", what, *what ? ": " : "", hipGetErrorString(e));
+  return ex;
+}
+
 // ------------------------------------------------------------------ blocking copies / fills that stay off the legacy stream
 // `hipMemset` / `hipMemcpy` run on the legacy (NULL) stream, which the runtime refuses while ANY stream of the process is
 // being captured ("operation would make the legacy stream depend on a capturing blocking stream") and which also tears

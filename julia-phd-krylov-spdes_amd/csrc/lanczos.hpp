@@ -132,20 +132,7 @@ struct Lanczos {
     }
     auto it = graphs.find(first);
     if (it == graphs.end()) {
-      hipGraph_t gr = nullptr;
-      MI_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      try {
-        for (int j = first; j < m; ++j) step(j);
-      } catch (...) {
-        (void)hipStreamEndCapture(s, &gr);
-        if (gr) (void)hipGraphDestroy(gr);
-        throw;
-      }
-      MI_HIP(hipStreamEndCapture(s, &gr));
-      hipGraphExec_t ex = nullptr;
-      hipError_t e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(gr);
-      if (e != hipSuccess) raise(MI_ERR_HIP, "mi_eigsolve: hipGraphInstantiate failed: %s", hipGetErrorString(e));
+      hipGraphExec_t ex = capture_graph(s, "mi_eigsolve", [&] { for (int j = first; j < m; ++j) step(j); });
       it = graphs.emplace(first, ex).first;
     }
     ++ctx->n_replays;

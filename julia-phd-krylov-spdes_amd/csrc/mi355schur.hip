@@ -868,23 +868,10 @@ static int dominant_impl(mi_op_t op, const double *x, int reps, double *us_per_l
     *us_per_launch = 0.0;
     if (reps == 0) return MI_OK;
     hipStream_t s = c->stream;
-    hipGraph_t gr = nullptr;
-    MI_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    try {
-      for (int i = 0; i < reps; ++i) op->impl->apply_dominant(xi.dev);
-    } catch (...) {
-      (void)hipStreamEndCapture(s, &gr);
-      if (gr) (void)hipGraphDestroy(gr);
-      throw;
-    }
-    MI_HIP(hipStreamEndCapture(s, &gr));
-    hipGraphExec_t ex = nullptr;
-    hipError_t e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(gr);
-    if (e != hipSuccess) raise(MI_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+    hipGraphExec_t ex = capture_graph(s, "", [&] { for (int i = 0; i < reps; ++i) op->impl->apply_dominant(xi.dev); });
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float ms = 0.f;
-    e = hipEventCreate(&e0);
+    hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     if (e == hipSuccess) e = hipGraphLaunch(ex, s);           // warm-up replay
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -1390,20 +1377,23 @@ int mi_schur_matfree_set_values(mi_op_t op, const double *ii_val, const double *
   return guarded([&]() -> int {
     c->use();
     DevBuf<double> s1, s2, s3;
-    In a(c, ii_val, ii_val && m->icg ? (size_t)m->icg->A.nnz : 0, s1), b(c, ig_val, ig_val ? (size_t)m->A_GI.nnz : 0, s2),
+    In a(c, ii_val, ii_val && m->interior.cg() ? (size_t)m->interior.cg()->A.nnz : 0, s1), b(c, ig_val, ig_val ? (size_t)m->A_GI.nnz : 0, s2),
         g(c, gg_val, gg_val ? (size_t)m->A_GG.nnz : 0, s3);
     m->set_values(ii_val ? a.dev : nullptr, ig_val ? b.dev : nullptr, gg_val ? g.dev : nullptr);
     MI_HIP(hipStreamSynchronize(c->stream));  // staging buffers go out of scope
     return MI_OK;
   });
 }
-static GlobalSchurOp *as_global(mi_op_t op) {
-  return op && op->impl ? dynamic_cast<GlobalSchurOp *>(op->impl.get()) : nullptr;
+// either matrix-free Schur operator (MatfreeSchurOp, GlobalSchurOp): what the entry points below need is in their common base
+static InteriorSchurOp *as_interior_schur(mi_op_t op) {
+  return op && op->impl ? dynamic_cast<InteriorSchurOp *>(op->impl.get()) : nullptr;
+}
+static InteriorCg *interior_cg_of(mi_op_t op) {
+  InteriorSchurOp *m = as_interior_schur(op);
+  return m ? m->interior.cg() : nullptr;
 }
 int mi_schur_interior_precond(mi_op_t op, int kind) {
-  MatfreeSchurOp *m = as_matfree(op);
-  GlobalSchurOp *gl = as_global(op);
-  InteriorCg *icg = m ? m->icg.get() : gl ? gl->icg.get() : nullptr;
+  InteriorCg *icg = interior_cg_of(op);
   if (!icg) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_precond: not a Schur operator with the interior solve on the device");
   if (kind != 0 && kind != 1) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_precond: kind must be 0 (none) or 1 (diagonal)");
   return guarded([&]() -> int {
@@ -1413,11 +1403,9 @@ int mi_schur_interior_precond(mi_op_t op, int kind) {
   });
 }
 int mi_schur_interior_amg(mi_op_t op, int64_t nlevels, const int64_t *n_l, const int64_t *const *agg, int index_base) {
-  MatfreeSchurOp *m = as_matfree(op);
-  GlobalSchurOp *gl = as_global(op);
-  InteriorCg *icg = m ? m->icg.get() : gl ? gl->icg.get() : nullptr;
+  InteriorCg *icg = interior_cg_of(op);
   if (!icg) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_amg: not a Schur operator with the interior solve on the device");
-  if (m && m->maps.sharded) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_amg: a sharded operator (the hierarchy is built on one device only)");
+  if (as_interior_schur(op)->sharded()) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_amg: a sharded operator (the hierarchy is built on one device only)");
   mi_ctx_s *c = op->impl->ctx;
   return guarded([&]() -> int {
     c->use();
@@ -1426,9 +1414,7 @@ int mi_schur_interior_amg(mi_op_t op, int64_t nlevels, const int64_t *n_l, const
   });
 }
 int mi_schur_interior_amg_stats(mi_op_t op, int64_t *levels, int64_t *coarse_n, int64_t *bytes_kept) {
-  MatfreeSchurOp *m = as_matfree(op);
-  GlobalSchurOp *gl = as_global(op);
-  InteriorCg *icg = m ? m->icg.get() : gl ? gl->icg.get() : nullptr;
+  InteriorCg *icg = interior_cg_of(op);
   InteriorAmgStats st{};
   if (!icg || !interior_amg_stats(*icg, &st)) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_amg_stats: no AMG `Pl` is selected on this operator");
   if (levels) *levels = st.levels;
@@ -1437,26 +1423,23 @@ int mi_schur_interior_amg_stats(mi_op_t op, int64_t *levels, int64_t *coarse_n, 
   return MI_OK;
 }
 int mi_schur_interior_iterations(mi_op_t op, int64_t *iterations) {
-  MatfreeSchurOp *m = as_matfree(op);
-  GlobalSchurOp *gl = as_global(op);
-  InteriorCg *icg = m ? m->icg.get() : gl ? gl->icg.get() : nullptr;
+  InteriorCg *icg = interior_cg_of(op);
   if (!icg || !iterations) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_iterations: not a Schur operator with the interior solve on the device");
   *iterations = icg->total_iterations;
   return MI_OK;
 }
 int mi_schur_matfree_rhs(mi_op_t op, const double *b_I, const double *b_gamma, double *b_schur) {
-  MatfreeSchurOp *m = as_matfree(op);
-  GlobalSchurOp *gl = as_global(op);
-  const int64_t ni_tot = m ? m->ni_tot : gl ? gl->ni_tot : 0;
-  if ((!m && !gl) || !b_gamma || !b_schur || (ni_tot && !b_I))
+  InteriorSchurOp *m = as_interior_schur(op);
+  const int64_t ni_tot = m ? m->interior.ni_tot : 0;
+  if (!m || !b_gamma || !b_schur || (ni_tot && !b_I))
     return fail(MI_ERR_BAD_ARG, "mi_schur_matfree_rhs: not a matrix-free (local or global) Schur operator, or NULL argument");
-  mi_ctx_s *c = op->impl->ctx;
+  mi_ctx_s *c = m->ctx;
   return guarded([&]() -> int {
     c->use();
     DevBuf<double> s1;
-    In bi(c, b_I, (size_t)ni_tot, s1), bg(c, b_gamma, (size_t)op->impl->n, c->scratch_a);
-    InOut out(c, b_schur, (size_t)op->impl->n, c->scratch_b, false);
-    if (m) m->schur_rhs(bi.dev, bg.dev, out.dev); else gl->schur_rhs(bi.dev, bg.dev, out.dev);
+    In bi(c, b_I, (size_t)ni_tot, s1), bg(c, b_gamma, (size_t)m->n, c->scratch_a);
+    InOut out(c, b_schur, (size_t)m->n, c->scratch_b, false);
+    m->schur_rhs(bi.dev, bg.dev, out.dev);
     out.finish();
     MI_HIP(hipStreamSynchronize(c->stream));
     return MI_OK;
@@ -1464,18 +1447,17 @@ int mi_schur_matfree_rhs(mi_op_t op, const double *b_I, const double *b_gamma, d
 }
 
 int mi_schur_matfree_interior_solutions(mi_op_t op, const double *u_gamma, const double *b_I, double *u_I) {
-  MatfreeSchurOp *m = as_matfree(op);
-  GlobalSchurOp *gl = as_global(op);
-  const int64_t ni_tot = m ? m->ni_tot : gl ? gl->ni_tot : 0;
-  if ((!m && !gl) || !u_gamma || (ni_tot && (!b_I || !u_I)))
+  InteriorSchurOp *m = as_interior_schur(op);
+  const int64_t ni_tot = m ? m->interior.ni_tot : 0;
+  if (!m || !u_gamma || (ni_tot && (!b_I || !u_I)))
     return fail(MI_ERR_BAD_ARG, "mi_schur_matfree_interior_solutions: not a matrix-free (local or global) Schur operator, or NULL argument");
-  mi_ctx_s *c = op->impl->ctx;
+  mi_ctx_s *c = m->ctx;
   return guarded([&]() -> int {
     c->use();
     DevBuf<double> s1, s2;
-    In ug(c, u_gamma, (size_t)op->impl->n, c->scratch_a), bi(c, b_I, (size_t)ni_tot, s1);
+    In ug(c, u_gamma, (size_t)m->n, c->scratch_a), bi(c, b_I, (size_t)ni_tot, s1);
     InOut out(c, u_I, (size_t)ni_tot, s2, false);
-    if (m) m->interior_solutions(ug.dev, bi.dev, out.dev); else gl->interior_solutions(ug.dev, bi.dev, out.dev);
+    m->interior_solutions(ug.dev, bi.dev, out.dev);
     out.finish();
     MI_HIP(hipStreamSynchronize(c->stream));
     return MI_OK;
@@ -1548,20 +1530,16 @@ int mi_schur_setup_interior_solve(mi_setup_t plan, const double *f, double *u) {
 }
 int mi_schur_matfree_interior_levels(mi_op_t op, mi_setup_t plan) {
   if (!op || !op->impl) return fail(MI_ERR_BAD_ARG, "op is NULL");
+  InteriorSchurOp *m = as_interior_schur(op);
+  if (!m) return fail(MI_ERR_BAD_ARG, "mi_schur_matfree_interior_levels: not a matrix-free Schur operator");
+  if (!plan) { m->interior.bind_levels(nullptr, nullptr); return MI_OK; }
+  if (plan->ctx != m->ctx) return fail(MI_ERR_BAD_ARG, "plan and operator live on different contexts");
+  const int ni_tot = m->interior.ni_tot, nd = m->interior.ndom();
+  if ((long long)ni_tot != plan->n_bi || nd != plan->ndom)
+    return fail(MI_ERR_BAD_ARG, "plan and operator differ in their subdomains (%d with %lld interior nodes vs %d with %lld)", plan->ndom, plan->n_bi, nd, (long long)ni_tot);
   return guarded([&]() -> int {
-    MatfreeSchurOp *mf = dynamic_cast<MatfreeSchurOp *>(op->impl.get());
-    GlobalSchurOp *gs = dynamic_cast<GlobalSchurOp *>(op->impl.get());
-    if (!mf && !gs) return fail(MI_ERR_BAD_ARG, "mi_schur_matfree_interior_levels: not a matrix-free Schur operator");
-    std::function<void(const double *, double *)> fn;
-    if (plan) {
-      if (plan->ctx != op->impl->ctx) return fail(MI_ERR_BAD_ARG, "plan and operator live on different contexts");
-      const size_t ni_tot = mf ? mf->ni_tot : gs->ni_tot;
-      const int nd = mf ? mf->maps.ndl : gs->ndom;
-      if ((long long)ni_tot != plan->n_bi || nd != plan->ndom)
-        return fail(MI_ERR_BAD_ARG, "plan and operator differ in their subdomains (%d with %lld interior nodes vs %d with %lld)", plan->ndom, plan->n_bi, nd, (long long)ni_tot);
-      fn = [plan](const double *f, double *u) { gj_level_solve(*plan, f, u); };
-    }
-    if (mf) mf->level_solver = fn; else gs->level_solver = fn;
+    // the plan counts the operator until it unbinds, binds another plan or is destroyed: mi_schur_setup_destroy waits for that
+    m->interior.bind_levels([plan](const double *f, double *u) { gj_level_solve(*plan, f, u); }, &plan->bound_matfree);
     return MI_OK;
   });
 }
@@ -1569,6 +1547,7 @@ int mi_schur_setup_destroy(mi_setup_t plan) {
   if (!plan) return MI_OK;
   if (plan->bound > 0) return fail(MI_ERR_BAD_ARG, "mi_schur_setup_destroy: %d live LORASC operator(s) use this plan; destroy them first", plan->bound);
   if (plan->bound_nni > 0) return fail(MI_ERR_BAD_ARG, "mi_schur_setup_destroy: %d live Neumann-Neumann induced operator(s) use this plan; destroy them first", plan->bound_nni);
+  if (plan->bound_matfree > 0) return fail(MI_ERR_BAD_ARG, "mi_schur_setup_destroy: %d live matrix-free Schur operator(s) solve with this plan; destroy them first", plan->bound_matfree);
   return guarded([&]() -> int {
     plan->ctx->use();
     (void)hipStreamSynchronize(plan->ctx->stream);

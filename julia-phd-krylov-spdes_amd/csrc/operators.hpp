@@ -891,20 +891,8 @@ struct InteriorCg {
     }
     MI_HIP(hipGetLastError());
     if (!graph || graph_x != x) {  // `chunk` iterations per replay
-      if (graph) { (void)hipGraphExecDestroy(graph); graph = nullptr; }
-      hipGraph_t gr = nullptr;
-      MI_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      try {
-        for (int k = 0; k < chunk; ++k) iteration(x);
-      } catch (...) {
-        (void)hipStreamEndCapture(s, &gr);
-        if (gr) (void)hipGraphDestroy(gr);
-        throw;
-      }
-      MI_HIP(hipStreamEndCapture(s, &gr));
-      hipError_t e = hipGraphInstantiate(&graph, gr, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(gr);
-      if (e != hipSuccess) raise(MI_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+      drop_graph();
+      graph = capture_graph(s, "", [&] { for (int k = 0; k < chunk; ++k) iteration(x); });
       graph_x = x;
     }
     const long long max_replays = (long long)n / chunk + 2;  // maxiter = size(A, 2)
@@ -936,43 +924,106 @@ struct InteriorCg {
   }
 };
 
+// ------------------------------------------------------------------ v = A_II^{-1} rhs for a set of subdomains
+// The interior solve of the two matrix-free Schur operators below, over the concatenated interior vectors of their
+// subdomains. In the order of preference: the level inverses a set-up plan keeps (exact; mi_schur_matfree_interior_levels,
+// setup_gj.hpp), the device CG above (the reference's own inexact `IterativeSolvers.cg(A_IIdd, rhs; reltol)`, SURVEY.md
+// §8 f2), the host callback through pinned staging (north_star: interior solve on the host).
+struct InteriorSolver {
+  mi_ctx_s *ctx = nullptr;
+  std::vector<int> ni, ioff;   // per subdomain: interior size, offset in the concatenated vectors
+  int ni_tot = 0;
+  int64_t d0 = 0;              // global index of the first subdomain (what the callback and its error text are given)
+  mi_interior_solve_fn callback = nullptr; void *user = nullptr;
+  HostStage stage;
+  std::unique_ptr<InteriorCg> icg;
+  std::function<void(const double *, double *)> level_solver;
+  int *level_users = nullptr;  // the bound plan's count of operators like this one: mi_schur_setup_destroy is refused while > 0
+
+  InteriorSolver() = default;
+  InteriorSolver(const InteriorSolver &) = delete;
+  InteriorSolver &operator=(const InteriorSolver &) = delete;
+  ~InteriorSolver() { bind_levels(nullptr, nullptr); }
+
+  // Subdomains d0 .. d0 + ndl - 1 of the caller's arrays. With `ii_ptr` (CSC arrays of the A_IIdd): blockdiag(A_IIdd) goes
+  // to the device CG; without: `f` is called through the staging.
+  void build(mi_ctx_s *c, int ndl, int64_t d0_, const int64_t *n_i, mi_interior_solve_fn f, void *u, const int64_t *const *ii_ptr,
+             const int64_t *const *ii_idx, const double *const *ii_val, double reltol, int base) {
+    ctx = c; d0 = d0_; callback = f; user = u;
+    if (ii_ptr && (!ii_idx || !ii_val || !(reltol > 0.0))) raise(MI_ERR_BAD_ARG, "device interior: bad A_II arrays / reltol");
+    int64_t itot = 0;
+    for (int dl = 0; dl < ndl; ++dl) {
+      ioff.push_back((int)itot); ni.push_back((int)n_i[d0 + dl]); itot += n_i[d0 + dl];
+      if (itot >= INT32_MAX) raise(MI_ERR_BAD_ARG, "interior too large");
+    }
+    ni_tot = (int)itot;
+    if (!ii_ptr) { stage.ensure(ni_tot); return; }
+    HostCsr ii;
+    for (int dl = 0; dl < ndl; ++dl)
+      append_block(ii, host_csr(ni[dl], ni[dl], ii_ptr[d0 + dl], ii_idx[d0 + dl], ii_val[d0 + dl], base), ioff[dl], ni_tot);
+    if (ii.rowptr.empty()) ii.rowptr = {0};
+    icg.reset(new InteriorCg);
+    icg->build(c, ii, ioff, ni, reltol);
+  }
+  int ndom() const { return (int)ni.size(); }
+  InteriorCg *cg() const { return icg.get(); }
+  // `fn` replaces the interior CG / the callback until it is unbound (empty `fn`); `users` is counted up while it is bound
+  void bind_levels(std::function<void(const double *, double *)> fn, int *users) {
+    if (level_users) --*level_users;
+    level_solver = std::move(fn);
+    level_users = level_solver ? users : nullptr;
+    if (level_users) ++*level_users;
+  }
+  // out = A_II^{-1} rhs for every subdomain (device pointers, concatenated), enqueued on ctx->stream
+  void solve(const double *rhs, double *out) {
+    if (level_solver) { level_solver(rhs, out); return; }
+    if (icg) { icg->solve(rhs, out); return; }
+    hipStream_t s = ctx->stream;
+    MI_HIP(hipMemcpyAsync(stage.rhs, rhs, sizeof(double) * ni_tot, hipMemcpyDeviceToHost, s));
+    MI_HIP(hipStreamSynchronize(s));
+    for (int dl = 0; dl < ndom(); ++dl)
+      if (callback(user, d0 + dl, ni[dl], stage.rhs + ioff[dl], stage.sol + ioff[dl]) != 0)
+        raise(MI_ERR_CALLBACK, "interior solve callback failed on subdomain %lld", (long long)(d0 + dl));
+    MI_HIP(hipMemcpyAsync(out, stage.sol, sizeof(double) * ni_tot, hipMemcpyHostToDevice, s));
+  }
+};
+
+// What the two matrix-free Schur operators share beyond `Operator`: the interior solver and the two solves built on it
+struct InteriorSchurOp : Operator {
+  InteriorSolver interior;
+  using Operator::Operator;
+  bool graph_safe() const override { return false; }
+  virtual bool sharded() const { return false; }
+  // b_schur = b_Γ - Σ_d A_IΓd' (A_IId^{-1} b_Id)   (get_schur_rhs); b_I: concatenated b_Id
+  virtual void schur_rhs(const double *b_I, const double *b_gamma, double *out) = 0;
+  // u_Id = A_IId^{-1} (b_Id - A_IΓd u_Γ) for every subdomain (get_subdomain_solutions); b_I / u_I: concatenated
+  virtual void interior_solutions(const double *u_gamma, const double *b_I, double *u_I) = 0;
+};
+
 // ------------------------------------------------------------------ matrix-free local Schur operator (EPDD.jl:711-747)
 // All local subdomains are stacked into block-diagonal CSR matrices over the concatenated local
-// spaces, so one SpMV launch serves every subdomain: rhs = A_IΓ xd ; t = A_ΓΓ xd ; yloc = t - A_ΓI v.
-// v = A_II^{-1} rhs is either the host callback (north_star: interior solve on the host) or the device CG
-// above (the reference's own inexact `IterativeSolvers.cg(A_IIdd, rhs; reltol)`).
-struct MatfreeSchurOp : Operator {
+// spaces, so one SpMV launch serves every subdomain: rhs = A_IΓ xd ; t = A_ΓΓ xd ; yloc = t - A_ΓI v, v = A_II^{-1} rhs.
+struct MatfreeSchurOp : InteriorSchurOp {
   LocalMaps maps;
   CsrDev A_IG, A_GI, A_GG;
-  std::vector<int> ni, ioff;
-  int64_t d0;
-  int ni_tot = 0;
-  mi_interior_solve_fn solve; void *user;
-  std::unique_ptr<InteriorCg> icg;
-  // exact interior solve by the level inverses a set-up plan keeps (mi_schur_matfree_interior_levels; setup_gj.hpp): when set,
-  // it replaces the callback / the interior CG in every interior solve of this operator
-  std::function<void(const double *, double *)> level_solver;
   DevBuf<double> xcat, rhs, sol, t1, yloc, t2;
   DevBuf<int> ig_perm;  // A_IG.val[k] = (caller's concatenated A_IΓ values)[ig_perm[k]]  (set_values)
-  HostStage stage;
 
   MatfreeSchurOp(mi_ctx_s *c, int64_t ndom, int64_t n_gamma, const int64_t *n_gamma_d, const int64_t *n_i,
                  const int64_t *const *gather_idx, const int64_t *const *ig_ptr, const int64_t *const *ig_idx,
                  const double *const *ig_val, const int64_t *const *gg_ptr, const int64_t *const *gg_idx,
-                 const double *const *gg_val, mi_interior_solve_fn f, void *u, int base, int64_t d0_, int64_t d1,
+                 const double *const *gg_val, mi_interior_solve_fn f, void *u, int base, int64_t d0, int64_t d1,
                  const int64_t *const *ii_ptr = nullptr, const int64_t *const *ii_idx = nullptr,
                  const double *const *ii_val = nullptr, double reltol = 1e-9)
-      : Operator(c, n_gamma), d0(d0_), solve(f), user(u) {
+      : InteriorSchurOp(c, n_gamma) {
     if ((!f && !ii_ptr) || !n_i || !ig_ptr || !ig_idx || !ig_val || !gg_ptr || !gg_idx || !gg_val)
       raise(MI_ERR_BAD_ARG, "mi_schur_matfree_create: NULL argument");
-    if (ii_ptr && (!ii_idx || !ii_val || !(reltol > 0.0))) raise(MI_ERR_BAD_ARG, "device interior: bad A_II arrays / reltol");
     maps.build(c, ndom, n_gamma, n_gamma_d, gather_idx, base, d0, d1);
-    HostCsr ig, gi, gg, ii;
+    interior.build(c, maps.ndl, d0, n_i, f, u, ii_ptr, ii_idx, ii_val, reltol, base);
+    const std::vector<int> &ni = interior.ni, &ioff = interior.ioff;
+    const int ni_tot = interior.ni_tot;
+    HostCsr ig, gi, gg;
     std::vector<int> perm_h;
-    int64_t itot = 0;
-    for (int dl = 0; dl < maps.ndl; ++dl) { ioff.push_back((int)itot); ni.push_back((int)n_i[d0 + dl]); itot += n_i[d0 + dl]; }
-    if (itot >= INT32_MAX) raise(MI_ERR_BAD_ARG, "interior too large");
-    ni_tot = (int)itot;
     for (int dl = 0; dl < maps.ndl; ++dl) {
       const int64_t d = d0 + dl;
       // CSC arrays of A_IΓdd (n_i x n_Γd) are the CSR arrays of A_ΓIdd = A_IΓdd' (n_Γd x n_i)
@@ -988,21 +1039,14 @@ struct MatfreeSchurOp : Operator {
       append_block(gi, gi_d, ioff[dl], ni_tot);
       append_block(ig, ig_d, maps.loc_off[dl], maps.nloc);
       append_block(gg, gg_d, maps.loc_off[dl], maps.nloc);
-      if (ii_ptr) append_block(ii, host_csr(ni[dl], ni[dl], ii_ptr[d], ii_idx[d], ii_val[d], base), ioff[dl], ni_tot);
     }
-    if (gi.rowptr.empty()) { gi.rowptr = {0}; ig.rowptr = {0}; gg.rowptr = {0}; ii.rowptr = {0}; }
+    if (gi.rowptr.empty()) { gi.rowptr = {0}; ig.rowptr = {0}; gg.rowptr = {0}; }
     A_IG.upload(ig, c->stream); A_GI.upload(gi, c->stream); A_GG.upload(gg, c->stream);
     ig_perm.upload(perm_h, c->stream);
     xcat.alloc(maps.nloc + 1); t1.alloc(maps.nloc + 1); yloc.alloc(maps.nloc + 1);
     rhs.alloc(ni_tot + 1); sol.alloc(ni_tot + 1); t2.alloc((size_t)n_gamma + 1);
-    if (ii_ptr) {
-      icg.reset(new InteriorCg);
-      icg->build(c, ii, ioff, ni, reltol);
-    } else {
-      stage.ensure(ni_tot);
-    }
   }
-  bool graph_safe() const override { return false; }
+  bool sharded() const override { return maps.sharded; }
   void apply(const double *x, double *y, const int *) override {
     hipStream_t s = ctx->stream;
     if (maps.nloc) {
@@ -1010,18 +1054,7 @@ struct MatfreeSchurOp : Operator {
       MI_HIP(hipGetLastError());
       A_IG.launch(0, xcat.p, nullptr, rhs.p, nullptr, s);
       A_GG.launch(0, xcat.p, nullptr, t1.p, nullptr, s);
-      if (level_solver) {
-        level_solver(rhs.p, sol.p);
-      } else if (icg) {
-        icg->solve(rhs.p, sol.p);
-      } else {
-        MI_HIP(hipMemcpyAsync(stage.rhs, rhs.p, sizeof(double) * ni_tot, hipMemcpyDeviceToHost, s));
-        MI_HIP(hipStreamSynchronize(s));
-        for (int dl = 0; dl < maps.ndl; ++dl)
-          if (solve(user, d0 + dl, ni[dl], stage.rhs + ioff[dl], stage.sol + ioff[dl]) != 0)
-            raise(MI_ERR_CALLBACK, "interior solve callback failed on subdomain %lld", (long long)(d0 + dl));
-        MI_HIP(hipMemcpyAsync(sol.p, stage.sol, sizeof(double) * ni_tot, hipMemcpyHostToDevice, s));
-      }
+      interior.solve(rhs.p, sol.p);
       A_GI.launch(1, sol.p, t1.p, yloc.p, nullptr, s);
     }
     maps.assemble(ctx, n, yloc.p, y, nullptr);
@@ -1031,6 +1064,7 @@ struct MatfreeSchurOp : Operator {
   void set_values(const double *ii_val, const double *ig_val, const double *gg_val) {
     hipStream_t s = ctx->stream;
     if (ii_val) {
+      InteriorCg *icg = interior.cg();
       if (!icg) raise(MI_ERR_BAD_ARG, "set_values: A_II lives in the interior-solve callback of this operator");
       // AMG `Pl`: its hierarchy first, from the caller's values. A refusal (MI_ERR_SINGULAR) leaves this call before anything of
       // the operator has changed: matrices, diagonal and hierarchy are those of the call before.
@@ -1045,56 +1079,33 @@ struct MatfreeSchurOp : Operator {
     }
     if (gg_val && A_GG.nnz) MI_HIP(hipMemcpyAsync(A_GG.val.p, gg_val, sizeof(double) * A_GG.nnz, hipMemcpyDeviceToDevice, s));
   }
-  // b_schur = b_Γ - Σ_d R_d' A_IΓdd' (A_IIdd^{-1} b_Id)   (get_schur_rhs, EPDD.jl:835-864); b_I: concatenated b_Id
-  void schur_rhs(const double *b_I, const double *b_gamma, double *out) {
+  // get_schur_rhs, EPDD.jl:835-864 (Σ_d R_d' A_IΓdd' ...)
+  void schur_rhs(const double *b_I, const double *b_gamma, double *out) override {
     hipStream_t s = ctx->stream;
     if (maps.nloc) {
-      if (level_solver) {
-        level_solver(b_I, sol.p);
-      } else if (icg) {
-        icg->solve(b_I, sol.p);
-      } else {
-        MI_HIP(hipMemcpyAsync(stage.rhs, b_I, sizeof(double) * ni_tot, hipMemcpyDeviceToHost, s));
-        MI_HIP(hipStreamSynchronize(s));
-        for (int dl = 0; dl < maps.ndl; ++dl)
-          if (solve(user, d0 + dl, ni[dl], stage.rhs + ioff[dl], stage.sol + ioff[dl]) != 0)
-            raise(MI_ERR_CALLBACK, "interior solve callback failed on subdomain %lld", (long long)(d0 + dl));
-        MI_HIP(hipMemcpyAsync(sol.p, stage.sol, sizeof(double) * ni_tot, hipMemcpyHostToDevice, s));
-      }
+      interior.solve(b_I, sol.p);
       A_GI.launch(0, sol.p, nullptr, yloc.p, nullptr, s);
     }
     maps.assemble(ctx, n, yloc.p, t2.p, nullptr);
     hipLaunchKernelGGL(k_sub, dim3(vec_grid(n)), dim3(NT), 0, s, (int)n, b_gamma, t2.p, out);
     MI_HIP(hipGetLastError());
   }
-  // u_Id = A_IIdd^{-1} (b_Id - A_IΓdd u_Γd) for every local subdomain (get_subdomain_solutions, EPDD.jl:1014-1025);
-  // b_I / u_I: concatenated over the local subdomains
-  void interior_solutions(const double *u_gamma, const double *b_I, double *u_I) {
+  // get_subdomain_solutions, EPDD.jl:1014-1025, for every local subdomain
+  void interior_solutions(const double *u_gamma, const double *b_I, double *u_I) override {
     hipStream_t s = ctx->stream;
     if (!maps.nloc) return;
     hipLaunchKernelGGL(k_gather, dim3(vec_grid(maps.nloc)), dim3(NT), 0, s, maps.nloc, maps.gidx.p, u_gamma, xcat.p);
     MI_HIP(hipGetLastError());
     A_IG.launch(1, xcat.p, b_I, rhs.p, nullptr, s);  // rhs = b_I - A_IΓ u_Γd
-    if (level_solver) {
-      level_solver(rhs.p, u_I);
-    } else if (icg) {
-      icg->solve(rhs.p, u_I);
-    } else {
-      MI_HIP(hipMemcpyAsync(stage.rhs, rhs.p, sizeof(double) * ni_tot, hipMemcpyDeviceToHost, s));
-      MI_HIP(hipStreamSynchronize(s));
-      for (int dl = 0; dl < maps.ndl; ++dl)
-        if (solve(user, d0 + dl, ni[dl], stage.rhs + ioff[dl], stage.sol + ioff[dl]) != 0)
-          raise(MI_ERR_CALLBACK, "interior solve callback failed on subdomain %lld", (long long)(d0 + dl));
-      MI_HIP(hipMemcpyAsync(u_I, stage.sol, sizeof(double) * ni_tot, hipMemcpyHostToDevice, s));
-    }
+    interior.solve(rhs.p, u_I);
   }
   void bytes(int64_t *a, int64_t *d) const override {
-    *a = A_IG.bytes() + A_GI.bytes() + A_GG.bytes() + 16ll * ni_tot;
-    *d = icg ? icg->A.bytes() : A_IG.bytes();
+    *a = A_IG.bytes() + A_GI.bytes() + A_GG.bytes() + 16ll * interior.ni_tot;
+    *d = interior.cg() ? interior.cg()->A.bytes() : A_IG.bytes();
   }
   void apply_dominant(const double *x) override {
     if (!maps.nloc) return;
-    if (icg) {  // the A_II SpMV of the interior CG (x is not used: the operand is the CG direction buffer)
+    if (InteriorCg *icg = interior.cg()) {  // the A_II SpMV of the interior CG (x is not used: the operand is the CG direction buffer)
       icg->A.launch(0, icg->u.p, nullptr, icg->c.p, nullptr, ctx->stream, icg->u.p, icg->p_uc.p);
       return;
     }
@@ -1104,98 +1115,56 @@ struct MatfreeSchurOp : Operator {
 };
 
 // ------------------------------------------------------------------ apply_global_schur (EPDD.jl:596-625)
-struct GlobalSchurOp : Operator {
+struct GlobalSchurOp : InteriorSchurOp {
   int ndom;
   std::vector<CsrDev> A_IG, A_GI;  // per subdomain: (n_i x n_Γ) and its transpose (n_Γ x n_i)
   CsrDev A_GG;
-  std::vector<int> ni, ioff;
-  int ni_tot = 0;
-  mi_interior_solve_fn solve; void *user;
   DevBuf<double> rhs, sol;
-  HostStage stage;
-
-  std::unique_ptr<InteriorCg> icg;  // device interior solve (no callback): IterativeSolvers.cg restated, all subdomains at once
-  std::function<void(const double *, double *)> level_solver;   // as in MatfreeSchurOp
 
   GlobalSchurOp(mi_ctx_s *c, int64_t ndom_, int64_t n_gamma, const int64_t *n_i, const int64_t *const *ig_ptr,
                 const int64_t *const *ig_idx, const double *const *ig_val, const int64_t *gg_ptr, const int64_t *gg_idx,
                 const double *gg_val, mi_interior_solve_fn f, void *u, int base, const int64_t *const *ii_ptr = nullptr,
                 const int64_t *const *ii_idx = nullptr, const double *const *ii_val = nullptr, double reltol = 0.0)
-      : Operator(c, n_gamma), ndom((int)ndom_), solve(f), user(u) {
+      : InteriorSchurOp(c, n_gamma), ndom((int)ndom_) {
     if ((!f && !ii_ptr) || ndom_ <= 0 || !n_i || !ig_ptr || !ig_idx || !ig_val || !gg_ptr)
       raise(MI_ERR_BAD_ARG, "mi_schur_global_create: NULL argument");
-    if (ii_ptr && (!ii_idx || !ii_val || !(reltol > 0.0))) raise(MI_ERR_BAD_ARG, "device interior: bad A_II arrays / reltol");
+    interior.build(c, ndom, 0, n_i, f, u, ii_ptr, ii_idx, ii_val, reltol, base);
     A_IG.resize(ndom); A_GI.resize(ndom);
-    int64_t itot = 0;
     for (int d = 0; d < ndom; ++d) {
-      ioff.push_back((int)itot); ni.push_back((int)n_i[d]); itot += n_i[d];
-      if (itot >= INT32_MAX) raise(MI_ERR_BAD_ARG, "interior too large");
       HostCsr gi_d = host_csr(n_gamma, n_i[d], ig_ptr[d], ig_idx[d], ig_val[d], base);
       A_GI[d].upload(gi_d, c->stream);
       A_IG[d].upload(transpose(gi_d), c->stream);
     }
-    ni_tot = (int)itot;
     A_GG.upload(host_csr(n_gamma, n_gamma, gg_ptr, gg_idx, gg_val, base), c->stream);
-    rhs.alloc(ni_tot + 1); sol.alloc(ni_tot + 1);
-    if (ii_ptr) {
-      HostCsr ii;
-      for (int d = 0; d < ndom; ++d) append_block(ii, host_csr(ni[d], ni[d], ii_ptr[d], ii_idx[d], ii_val[d], base), ioff[d], ni_tot);
-      if (ii.rowptr.empty()) ii.rowptr = {0};
-      icg.reset(new InteriorCg);
-      icg->build(c, ii, ioff, ni, reltol);
-    } else {
-      stage.ensure(ni_tot);
-    }
+    rhs.alloc(interior.ni_tot + 1); sol.alloc(interior.ni_tot + 1);
   }
-  bool graph_safe() const override { return false; }
   bool writes_y_once() const override { return false; }  // y = A_ΓΓ x, then ndom in-place `y -= A_IΓd' v` passes
   void apply(const double *x, double *y, const int *) override {
     hipStream_t s = ctx->stream;
+    const std::vector<int> &ioff = interior.ioff;
     A_GG.launch(0, x, nullptr, y, nullptr, s);  // Sx = A_ΓΓ * x
     for (int d = 0; d < ndom; ++d) A_IG[d].launch(0, x, nullptr, rhs.p + ioff[d], nullptr, s);
-    if (level_solver) {
-      level_solver(rhs.p, sol.p);
-    } else if (icg) {
-      icg->solve(rhs.p, sol.p);
-    } else {
-      MI_HIP(hipMemcpyAsync(stage.rhs, rhs.p, sizeof(double) * ni_tot, hipMemcpyDeviceToHost, s));
-      MI_HIP(hipStreamSynchronize(s));
-      for (int d = 0; d < ndom; ++d)
-        if (solve(user, d, ni[d], stage.rhs + ioff[d], stage.sol + ioff[d]) != 0)
-          raise(MI_ERR_CALLBACK, "interior solve callback failed on subdomain %d", d);
-      MI_HIP(hipMemcpyAsync(sol.p, stage.sol, sizeof(double) * ni_tot, hipMemcpyHostToDevice, s));
-    }
+    interior.solve(rhs.p, sol.p);
     for (int d = 0; d < ndom; ++d) A_GI[d].launch(1, sol.p + ioff[d], y, y, nullptr, s);  // Sx .-= A_IΓd' * v
   }
-  // A_IId^{-1} v for every subdomain (device pointers; v, out: concatenated over the subdomains)
-  void interior_solve(const double *v, double *out) {
+  // get_schur_rhs, EPDD.jl:798-821, subdomain by subdomain
+  void schur_rhs(const double *b_I, const double *b_gamma, double *out) override {
     hipStream_t s = ctx->stream;
-    if (level_solver) { level_solver(v, out); return; }
-    if (icg) { icg->solve(v, out); return; }
-    MI_HIP(hipMemcpyAsync(stage.rhs, v, sizeof(double) * ni_tot, hipMemcpyDeviceToHost, s));
-    MI_HIP(hipStreamSynchronize(s));
-    for (int d = 0; d < ndom; ++d)
-      if (solve(user, d, ni[d], stage.rhs + ioff[d], stage.sol + ioff[d]) != 0)
-        raise(MI_ERR_CALLBACK, "interior solve callback failed on subdomain %d", d);
-    MI_HIP(hipMemcpyAsync(out, stage.sol, sizeof(double) * ni_tot, hipMemcpyHostToDevice, s));
-  }
-  // b_schur = b_Γ - Σ_d A_IΓd' (A_IId \ b_Id), subdomain by subdomain (get_schur_rhs, EPDD.jl:798-821)
-  void schur_rhs(const double *b_I, const double *b_gamma, double *out) {
-    hipStream_t s = ctx->stream;
-    interior_solve(b_I, sol.p);
+    interior.solve(b_I, sol.p);
     MI_HIP(hipMemcpyAsync(out, b_gamma, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    for (int d = 0; d < ndom; ++d) A_GI[d].launch(1, sol.p + ioff[d], out, out, nullptr, s);
+    for (int d = 0; d < ndom; ++d) A_GI[d].launch(1, sol.p + interior.ioff[d], out, out, nullptr, s);
   }
-  // u_Id = A_IId \ (b_Id - A_IΓd u_Γ) (get_subdomain_solutions, EPDD.jl:1014-1025)
-  void interior_solutions(const double *u_gamma, const double *b_I, double *u_I) {
+  // get_subdomain_solutions, EPDD.jl:1014-1025
+  void interior_solutions(const double *u_gamma, const double *b_I, double *u_I) override {
     hipStream_t s = ctx->stream;
+    const std::vector<int> &ioff = interior.ioff;
     for (int d = 0; d < ndom; ++d) A_IG[d].launch(1, u_gamma, b_I + ioff[d], rhs.p + ioff[d], nullptr, s);
-    interior_solve(rhs.p, u_I);
+    interior.solve(rhs.p, u_I);
   }
   void bytes(int64_t *a, int64_t *dd) const override {
     int64_t t = A_GG.bytes();
     for (int d = 0; d < ndom; ++d) t += A_IG[d].bytes() + A_GI[d].bytes();
-    *a = t + 16ll * ni_tot; *dd = A_GG.bytes();
+    *a = t + 16ll * interior.ni_tot; *dd = A_GG.bytes();
   }
   void apply_dominant(const double *) override {}
 };

@@ -92,6 +92,7 @@ struct mi_setup_s : mi::setup::Plan {
   std::unique_ptr<mi::GjState> gj;       // block Gauss-Jordan elimination, batched over the subdomains, replayed from a hipGraph
   int bound = 0;                         // operators that borrow this plan (lorasc.hpp): mi_schur_setup_destroy is refused while > 0
   int bound_nni = 0;                     // ... and the Neumann-Neumann induced operators that do (nn_induced.hpp)
+  int bound_matfree = 0;                 // ... and the matrix-free Schur operators that solve their interiors with its levels (InteriorSolver)
 };
 
 namespace mi {
@@ -1082,15 +1083,7 @@ inline void gj_level_solve(mi_setup_s &P, const double *f, double *u) {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(s, &cap);
   if (cap != hipStreamCaptureStatusNone || env_int("MI355_SETUP_NO_GRAPH", 0)) { gj_level_enqueue(P, s, f, u); return; }   // inside somebody's capture: plain launches
-  if (!G.solve_graph) {
-    hipGraph_t gr = nullptr;
-    MI_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    try { gj_level_enqueue(P, s, G.sv_in.p, G.sv_out.p); } catch (...) { (void)hipStreamEndCapture(s, &gr); if (gr) (void)hipGraphDestroy(gr); throw; }
-    MI_HIP(hipStreamEndCapture(s, &gr));
-    hipError_t e = hipGraphInstantiate(&G.solve_graph, gr, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(gr);
-    if (e != hipSuccess) { G.solve_graph = nullptr; raise(MI_ERR_HIP, "level solves: hipGraphInstantiate failed: %s", hipGetErrorString(e)); }
-  }
+  if (!G.solve_graph) G.solve_graph = capture_graph(s, "level solves", [&] { gj_level_enqueue(P, s, G.sv_in.p, G.sv_out.p); });
   MI_HIP(hipMemcpyAsync(G.sv_in.p, f, sizeof(double) * (size_t)P.n_bi, hipMemcpyDeviceToDevice, s));
   MI_HIP(hipGraphLaunch(G.solve_graph, s));
   MI_HIP(hipMemcpyAsync(u, G.sv_out.p, sizeof(double) * (size_t)P.n_bi, hipMemcpyDeviceToDevice, s));

@@ -483,40 +483,34 @@ struct Krylov {
     GraphKey key{A, M, nvec, chunk, eig.tag * 8 + (fused ? 1 : 0) + (fold ? 2 : 0) + (csrfold() ? 4 : 0) + 1024 * whole};  // the loop form is part of the graph
     auto it = ws.graphs.find(key);
     if (it != ws.graphs.end()) return it->second;
-    hipGraph_t gr = nullptr;
-    MI_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    hipGraphExec_t ex = nullptr;
     try {
-      capture_whole = whole;
-      if (whole == 2) {   // folded loop, x0 == 0: one entry launch
+      ex = capture_graph(s, "", [&] {
+        capture_whole = whole;
+        if (whole == 2) {   // folded loop, x0 == 0: one entry launch
 #define MI_CALL(E) hipLaunchKernelGGL((k_entry_zero<E>), dim3(1), dim3(NTF), 0, s, n, ws.args, ws.b, ws.x, ws.r, ws.st, ws.args_dev.p, &ws.flags[0])
-        MI_EPT_DISPATCH(MI_CALL);
+          MI_EPT_DISPATCH(MI_CALL);
 #undef MI_CALL
-        MI_HIP(hipGetLastError());
-      } else {
+          MI_HIP(hipGetLastError());
+        } else {
+          if (whole) {
+            hipLaunchKernelGGL(k_solve_begin_g, dim3(g), dim3(NT), 0, s, n, ws.args, ws.b, ws.x, ws.st, ws.args_dev.p, &ws.flags[0]);
+            MI_HIP(hipGetLastError());
+          }
+          if (chunk < 0) setup_tail();
+        }
+        for (int k = 0; k < std::abs(chunk); ++k) iteration();
+        capture_whole = 0;
         if (whole) {
-          hipLaunchKernelGGL(k_solve_begin_g, dim3(g), dim3(NT), 0, s, n, ws.args, ws.b, ws.x, ws.st, ws.args_dev.p, &ws.flags[0]);
+          hipLaunchKernelGGL(k_solve_end_g, dim3(g), dim3(NT), 0, s, n, ws.st, ws.args_dev.p, (int)(fold || csrfold()), ws.x, ws.res_norm.p,
+                             &ws.flags[0], &ws.st->x0_zero, ws.end_count.p);
           MI_HIP(hipGetLastError());
         }
-        if (chunk < 0) setup_tail();
-      }
-      for (int k = 0; k < std::abs(chunk); ++k) iteration();
-      capture_whole = 0;
-      if (whole) {
-        hipLaunchKernelGGL(k_solve_end_g, dim3(g), dim3(NT), 0, s, n, ws.st, ws.args_dev.p, (int)(fold || csrfold()), ws.x, ws.res_norm.p,
-                           &ws.flags[0], &ws.st->x0_zero, ws.end_count.p);
-        MI_HIP(hipGetLastError());
-      }
+      });
     } catch (...) {
       capture_whole = 0;
-      (void)hipStreamEndCapture(s, &gr);
-      if (gr) (void)hipGraphDestroy(gr);
       throw;
     }
-    MI_HIP(hipStreamEndCapture(s, &gr));
-    hipGraphExec_t ex = nullptr;
-    hipError_t e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(gr);
-    if (e != hipSuccess) raise(MI_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
     ws.graphs[key] = ex;
     return ex;
   }

@@ -332,7 +332,11 @@ function interior_solve(p::SchurSetup, f::Vector{Float64})
   check(ccall((:mi_schur_setup_interior_solve, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), p.h, f, u))
   u
 end
-use_level_solver!(S::MiOperator, p::SchurSetup) = check(ccall((:mi_schur_matfree_interior_levels, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), S.h, p.h))
+function use_level_solver!(S::MiOperator, p::SchurSetup)
+  check(ccall((:mi_schur_matfree_interior_levels, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), S.h, p.h))
+  S.keep = (S.keep, p)   # the plan outlives S: while S is bound the library refuses the mi_schur_setup_destroy of p's finalizer
+  nothing
+end
 
 # ---------------------------------------------------------------- one Julia worker per GPU
 # The reference's sketch of the distributed apply is `@sync @distributed (+) for idom` (EllipticPdePllDomainDecomposition.jl:

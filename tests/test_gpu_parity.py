@@ -200,6 +200,40 @@ def test_matrix_free_and_global_schur_vs_oracle(pkg, ctx, orc, fem, ragged):
     assert_history(pkg.api.pcg(Sm, P.b_schur, np.zeros(n), M), orc.pcg(Smo, P.b_schur, np.zeros(n), Mo))
 
 
+def test_failing_interior_callback_names_the_global_subdomain_and_leaves_no_trace(pkg, ctx, fem, ragged):
+    """The host callback returns an error for one subdomain: `apply`, `schur_rhs` and `interior_solutions` of both
+    matrix-free operators return MI_ERR_CALLBACK naming the GLOBAL subdomain (a slice 2..4 fails on its local subdomain 1),
+    and once the callback works again the same handles give the bits they gave before."""
+    api, P = pkg.api, ragged
+    n, k, (lo, hi) = P.sub.n_Γ, 3, (2, 5)
+    failing = {"on": False}
+
+    def guard(d, solve):
+        def f(rhs):
+            if failing["on"] and d == k:
+                raise RuntimeError("interior solver %d fails" % d)
+            return solve(rhs)
+        return f
+
+    solvers = [guard(d, s) for d, s in enumerate(P.solvers)]
+    Sm = api.MatrixFreeLocalSchurs(ctx, P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd, P.sub.gather_idx, P.sub.node_Γ_cnt, solvers, dom_slice=(lo, hi))
+    coeff = lognormal_coeff(fem, P.mesh.points, 7)
+    A_IIg, A_IΓg, A_ΓΓ, b_Id, b_Γ = fem.prepare_global_schur(P.mesh.cells, P.mesh.points, P.epart, P.sub, coeff, f_m1, u0734)
+    Sg = api.GlobalSchur(ctx, A_IIg, A_IΓg, A_ΓΓ, solvers)
+    v = np.random.default_rng(12).standard_normal(n)
+    for S, bI in ((Sm, np.concatenate(P.b_Id[lo:hi])), (Sg, np.concatenate(b_Id))):
+        calls = (lambda: S * v, lambda: S.schur_rhs(bI, b_Γ), lambda: S.interior_solutions(v, bI))
+        before = [c() for c in calls]
+        failing["on"] = True
+        for c in calls:
+            with pytest.raises(pkg._lib.MiError) as e:
+                c()
+            assert e.value.code == pkg._lib.MI_ERR_CALLBACK and "subdomain %d" % k in str(e.value), str(e.value)
+        failing["on"] = False
+        for c, want in zip(calls, before):
+            assert np.array_equal(c(), want)
+
+
 # ------------------------------------------------------------------ solvers
 @pytest.mark.parametrize("case", ["micro", "toy", "ragged"])
 def test_schur_solvers_vs_oracle(pkg, ctx, orc, case, micro, toy, ragged):

@@ -228,3 +228,82 @@ def test_level_solves_exact_interior_solve_on_the_device(pkg, ctx, orc, fem, N, 
     Smf.use_level_solver(None)                                          # back to the interior CG of the operator
     y2 = Smf * v
     assert np.abs(y2 - y).max() <= 1e-7 * np.abs(y).max()
+
+
+def _global_blocks(fem, P):
+    """`prepare_global_schur` of the `ragged` problem: the same interiors as P.A_IIdd, A_IΓd with Γ-global columns."""
+    coeff = lognormal_coeff(fem, P.mesh.points, 7)
+    return fem.prepare_global_schur(P.mesh.cells, P.mesh.points, P.epart, P.sub, coeff, f_m1, u0734)
+
+
+def test_level_solver_on_the_global_schur_operator(pkg, ctx, orc, fem, ragged):
+    """`GlobalSchur.use_level_solver`: the plan of the test above (N = 50, 3 x 2, seed 7 is the `ragged` fixture) serves
+    `apply_global_schur`, `get_schur_rhs` and `get_subdomain_solutions` of the Γ-global operator; against the host's
+    sparse direct solves at that test's bar, 1e-10 of the largest entry."""
+    api, P = pkg.api, ragged
+    n = P.sub.n_Γ
+    setup = api.SchurSetup(ctx, P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd)
+    setup.keep_levels(True)
+    setup.run()
+    A_IIg, A_IΓg, A_ΓΓ, b_Id, b_Γ = _global_blocks(fem, P)
+    G = api.GlobalSchur(ctx, A_IIg, A_IΓg, A_ΓΓ, None, reltol=1e-9)
+    G.use_level_solver(setup)
+    v = np.random.default_rng(1).standard_normal(n)
+    bI = np.concatenate(b_Id)
+    y = G * v
+    want = orc.apply_global_schur_operator(A_IIg, A_IΓg, A_ΓΓ, P.solvers) * v
+    assert np.abs(y - want).max() <= 1e-10 * np.abs(y).max()
+    b_schur = G.schur_rhs(bI, b_Γ)
+    want = fem.get_schur_rhs(b_Id, A_IIg, A_IΓg, b_Γ, solvers=P.solvers)
+    assert np.abs(b_schur - want).max() <= 1e-10 * np.abs(want).max()
+    u_I = G.interior_solutions(v, bI)
+    want = np.concatenate(fem.get_subdomain_solutions(v, A_IIg, A_IΓg, b_Id, P.solvers))
+    assert np.abs(u_I - want).max() <= 1e-10 * np.abs(want).max()
+    G.use_level_solver(None)                                            # back to the interior CG of the operator
+    y2 = G * v
+    assert np.abs(y2 - y).max() <= 1e-7 * np.abs(y).max()
+
+
+def test_a_plan_counts_the_matrix_free_operators_bound_to_it(pkg, ctx, fem, ragged):
+    """`mi_schur_matfree_interior_levels` counts the operator in the plan: `mi_schur_setup_destroy` (called on the library:
+    `SchurSetup.close` drops the code) is refused until every bound operator has unbound, bound another plan or gone;
+    `keep_levels(False)` is not refused for these users."""
+    api, P = pkg.api, ragged
+    L, BAD_ARG = ctx._L, pkg._lib.MI_ERR_BAD_ARG
+    sub = P.sub
+
+    def destroy(plan):
+        rc = L.mi_schur_setup_destroy(plan._h)
+        if rc == 0:
+            plan._h = None                                              # gone: nothing left for close()
+            return rc, ""
+        return rc, L.mi_last_error().decode()
+
+    A, B, C_ = (api.SchurSetup(ctx, P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd) for _ in range(3))
+    A.keep_levels(True)
+    A.run()
+    f = np.random.default_rng(2).standard_normal(int(sum(A.n_Id)))
+    u = A.interior_solve(f)
+    Smf = api.MatrixFreeLocalSchurs(ctx, P.A_IIdd, P.A_IΓdd, P.A_ΓΓdd, sub.gather_idx, sub.node_Γ_cnt, None, reltol=1e-9)
+    G = api.GlobalSchur(ctx, *_global_blocks(fem, P)[:3], None, reltol=1e-9)
+    Smf.use_level_solver(A)
+    G.use_level_solver(A)
+    rc, msg = destroy(A)
+    assert rc == BAD_ARG and "2 live matrix-free Schur operator(s) solve with this plan; destroy them first" in msg, (rc, msg)
+    assert np.array_equal(A.interior_solve(f), u)                       # refused: the plan still solves
+    Smf.use_level_solver(None)
+    rc, msg = destroy(A)
+    assert rc == BAD_ARG and "1 live matrix-free Schur operator(s)" in msg, (rc, msg)
+    A.keep_levels(False)                                                # accepted with G bound; its next apply says what is missing
+    with pytest.raises(pkg._lib.MiError, match="level solves need"):
+        G * np.ones(sub.n_Γ)
+    G.close()
+    assert destroy(A) == (0, "")
+    # binding another plan releases the first
+    Smf.use_level_solver(B)
+    assert destroy(B)[0] == BAD_ARG
+    Smf.use_level_solver(C_)
+    assert destroy(B) == (0, "")
+    assert destroy(C_)[0] == BAD_ARG
+    Smf.close()
+    assert destroy(C_) == (0, "")

@@ -179,3 +179,12 @@ def test_every_ccall_matches_the_c_prototype():
                  "mi_schur_setup_keep_levels", "mi_schur_setup_interior_solve", "mi_schur_matfree_interior_levels",
                  "mi_ctx_peer_init", "mi_ctx_peer_export", "mi_ctx_peer_import", "mi_ctx_peer_ready", "mi_ctx_set_exchange"):
         assert need in seen, f"{need} is not bound by the shim"
+
+
+def test_use_level_solver_roots_the_plan_in_the_operator():
+    """A bound plan must outlive its operator (mi_schur_matfree_interior_levels): `use_level_solver!` stores it in `keep`."""
+    m = re.search(r"^function use_level_solver!\(S::MiOperator, p::SchurSetup\)\n(.*?)^end", _src(), flags=re.M | re.S)
+    assert m, "use_level_solver!(S::MiOperator, p::SchurSetup) is not a function block"
+    body = _strip_comments_and_docstrings(m.group(1))
+    assert re.search(r"^\s*S\.keep\s*=\s*\(S\.keep,\s*p\)\s*$", body, flags=re.M), "the plan is not stored in S.keep"
+    assert body.index("mi_schur_matfree_interior_levels") < body.index("S.keep")     # rooted once the library has bound it
