@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""The flows of Example12_Quantization.jl, Example14_QuantizationAndShepardLocalInterpolation.jl and
+Example20_QuantizedPreconditioner.jl in one driver, at small default sizes, on the MI355X drop-in:
+
+    X, centroids, ... = get_quantizer(ns, P, Λ; distance)              (Example12_Quantization_Functions.jl:29-59)
+                                                                        -> api.get_quantizer: k-means++ and Lloyd on the device
+    Π = get_centroidal_preconds(centroids, Λ, Ψ)                       (:85-113) -> api.get_centroidal_preconds: per centroid,
+                                                                        KLField.coefficient, assembly, AMGPreconditioner.set_values
+    per fresh realization ξ: p = find_precond(ξ, centroids)            (Example20_…_Functions.jl:39-54) -> api.find_precond
+                             pcg(A, b, 0, Π[p])                        (Example12_…_Functions.jl:147-160)
+    --interpolate k:         pcg(A, b, 0, InterpolatingPreconditioner(shepard coefficients of the k nearest, their Π))
+                                                                        (Example14_…_Functions.jl:73-113, 174-206)
+
+The iteration counts are printed beside those of the constant preconditioner of ξ = 0 (Example06's Π_amg_0).
+
+    python examples/example12_quantization.py [--N 60] [--ns 2000] [--P 8] [--nreals 5] [--distance L2-full] [--interpolate 4]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import __graft_entry__ as graft  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--N", type=int, default=60, help="nodes per side")
+    ap.add_argument("--m-side", type=int, default=4, help="fem.synthetic_kl: m_side² modes")
+    ap.add_argument("--ns", type=int, default=2000, help="draws of ξ that are clustered")
+    ap.add_argument("--P", type=int, default=8, help="centroids")
+    ap.add_argument("--nreals", type=int, default=5, help="fresh realizations that are solved")
+    ap.add_argument("--distance", default="L2-full", choices=["L2", "L2-full", "L2-10%", "cdf", "cdf-full"])
+    ap.add_argument("--interpolate", type=int, default=0, help="k > 0: Shepard combination of the k nearest centroids' preconditioners")
+    ap.add_argument("--seed", type=int, default=987654321)
+    args = ap.parse_args()
+    pkg = graft.load_package()
+    fem, api = pkg.fem, pkg.api
+    mesh = fem.get_mesh(args.N)
+    dinds = fem.get_dirichlet_inds(mesh.points, mesh.point_marker)
+    f, uexact = (lambda x, y: -1.0 + 0 * x), (lambda x, y: 0.734 + 0 * x)
+    system = lambda a: fem.do_isotropic_elliptic_assembly(mesh.cells, mesh.points, dinds, mesh.point_marker, a, f, uexact)
+    kl = fem.synthetic_kl(mesh.points, m_side=args.m_side)
+    rng = np.random.default_rng(args.seed)
+    ctx = api.Context(int(os.environ.get("LOCAL_RANK", "0")))
+    field = api.KLField(ctx, kl.Λ, kl.Ψ)
+
+    t = time.perf_counter()
+    X, centroids, assignments, costs = api.get_quantizer(ctx, args.ns, args.P, kl.Λ, args.distance, rng=rng)
+    sizes = np.bincount(np.asarray(assignments), minlength=args.P)
+    print(f"quantizer: {args.ns} draws of {kl.Λ.size} coordinates into P = {args.P} cells ({args.distance}) in {time.perf_counter() - t:.3f} s; "
+          f"cell sizes {sizes.tolist()}, distortion {float(np.sum(costs)) / args.ns:.4e}")
+
+    A_0, _ = system(np.ones(mesh.points.shape[1]))
+    t = time.perf_counter()
+    Π = api.get_centroidal_preconds(ctx, centroids, field, lambda a: system(a)[0], A_0)
+    print(f"{args.P} centroidal AMG preconditioners (n = {A_0.shape[0]}) in {time.perf_counter() - t:.2f} s")
+    Π_0 = api.AMGPreconditioner(ctx, A_0)
+
+    scaled_centroids = fem.scale_data(centroids, kl.Λ, args.distance)
+    rows = centroids.shape[0]
+    iters_0, iters_q = [], []
+    for ireal in range(1, args.nreals + 1):
+        ξ = rng.standard_normal(kl.Λ.size)
+        A, b = system(field.coefficient(ξ))
+        A_op = api.SparseMatrixCSC(ctx, A)
+        x0 = np.zeros(b.size)
+        η = fem.scale_data(ξ, kl.Λ, args.distance)
+        if args.interpolate > 0:
+            _, dist2, _ = api.vq_assign(ctx, η.reshape(-1, 1), scaled_centroids, want_assign=False, want_objv=False)
+            d2 = fem.vq_dist2(η[:, None], scaled_centroids)[0]
+            near = np.argsort(d2, kind="stable")[:min(args.interpolate, args.P)]
+            full = np.zeros((kl.Λ.size, near.size))
+            full[:rows] = centroids[:, near]
+            coef = fem.shepard_coefficients(ξ, full, kl.Λ)
+            M = api.InterpolatingPreconditioner(ctx, coef, [Π[p] for p in near])
+            what = f"Shepard combination of centroids {near.tolist()} (nearest at squared distance {float(dist2[0]):.3e})"
+        else:
+            p = api.find_precond(ctx, η, scaled_centroids)
+            M = Π[p]
+            what = f"centroid {p}"
+        u, it_q, _ = api.pcg(A_op, b, x0, M)
+        _, it_0, _ = api.pcg(A_op, b, x0, Π_0)
+        iters_q.append(int(it_q)); iters_0.append(int(it_0))
+        print(f"realization {ireal}: {what}: pcg it = {it_q} (ξ = 0 preconditioner: {it_0}), |b - A u| / |b| = "
+              f"{np.linalg.norm(b - A @ u) / np.linalg.norm(b):.3e}")
+        if args.interpolate > 0:
+            M.close()
+        A_op.close()
+    print(f"iters_quantized = {iters_q}\niters_xi_0 = {iters_0}")
+
+
+if __name__ == "__main__":
+    main()

@@ -735,6 +735,68 @@ int mi_kl_field_tiling(int64_t n, int64_t m, int64_t nreal, int64_t *row_tile, i
 int mi_kl_field_stats(mi_kl_field_t field, int64_t *bytes_kept, int64_t *bytes_per_set);
 int mi_kl_field_destroy(mi_kl_field_t field);
 
+/* ---------------------------------------------------------------- vector quantization of ξ and the operators it selects
+ * The reference's quantization studies (Examples 12-14, 18, 20) cluster draws of ξ into a Voronoi quantizer with
+ * `kmeans(X, P, tol=1e-8, maxiter=1_000)` (Clustering.jl; Example20_QuantizedPreconditioner_Functions.jl:56-73 = "Ex20F",
+ * Example12_Quantization_Functions.jl:29-59 = "Ex12F", Example13_CLVQ_Functions.jl:129-159 = "Ex13F"), build one constant
+ * preconditioner per centroid and solve every realization with the nearest one (`find_precond`, Ex20F:39-54; the loop of
+ * test_solver_with_centroidal_preconds, Ex12F:147-155) or with a Shepard combination of a few
+ * (Example14_QuantizationAndShepardLocalInterpolation_Functions.jl:73-113, 174-206 = "Ex14F"). Kernels: csrc/vq.hpp.
+ * X is d x ns (a sample per column, ldx >= d), C is d x P (a centroid per column, ldc >= d), column-major as Julia passes them;
+ * rows past d of a column are neither read nor written. Indices are 0-based int64_t. Array pointers (X, C, assign, dist2,
+ * counts, u, picked) follow the context's pointer mode; objv, iters and converged are HOST pointers. Every call returns when
+ * its outputs are complete (its workspace is its own). No float atomics, fixed orders: equal calls give equal bits.
+ *
+ * mi_vq_tiling — pure host function (no device, no context): points per workgroup, centroids staged at a time, coordinates per
+ *   LDS chunk, the number of centroid splits mi_vq_assign uses for these sizes, and the chunk of the ordered sums. Any output
+ *   pointer may be NULL.
+ * mi_vq_assign — for every column of X the nearest centroid and its squared distance: the scan of find_precond (Ex20F:44-52),
+ *   of get_distortion (Ex13F:53-69) and of clvq's competitive phase (Ex13F:77-85) for ns samples at once. dist2[s] carries the
+ *   bits of the reference's `(x .- c)' * (x .- c)` as a loop (t = x_k - c_k; acc = acc + t * t; k ascending from +0); the winner
+ *   is the smallest dist2, among equals the lowest p (the strict `<` scan, started at centroid 0 as the reference starts it: a
+ *   NaN distance to centroid 0 stays, a NaN distance to another centroid never wins). objv = Σ_s dist2[s] in the chunked order:
+ *   sum_chunk consecutive samples ascending from +0, then the chunk totals ascending (get_distortion's w2 is objv / ns). assign,
+ *   dist2 and objv may each be NULL. P > ns is allowed.
+ * mi_vq_update — Lloyd's centre update for the assignments `assign`: counts[p] members; C[:, p] = (Σ X[:, s] over the members
+ *   in ascending s, from +0) / counts[p], a true division — the bits of `for s: sum[:, a[s]] += X[:, s]`. A cluster without a
+ *   member keeps its centre bit for bit and has count 0 (Clustering.jl repicks such a centre at random: a deviation).
+ * mi_vq_seed — k-means++ (Clustering.jl's default `init`) on P uniforms u[j] in [0, 1) drawn by the caller: centre 0 is sample
+ *   floor(u[0] ns); for j >= 1, mind[s] = min(mind[s], dist2(x_s, c_{j-1})), prefix(s) = (ascending sum of the totals of the
+ *   earlier chunks) + (ascending sum within the chunk of s up to and including s), total = prefix(ns - 1), and the pick is the
+ *   smallest s with prefix(s) > u[j] total (where rounding leaves none: the smallest s with prefix(s) >= total). picked (P
+ *   sample indices) and C (the P centres) are written. total == 0 — fewer distinct points than centres — is MI_ERR_BAD_ARG.
+ * mi_vq_kmeans — Lloyd's algorithm from the initial centres in C:
+ *     a, c = assign(X, C); objv = Σc; t = 0; converged = false
+ *     while !converged && t < maxiter:
+ *         t += 1; C = update(X, a, C); a, c = assign(X, C); prev = objv; objv = Σc; converged = |objv - prev| < tol
+ *   with one 8-byte readback per iteration. assign, counts, dist2 (arrays, may be NULL) and objv, iters, converged (host, may be
+ *   NULL) describe the final state. A non-finite objective after the first assignment is MI_ERR_BAD_ARG and C is untouched.
+ * mi_op_combine — z = Σ_i coef[i] (ops[i] applied to r), i ascending: `InterpolatingPreconditioner` / apply_local_interpolation
+ *   (Ex14F:73-97; the coefficients of shepard_interpolating_precond, Ex14F:174-206). 1 <= k <= 16 operators of this context and
+ *   of one size; coef: k finite HOST numbers. The children stay the caller's and must outlive the combination (destroying the
+ *   combination leaves them usable). apply runs child i into the i-th temporary, then one kernel forms z = z + coef[i] * t_i
+ *   from z = +0 (product, then sum); it honours the solvers' `done` word, allocates nothing, and is captured into the solve
+ *   graphs of mi_pcg, mi_defpcg and the eigCG family iff every child can be.
+ * mi_op_combine_set_coefficients — new coefficients (k finite HOST numbers) into the same device array: a captured graph keeps
+ *   working.
+ * MI_ERR_BAD_ARG with a mi_last_error() text, nothing written: d, ns or P < 1; ns or P >= 2^31; P > ns in mi_vq_kmeans and
+ *   mi_vq_seed; a leading dimension below d; a NULL required pointer; an assignment outside [0, P) (mi_vq_update); a negative
+ *   or non-finite tol, maxiter < 0; a context that is one rank of several; k outside [1, 16], operators of different sizes or
+ *   contexts, a coefficient that is not finite. */
+int mi_vq_tiling(int64_t d, int64_t ns, int64_t P, int64_t *point_tile, int64_t *cent_tile, int64_t *k_chunk,
+                 int64_t *cent_splits, int64_t *sum_chunk);
+int mi_vq_assign(mi_ctx_t ctx, int64_t d, int64_t ns, const double *X, int64_t ldx, int64_t P, const double *C, int64_t ldc,
+                 int64_t *assign /*NULL ok*/, double *dist2 /*NULL ok*/, double *objv /*NULL ok; host*/);
+int mi_vq_update(mi_ctx_t ctx, int64_t d, int64_t ns, const double *X, int64_t ldx, int64_t P, const int64_t *assign, double *C,
+                 int64_t ldc, int64_t *counts);
+int mi_vq_seed(mi_ctx_t ctx, int64_t d, int64_t ns, const double *X, int64_t ldx, int64_t P, const double *u, int64_t *picked,
+               double *C, int64_t ldc);
+int mi_vq_kmeans(mi_ctx_t ctx, int64_t d, int64_t ns, const double *X, int64_t ldx, int64_t P, double *C /*in: initial, out: final*/,
+                 int64_t ldc, double tol, int64_t maxiter, int64_t *assign, int64_t *counts, double *dist2, double *objv,
+                 int64_t *iters, int *converged);
+int mi_op_combine(mi_ctx_t ctx, int64_t k, const mi_op_t *ops, const double *coef, mi_op_t *op);
+int mi_op_combine_set_coefficients(mi_op_t op, const double *coef);
+
 /* ---------------------------------------------------------------- timing on the context's stream */
 int mi_event_create(mi_event_t *ev);
 int mi_event_record(mi_ctx_t ctx, mi_event_t ev);

@@ -143,6 +143,13 @@ SIGNATURES = {
     "mi_kl_field_tiling": [i64, i64, i64, i64p, i64p, i64p, i64p],
     "mi_kl_field_stats": [vp, i64p, i64p],
     "mi_kl_field_destroy": [vp],
+    "mi_vq_tiling": [i64, i64, i64, i64p, i64p, i64p, i64p, i64p],
+    "mi_vq_assign": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, f64p],
+    "mi_vq_update": [vp, i64, i64, vp, i64, i64, vp, vp, i64, vp],
+    "mi_vq_seed": [vp, i64, i64, vp, i64, i64, vp, vp, vp, i64],
+    "mi_vq_kmeans": [vp, i64, i64, vp, i64, i64, vp, i64, C.c_double, i64, vp, vp, vp, f64p, i64p, C.POINTER(C.c_int)],
+    "mi_op_combine": [vp, i64, C.POINTER(vp), f64p, C.POINTER(vp)],
+    "mi_op_combine_set_coefficients": [vp, f64p],
     "mi_event_create": [C.POINTER(vp)],
     "mi_event_record": [vp, vp],
     "mi_event_elapsed_ms": [vp, vp, f64p],

@@ -1858,3 +1858,237 @@ class HybridSampler(McmcSampler):
         self.ξ = np.concatenate([self.χ, tail])
         self._field()
         return cnt
+
+
+# ------------------------------------------------------------------ quantization of ξ and the operators it selects
+# Examples 12-14, 18, 20 (include/mi355schur.h "vector quantization"; kernels in csrc/vq.hpp; host mirror with the same bits in
+# fem.py). Matrices are d x ns / d x P with a sample / a centroid per column; numpy in gives numpy out, torch CUDA tensors in
+# give torch CUDA tensors out. A numpy view `A[:d, :]` of a Fortran-ordered array, or a torch view `B[:, :d].t()` of a
+# contiguous (ns, ld) tensor, is passed with its leading dimension and without a copy: the padding rows are not touched.
+def vq_tiling(d: int, ns: int, P: int):
+    """`mi_vq_tiling` -> (point_tile, cent_tile, k_chunk, cent_splits, sum_chunk); a pure host function, no device needed."""
+    out = [i64() for _ in range(5)]
+    check(_lib.load().mi_vq_tiling(i64(d), i64(ns), i64(P), *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+def _vq_mat(M, writable: bool = False):
+    """(keepalive, void*, rows, cols, ld) of a column-major fp64 matrix; a vector is one column."""
+    if _is_torch(M):
+        import torch
+        if M.dtype != torch.float64 or not M.is_cuda:
+            raise TypeError("device matrices must be float64 CUDA tensors")
+        if M.dim() == 1:
+            M = M.reshape(-1, 1)
+        r, c = M.shape
+        if not ((r == 1 or M.stride(0) == 1) and (c == 1 or M.stride(1) >= r)):
+            if writable:
+                raise ValueError("an output matrix must be column-major (stride 1 along its rows)")
+            M = M.t().contiguous().t()
+        return M, vp(M.data_ptr()), r, c, (M.stride(1) if c > 1 else r)
+    A = np.asarray(M) if writable else np.asarray(M, dtype=np.float64)
+    if A.ndim == 1:
+        A = A.reshape(-1, 1)
+    r, c = A.shape
+    ok = (A.dtype == np.float64 and (r == 1 or A.strides[0] == 8) and (c == 1 or (A.strides[1] >= 8 * r and A.strides[1] % 8 == 0))
+          and (A.flags.writeable or not writable))
+    if not ok:
+        if writable:
+            raise ValueError("an output matrix must be a writeable column-major float64 array")
+        A = np.asfortranarray(A, dtype=np.float64)
+    return A, vp(A.ctypes.data), r, c, (A.strides[1] // 8 if c > 1 else r)
+
+
+def _vq_out(like, n: int, dtype):
+    if _is_torch(like):
+        import torch
+        t = torch.empty(n, dtype=torch.int64 if dtype == np.int64 else torch.float64, device=like.device)
+        return t, vp(t.data_ptr())
+    a = np.empty(n, dtype=dtype)
+    return a, vp(a.ctypes.data)
+
+
+def vq_assign(ctx: Context, X, C_, want_assign: bool = True, want_dist2: bool = True, want_objv: bool = True):
+    """`mi_vq_assign`: (assign, dist2, objv) — the nearest centroid (0-based) and its squared distance for every column of X,
+    and Σ dist2 in the chunked order; an output that is not wanted is None."""
+    ctx._mode_for(X, C_)
+    kx, px, d, ns, ldx = _vq_mat(X)
+    kc, pc, dc, P, ldc = _vq_mat(C_)
+    if dc != d:
+        raise ValueError(f"X has {d} rows, C has {dc}")
+    a, pa = _vq_out(kx, ns, np.int64) if want_assign else (None, None)
+    c, pd = _vq_out(kx, ns, np.float64) if want_dist2 else (None, None)
+    objv = C.c_double(0.0)
+    ctx._order((kx, kc, a, c), after=False)
+    check(ctx._L.mi_vq_assign(ctx._h, i64(d), i64(ns), px, i64(ldx), i64(P), pc, i64(ldc), pa, pd, C.byref(objv) if want_objv else None))
+    ctx._order((kx, kc, a, c), after=True)
+    return a, c, (float(objv.value) if want_objv else None)
+
+
+def vq_update(ctx: Context, X, assign, C_):
+    """`mi_vq_update`: C_ (d x P, column-major, writeable) is updated in place for the assignments; returns (C_, counts)."""
+    ctx._mode_for(X, assign, C_)
+    kx, px, d, ns, ldx = _vq_mat(X)
+    kc, pc, dc, P, ldc = _vq_mat(C_, writable=True)
+    if _is_torch(assign):
+        ka = assign.contiguous()
+        pa = vp(ka.data_ptr())
+    else:
+        ka = _i64(assign)
+        pa = vp(ka.ctypes.data)
+    n, pn = _vq_out(kx, P, np.int64)
+    ctx._order((kx, kc, ka, n), after=False)
+    check(ctx._L.mi_vq_update(ctx._h, i64(d), i64(ns), px, i64(ldx), i64(P), pa, pc, i64(ldc), pn))
+    ctx._order((kx, kc, ka, n), after=True)
+    return kc, n
+
+
+def kmpp_seed(ctx: Context, X, P: int, u):
+    """`mi_vq_seed`: k-means++ on P uniforms u[j] in [0, 1) -> (picked, C); MiError(MI_ERR_BAD_ARG) with fewer distinct points
+    than centres."""
+    ctx._mode_for(X, u)
+    kx, px, d, ns, ldx = _vq_mat(X)
+    ku, pu, nu, _, _ = _vq_mat(u)
+    if nu < P:
+        raise ValueError(f"{nu} uniforms for {P} centres")
+    picked, pp = _vq_out(kx, P, np.int64)
+    if _is_torch(kx):
+        import torch
+        Cn = torch.empty((P, d), dtype=torch.float64, device=kx.device).t()
+        pc = vp(Cn.data_ptr())
+    else:
+        Cn = np.empty((d, P), order="F")
+        pc = vp(Cn.ctypes.data)
+    ctx._order((kx, ku, picked, Cn), after=False)
+    check(ctx._L.mi_vq_seed(ctx._h, i64(d), i64(ns), px, i64(ldx), i64(P), pu, pp, pc, i64(d)))
+    ctx._order((kx, ku, picked, Cn), after=True)
+    return picked, Cn
+
+
+class KmeansResult:
+    """The fields of Clustering.jl's `KmeansResult` that the reference reads (`res.centers`, `res.assignments`, `res.costs`:
+    Ex12F:58), with 0-based assignments."""
+
+    def __init__(self, centers, assignments, costs, counts, totalcost, iterations, converged):
+        self.centers, self.assignments, self.costs, self.counts = centers, assignments, costs, counts
+        self.totalcost, self.iterations, self.converged = totalcost, iterations, converged
+
+
+def kmeans(ctx: Context, X, P: int, init="kmpp", rng=None, tol: float = 1e-8, maxiter: int = 1000) -> KmeansResult:
+    """`kmeans(X, P, tol=1e-8, maxiter=1_000)` (Ex20F:63; Ex12F:40; Ex13F:143) on the device (`mi_vq_kmeans`). `init`: "kmpp"
+    (k-means++ on P uniforms drawn from `rng`, a numpy Generator; Clustering.jl's default), a d x P matrix of centres, or P
+    sample indices. An empty cluster keeps its centre (Clustering.jl repicks it at random)."""
+    torch_in = _is_torch(X)
+    kx, px, d, ns, ldx = _vq_mat(X)
+    if isinstance(init, str):
+        if init != "kmpp":
+            raise ValueError(f"unknown init {init!r}")
+        u = (rng if rng is not None else np.random.default_rng()).random(P)
+        if torch_in:
+            import torch
+            u = torch.as_tensor(u, device=kx.device)
+        _, C0 = kmpp_seed(ctx, kx, P, u)
+    else:
+        init = init if _is_torch(init) else np.asarray(init)
+        if init.ndim == 1:
+            C0 = kx[:, init] if not torch_in else kx[:, init.long() if _is_torch(init) else list(init)]
+        else:
+            C0 = init
+    if torch_in:
+        import torch
+        Cn = torch.as_tensor(C0, dtype=torch.float64, device=kx.device).t().contiguous().clone().t()
+    else:
+        Cn = np.array(C0, dtype=np.float64, order="F")
+    if tuple(Cn.shape) != (d, P):
+        raise ValueError(f"initial centres are {tuple(Cn.shape)}, expected {(d, P)}")
+    ctx._mode_for(kx, Cn)
+    kc, pc, _, _, ldc = _vq_mat(Cn, writable=True)
+    a, pa = _vq_out(kx, ns, np.int64)
+    n, pn = _vq_out(kx, P, np.int64)
+    c, pd = _vq_out(kx, ns, np.float64)
+    objv, it, conv = C.c_double(0.0), i64(0), C.c_int(0)
+    ctx._order((kx, kc, a, n, c), after=False)
+    check(ctx._L.mi_vq_kmeans(ctx._h, i64(d), i64(ns), px, i64(ldx), i64(P), pc, i64(ldc), C.c_double(tol), i64(maxiter), pa, pn, pd,
+                              C.byref(objv), C.byref(it), C.byref(conv)))
+    ctx._order((kx, kc, a, n, c), after=True)
+    return KmeansResult(kc, a, c, n, float(objv.value), int(it.value), bool(conv.value))
+
+
+def find_precond(ctx: Context, x, hXt) -> int:
+    """`find_precond(x, hXt)` (Ex20F:39-54): the nearest centroid of x, 0-based; the centroids (nKL_trunc x P) are zero-padded
+    to length(x) on the host, as the reference does. Host arrays."""
+    x, hXt = _f64(x).ravel(), np.asarray(hXt, dtype=np.float64)
+    if hXt.ndim != 2 or hXt.shape[0] > x.size:
+        raise ValueError(f"hXt is {hXt.shape} for an x of {x.size} entries")
+    padded = np.zeros((x.size, hXt.shape[1]), order="F")
+    padded[:hXt.shape[0]] = hXt
+    return int(vq_assign(ctx, x.reshape(-1, 1), padded, want_dist2=False, want_objv=False)[0][0])
+
+
+def get_distortion(ctx: Context, X, hXt) -> float:
+    """`get_distortion(X, hXt)` (Ex13F:53-69): objv / ns."""
+    objv = vq_assign(ctx, X, hXt, want_assign=False, want_dist2=False)[2]
+    return objv / int(X.shape[1])
+
+
+def get_quantizer(ctx: Context, n: int, P: int, Λ, distance: str = "L2-full", rng=None):
+    """`get_quantizer(n, P, Λ; distance)` (Ex12F:29-59): n draws of ξ ~ N(0, I), k-means on the data scaled for `distance`
+    ("L2-full" / "L2", "L2-10%", "cdf-full", "cdf": fem.scale_data), the centres scaled back. Returns (X, centers, assignments,
+    costs) with X the unscaled draws. The reference seeds Julia's generator; here `rng` (a numpy Generator) draws both the
+    samples and the k-means++ uniforms."""
+    from . import fem
+    rng = rng if rng is not None else np.random.default_rng()
+    Λ = _f64(Λ)
+    X = rng.standard_normal((Λ.size, n))
+    res = kmeans(ctx, fem.scale_data(X, Λ, distance), P, init="kmpp", rng=rng)
+    return X, fem.unscale_centers(res.centers, Λ, distance), res.assignments, res.costs
+
+
+class InterpolatingPreconditioner(Operator):
+    """`InterpolatingPreconditioner(coefficients, Πs)` (Ex14F:73-113): `Π \\ r` = Σ_i c_i (Πs[i] \\ r), on the device
+    (`mi_op_combine`), usable as the `M` of pcg and its relatives. 1 to 16 operators of one context and one size; they must
+    outlive this object (it keeps references to them). A non-finite coefficient — what `fem.shepard_coefficients` gives at
+    zero distance — raises ValueError."""
+
+    def __init__(self, ctx: Context, coefficients, Πs: Sequence[Operator]):
+        coef = self._coef(coefficients)
+        Πs = list(Πs)
+        if coef.size != len(Πs):
+            raise ValueError(f"{coef.size} coefficients for {len(Πs)} operators")
+        hs = (vp * max(len(Πs), 1))(*[p._h for p in Πs])
+        h = vp()
+        check(ctx._L.mi_op_combine(ctx._h, i64(len(Πs)), hs, coef.ctypes.data_as(f64p), C.byref(h)))
+        super().__init__(ctx, h, keep=tuple(Πs))
+        self.coefficients, self.Πs = coef, Πs
+
+    @staticmethod
+    def _coef(coefficients):
+        coef = _f64(coefficients).ravel()
+        if not np.all(np.isfinite(coef)):
+            raise ValueError("a coefficient is not finite (Shepard weights at zero distance?)")
+        return coef
+
+    def set_coefficients(self, coefficients) -> None:
+        """New coefficients into the same device array (`mi_op_combine_set_coefficients`); solve graphs stay valid."""
+        coef = self._coef(coefficients)
+        if coef.size != len(self.Πs):
+            raise ValueError(f"{coef.size} coefficients for {len(self.Πs)} operators")
+        check(self.ctx._L.mi_op_combine_set_coefficients(self._h, coef.ctypes.data_as(f64p)))
+        self.coefficients = coef
+
+
+def get_centroidal_preconds(ctx: Context, centroids, field: KLField, assemble: Callable, A0, **amg_kw):
+    """`get_centroidal_preconds(centroids, Λ, Ψ)` (Ex12F:85-113): one constant AMG preconditioner per centroid. For column p,
+    a = field.coefficient(ξ_p) (`set!` + `exp.(g)`; a centroid with fewer rows than the field has modes is zero-padded, as
+    Ex20F:100-101 does), A_p = assemble(a) — a scipy sparse matrix on the pattern of A0, or its CSR values — and
+    `AMGPreconditioner(ctx, A0, device_setup=True)` + `.set_values(A_p)`: the aggregates are those of A0 for every centroid."""
+    centroids = np.asarray(centroids, dtype=np.float64)
+    Π = []
+    for p in range(centroids.shape[1]):
+        ξ = np.zeros(field.m)
+        ξ[:centroids.shape[0]] = centroids[:, p]
+        # the host set-up (the aggregates) runs once, for the first one
+        M = AMGPreconditioner(ctx, A0, device_setup=True, **(amg_kw if not Π else dict(aggregates=Π[0].aggregates)))
+        M.set_values(assemble(field.coefficient(ξ)))
+        Π.append(M)
+    return Π

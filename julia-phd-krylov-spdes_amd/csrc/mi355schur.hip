@@ -17,6 +17,7 @@
 #include "interior_amg.hpp"
 #include "kl.hpp"
 #include "kl_field.hpp"
+#include "vq.hpp"
 
 namespace mi {
 
@@ -1298,6 +1299,184 @@ int mi_kl_field_destroy(mi_kl_field_t field) {
     field->ctx->use();
     (void)hipStreamSynchronize(field->ctx->stream);
     delete field;
+    return MI_OK;
+  });
+}
+
+// ---------------------------------------------------------------- vector quantization of ξ (vq.hpp)
+int mi_vq_tiling(int64_t d, int64_t ns, int64_t P, int64_t *point_tile, int64_t *cent_tile, int64_t *k_chunk, int64_t *cent_splits,
+                 int64_t *sum_chunk) {
+  if (d < 1 || ns < 1 || P < 1 || ns >= VQ_MAX_N || P >= VQ_MAX_N)
+    return fail(MI_ERR_BAD_ARG, "mi_vq_tiling: d = %lld, ns = %lld, P = %lld: each at least 1, ns and P below 2^31", (long long)d, (long long)ns, (long long)P);
+  if (point_tile) *point_tile = VQ_POINT_TILE;
+  if (cent_tile) *cent_tile = VQ_CENT_TILE;
+  if (k_chunk) *k_chunk = VQ_K_CHUNK;
+  if (cent_splits) *cent_splits = vq_tiling(d, ns, P).splits;
+  if (sum_chunk) *sum_chunk = VQ_SUM_CHUNK;
+  return MI_OK;
+}
+
+// the checks every mi_vq_* call shares; MI_OK or the refusal (mi_last_error is set)
+static int vq_check(const char *me, mi_ctx_t ctx, int64_t d, int64_t ns, const void *X, int64_t ldx, int64_t P, const void *C, int64_t ldc,
+                    bool p_le_ns) {
+  if (!ctx || !X || !C) return fail(MI_ERR_BAD_ARG, "%s: ctx, X or C is NULL", me);
+  if (d < 1 || ns < 1 || P < 1 || ns >= VQ_MAX_N || P >= VQ_MAX_N || d >= VQ_MAX_N)
+    return fail(MI_ERR_BAD_ARG, "%s: d = %lld, ns = %lld, P = %lld: each at least 1 and below 2^31", me, (long long)d, (long long)ns, (long long)P);
+  if (p_le_ns && P > ns) return fail(MI_ERR_BAD_ARG, "%s: P = %lld centres for ns = %lld samples", me, (long long)P, (long long)ns);
+  if (ldx < d || ldc < d) return fail(MI_ERR_BAD_ARG, "%s: ldx = %lld or ldc = %lld < d = %lld", me, (long long)ldx, (long long)ldc, (long long)d);
+  if (ctx->has_comm()) return fail(MI_ERR_BAD_ARG, "%s: the context is one rank of several; sharded quantizers are not provided", me);
+  return MI_OK;
+}
+
+int mi_vq_assign(mi_ctx_t ctx, int64_t d, int64_t ns, const double *X, int64_t ldx, int64_t P, const double *C, int64_t ldc, int64_t *assign,
+                 double *dist2, double *objv) {
+  const char *me = "mi_vq_assign";
+  if (int rc = vq_check(me, ctx, d, ns, X, ldx, P, C, ldc, false)) return rc;
+  return guarded([&]() -> int {
+    ctx->use();
+    hipStream_t s = ctx->stream;
+    VqArg<const double> x(ctx, X, (size_t)d, (size_t)ns, ldx, true), c(ctx, C, (size_t)d, (size_t)P, ldc, true);
+    VqArg<long long> a(ctx, (long long *)assign, (size_t)ns, 1, ns, false);
+    VqArg<double> d2(ctx, dist2, (size_t)ns, 1, ns, false);
+    DevBuf<double> own;
+    double *dd = d2.dev;
+    if (!dd && objv) { own.alloc((size_t)ns); dd = own.p; }
+    VqWork w(d, ns, P);
+    w.assign(s, x.dev, x.ld, P, c.dev, c.ld, a.dev, dd, nullptr);
+    if (objv) w.ordered_sum(s, dd, nullptr, nullptr);
+    a.finish(); d2.finish();
+    const double total = objv ? w.read_total(s) : 0.0;
+    MI_HIP(hipStreamSynchronize(s));
+    if (objv) *objv = total;
+    return MI_OK;
+  });
+}
+
+int mi_vq_update(mi_ctx_t ctx, int64_t d, int64_t ns, const double *X, int64_t ldx, int64_t P, const int64_t *assign, double *C, int64_t ldc,
+                 int64_t *counts) {
+  const char *me = "mi_vq_update";
+  if (int rc = vq_check(me, ctx, d, ns, X, ldx, P, C, ldc, false)) return rc;
+  if (!assign || !counts) return fail(MI_ERR_BAD_ARG, "%s: assign or counts is NULL", me);
+  return guarded([&]() -> int {
+    ctx->use();
+    hipStream_t s = ctx->stream;
+    VqArg<const double> x(ctx, X, (size_t)d, (size_t)ns, ldx, true);
+    VqArg<const long long> a(ctx, (const long long *)assign, (size_t)ns, 1, ns, true);
+    if (ctx->ptr_mode != MI_PTR_DEVICE)   // refused before anything is written
+      for (int64_t i = 0; i < ns; ++i)
+        if (assign[i] < 0 || assign[i] >= P) return fail(MI_ERR_BAD_ARG, "%s: assign[%lld] = %lld outside [0, %lld)", me, (long long)i, (long long)assign[i], (long long)P);
+    VqArg<double> c(ctx, C, (size_t)d, (size_t)P, ldc, true);
+    VqArg<long long> n(ctx, (long long *)counts, (size_t)P, 1, P, false);
+    VqWork w(d, ns, P);
+    if (!w.update(s, x.dev, x.ld, a.dev, c.dev, c.ld, n.dev, true)) return fail(MI_ERR_BAD_ARG, "%s: an assignment outside [0, %lld)", me, (long long)P);
+    c.finish(); n.finish();
+    MI_HIP(hipStreamSynchronize(s));
+    return MI_OK;
+  });
+}
+
+int mi_vq_seed(mi_ctx_t ctx, int64_t d, int64_t ns, const double *X, int64_t ldx, int64_t P, const double *u, int64_t *picked, double *C,
+               int64_t ldc) {
+  const char *me = "mi_vq_seed";
+  if (int rc = vq_check(me, ctx, d, ns, X, ldx, P, C, ldc, true)) return rc;
+  if (!u || !picked) return fail(MI_ERR_BAD_ARG, "%s: u or picked is NULL", me);
+  return guarded([&]() -> int {
+    ctx->use();
+    hipStream_t s = ctx->stream;
+    VqArg<const double> x(ctx, X, (size_t)d, (size_t)ns, ldx, true), uu(ctx, u, (size_t)P, 1, P, true);
+    // the centres are built in a buffer of the call's own, so that a refusal leaves C as it was
+    DevBuf<double> cs((size_t)d * (size_t)P);
+    DevBuf<long long> ps((size_t)P);
+    VqWork w(d, ns, P);
+    w.seed(s, x.dev, x.ld, uu.dev, ps.p, cs.p, d);
+    if (w.read_err(s)) return fail(MI_ERR_BAD_ARG, "%s: the distances to the centres chosen so far sum to 0 (or are not finite): fewer distinct points than centres", me);
+    const hipMemcpyKind kind = ctx->ptr_mode == MI_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    MI_HIP(hipMemcpy2DAsync(C, sizeof(double) * (size_t)ldc, cs.p, sizeof(double) * (size_t)d, sizeof(double) * (size_t)d, (size_t)P, kind, s));
+    MI_HIP(hipMemcpyAsync(picked, ps.p, sizeof(long long) * (size_t)P, kind, s));
+    MI_HIP(hipStreamSynchronize(s));
+    return MI_OK;
+  });
+}
+
+int mi_vq_kmeans(mi_ctx_t ctx, int64_t d, int64_t ns, const double *X, int64_t ldx, int64_t P, double *C, int64_t ldc, double tol,
+                 int64_t maxiter, int64_t *assign, int64_t *counts, double *dist2, double *objv, int64_t *iters, int *converged) {
+  const char *me = "mi_vq_kmeans";
+  if (int rc = vq_check(me, ctx, d, ns, X, ldx, P, C, ldc, true)) return rc;
+  if (!(tol >= 0.0) || !std::isfinite(tol) || maxiter < 0) return fail(MI_ERR_BAD_ARG, "%s: tol = %g, maxiter = %lld", me, tol, (long long)maxiter);
+  return guarded([&]() -> int {
+    ctx->use();
+    hipStream_t s = ctx->stream;
+    VqArg<const double> x(ctx, X, (size_t)d, (size_t)ns, ldx, true);
+    VqArg<double> c(ctx, C, (size_t)d, (size_t)P, ldc, true);
+    VqArg<long long> a(ctx, (long long *)assign, (size_t)ns, 1, ns, false), n(ctx, (long long *)counts, (size_t)P, 1, P, false);
+    VqArg<double> d2(ctx, dist2, (size_t)ns, 1, ns, false);
+    DevBuf<long long> own_a, own_n;
+    DevBuf<double> own_d;
+    long long *ad = a.dev, *nd = n.dev;
+    double *dd = d2.dev;
+    if (!ad) { own_a.alloc((size_t)ns); ad = own_a.p; }
+    if (!nd) { own_n.alloc((size_t)P); nd = own_n.p; }
+    if (!dd) { own_d.alloc((size_t)ns); dd = own_d.p; }
+    VqWork w(d, ns, P);
+    w.assign(s, x.dev, x.ld, P, c.dev, c.ld, ad, dd, nullptr);
+    w.ordered_sum(s, dd, nullptr, nullptr);
+    double obj = w.read_total(s);
+    if (!std::isfinite(obj)) return fail(MI_ERR_BAD_ARG, "%s: the objective after the first assignment is %g (X or C is not finite)", me, obj);
+    MI_HIP(hipMemsetAsync(nd, 0, (size_t)P * sizeof(long long), s));   // maxiter == 0: no update ever counts
+    int64_t t = 0;
+    bool conv = false;
+    while (!conv && t < maxiter) {
+      ++t;
+      w.update(s, x.dev, x.ld, ad, c.dev, c.ld, nd, false);
+      w.assign(s, x.dev, x.ld, P, c.dev, c.ld, ad, dd, nullptr);
+      w.ordered_sum(s, dd, nullptr, nullptr);
+      const double prev = obj;
+      obj = w.read_total(s);
+      conv = std::fabs(obj - prev) < tol;
+    }
+    c.finish(); a.finish(); n.finish(); d2.finish();
+    MI_HIP(hipStreamSynchronize(s));
+    if (objv) *objv = obj;
+    if (iters) *iters = t;
+    if (converged) *converged = conv ? 1 : 0;
+    return MI_OK;
+  });
+}
+
+// ---------------------------------------------------------------- z = Σ_i c_i (Π_i \ r) (vq.hpp)
+static CombineOp *as_combine(mi_op_t op) { return op && op->impl ? dynamic_cast<CombineOp *>(op->impl.get()) : nullptr; }
+static int combine_coef_check(const char *me, int64_t k, const double *coef) {
+  if (!coef) return fail(MI_ERR_BAD_ARG, "%s: coef is NULL", me);
+  for (int64_t i = 0; i < k; ++i)
+    if (!std::isfinite(coef[i])) return fail(MI_ERR_BAD_ARG, "%s: coef[%lld] = %g is not finite", me, (long long)i, coef[i]);
+  return MI_OK;
+}
+int mi_op_combine(mi_ctx_t ctx, int64_t k, const mi_op_t *ops, const double *coef, mi_op_t *op) {
+  const char *me = "mi_op_combine";
+  if (!ctx || !op) return fail(MI_ERR_BAD_ARG, "%s: ctx/op is NULL", me);
+  *op = nullptr;
+  if (k < 1 || k > 16) return fail(MI_ERR_BAD_ARG, "%s: k = %lld operators (1 <= k <= 16)", me, (long long)k);
+  if (!ops) return fail(MI_ERR_BAD_ARG, "%s: ops is NULL", me);
+  if (int rc = combine_coef_check(me, k, coef)) return rc;
+  std::vector<Operator *> kids;
+  for (int64_t i = 0; i < k; ++i) {
+    if (!ops[i] || !ops[i]->impl) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is NULL", me, (long long)i);
+    Operator *o = ops[i]->impl.get();
+    if (o->ctx != ctx) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] belongs to another context", me, (long long)i);
+    if (o->n != ops[0]->impl->n) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is of size %lld, ops[0] of size %lld", me, (long long)i, (long long)o->n, (long long)ops[0]->impl->n);
+    kids.push_back(o);
+  }
+  const int64_t n = kids[0]->n;
+  MI_NEW_OP(ctx, op, new CombineOp(ctx, n, kids, coef));
+}
+int mi_op_combine_set_coefficients(mi_op_t op, const double *coef) {
+  const char *me = "mi_op_combine_set_coefficients";
+  CombineOp *c = as_combine(op);
+  if (!c) return fail(MI_ERR_BAD_ARG, "%s: not a combined operator", me);
+  if (int rc = combine_coef_check(me, (int64_t)c->kids.size(), coef)) return rc;
+  return guarded([&]() -> int {
+    c->ctx->use();
+    c->set_coefficients(coef);
     return MI_OK;
   });
 }

@@ -1468,3 +1468,261 @@ def build_schur_problem(N: int, px: int, py: int, coeff: Coeff, f, uexact,
     prob.info["dom_slice"] = (lo, hi)
     prob.Sd, prob.ΠSd = Sd, Pi
     return prob
+
+
+# --------------------------------------------------------------------------------------
+# Quantization of ξ (Examples 12-14, 18, 20), host side, in the orders of the device kernels (csrc/vq.hpp): the results
+# below carry the bits of api.vq_assign / kmeans / ... . X is d x ns (a sample per column), C is d x P (a centroid per
+# column), indices are 0-based. "Ex12F" = Example12_Quantization_Functions.jl, "Ex13F" = Example13_CLVQ_Functions.jl,
+# "Ex14F" = Example14_QuantizationAndShepardLocalInterpolation_Functions.jl, "Ex20F" =
+# Example20_QuantizedPreconditioner_Functions.jl.
+# --------------------------------------------------------------------------------------
+VQ_SUM_CHUNK = 256          # samples per chunk of the ordered sums (mi_vq_tiling's sum_chunk)
+
+
+def vq_dist2(X, C):
+    """dist2[s, p] = (x_s .- c_p)' * (x_s .- c_p) as a loop: t = x_k - c_k, acc = acc + t * t, k ascending from +0."""
+    X, C = np.asarray(X, dtype=np.float64), np.asarray(C, dtype=np.float64)
+    acc = np.zeros((X.shape[1], C.shape[1]))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(X.shape[0]):
+            t = X[k, :, None] - C[k, None, :]
+            acc = acc + t * t
+    return acc
+
+
+def vq_scan(D):
+    """The reference's strict `<` scan over the columns of D (ns x P), started at column 0 (Ex20F:44-52): a NaN in column 0
+    stays, a NaN elsewhere never wins, among equals the lowest p wins."""
+    best, arg = D[:, 0].copy(), np.zeros(D.shape[0], dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        for p in range(1, D.shape[1]):
+            m = D[:, p] < best
+            best[m], arg[m] = D[m, p], p
+    return arg, best
+
+
+def vq_assign(X, C, block: int = 2048):
+    """Nearest centroid and its squared distance for every column of X -> (assign, dist2)."""
+    X, C = np.asarray(X, dtype=np.float64), np.asarray(C, dtype=np.float64)
+    ns = X.shape[1]
+    a, c = np.zeros(ns, dtype=np.int64), np.zeros(ns)
+    for s0 in range(0, ns, block):
+        a[s0:s0 + block], c[s0:s0 + block] = vq_scan(vq_dist2(X[:, s0:s0 + block], C))
+    return a, c
+
+
+def vq_chunk_sums(v, chunk: int = VQ_SUM_CHUNK):
+    """The ordered sums over samples: (excl, within, total). within[s] = ascending sum inside the chunk of s up to and
+    including s; excl[c] = ascending sum of the totals of the chunks before c; total = excl[-1] + (last chunk's total)."""
+    v = np.asarray(v, dtype=np.float64)
+    nch = (v.size + chunk - 1) // chunk
+    within, tot = np.empty(v.size), np.empty(nch)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for c in range(nch):
+            w = np.cumsum(v[c * chunk:(c + 1) * chunk])      # sequential: ((v0 + v1) + v2) + ...
+            within[c * chunk:c * chunk + w.size], tot[c] = w, w[-1]
+        excl = np.concatenate(([0.0], np.cumsum(tot)[:-1]))
+        total = excl[-1] + tot[-1]
+    return excl, within, float(total)
+
+
+def vq_objective(dist2, chunk: int = VQ_SUM_CHUNK) -> float:
+    """objv = Σ_s dist2[s] in the chunked order."""
+    return vq_chunk_sums(dist2, chunk)[2]
+
+
+def get_distortion(X, hXt) -> float:
+    """`get_distortion` (Ex13F:53-69): w2 = (Σ_s min_p dist2) / ns, the sum in the chunked order."""
+    return vq_objective(vq_assign(X, hXt)[1]) / np.asarray(X).shape[1]
+
+
+def vq_update(X, assign, C):
+    """Lloyd's centre update -> (C_new, counts): sum[:, a[s]] += X[:, s] for s ascending from +0, then a true division by the
+    count; a cluster without a member keeps its centre bit for bit (Clustering.jl would repick it at random)."""
+    X, C = np.asarray(X, dtype=np.float64), np.array(C, dtype=np.float64)
+    assign = np.asarray(assign, dtype=np.int64)
+    P = C.shape[1]
+    if assign.size and (assign.min() < 0 or assign.max() >= P):
+        raise ValueError("assignment outside [0, P)")
+    sums = np.zeros((P, X.shape[0]))
+    np.add.at(sums, assign, X.T)                             # unbuffered: one sample after the other, s ascending
+    counts = np.bincount(assign, minlength=P).astype(np.int64)
+    live = counts > 0
+    C[:, live] = (sums[live] / counts[live, None]).T
+    return C, counts
+
+
+def kmpp_seed(X, P: int, u, chunk: int = VQ_SUM_CHUNK):
+    """k-means++ on P uniforms u[j] in [0, 1) -> (picked, C). Centre 0 is sample floor(u[0] ns); then mind = min(mind,
+    dist2(·, c_{j-1})), prefix(s) = excl[chunk of s] + within[s], and the pick is the smallest s with prefix(s) > u[j] total
+    (where rounding leaves none: the smallest s with prefix(s) >= total). total == 0 raises ValueError."""
+    X, u = np.asarray(X, dtype=np.float64), np.asarray(u, dtype=np.float64)
+    d, ns = X.shape
+    if P > ns or u.size < P:
+        raise ValueError("P > ns, or fewer than P uniforms")
+    picked = np.zeros(P, dtype=np.int64)
+    f = np.floor(u[0] * float(ns))
+    picked[0] = int(min(f, ns - 1)) if f >= 0 else 0
+    mind = np.full(ns, np.inf)
+    for j in range(1, P):
+        dj = vq_dist2(X, X[:, picked[j - 1]][:, None])[:, 0]
+        mind = np.where(dj < mind, dj, mind)
+        excl, within, total = vq_chunk_sums(mind, chunk)
+        if not (total > 0.0) or not np.isfinite(total):
+            raise ValueError("the distances to the centres chosen so far sum to 0: fewer distinct points than centres")
+        prefix = np.repeat(excl, chunk)[:ns] + within
+        hit = np.nonzero(prefix > u[j] * total)[0]
+        if hit.size == 0:
+            hit = np.nonzero(prefix >= total)[0]
+        picked[j] = hit[0]
+    return picked, X[:, picked].copy()
+
+
+@dataclass
+class KmeansResult:
+    """The fields of Clustering.jl's KmeansResult the reference reads (0-based assignments)."""
+    centers: np.ndarray
+    assignments: np.ndarray
+    costs: np.ndarray
+    counts: np.ndarray
+    totalcost: float
+    iterations: int
+    converged: bool
+
+
+def kmeans(X, C0, tol: float = 1e-8, maxiter: int = 1000) -> KmeansResult:
+    """Lloyd's algorithm from the centres C0, the loop of mi_vq_kmeans: assign; then update, assign, and stop when the
+    objective changed by less than `tol` in absolute value (Clustering.jl's documented rule, restated) or after maxiter."""
+    X, C = np.asarray(X, dtype=np.float64), np.array(C0, dtype=np.float64)
+    a, c = vq_assign(X, C)
+    objv = vq_objective(c)
+    if not np.isfinite(objv):
+        raise ValueError("the objective after the first assignment is not finite")
+    counts = np.zeros(C.shape[1], dtype=np.int64)
+    t, converged = 0, False
+    while not converged and t < maxiter:
+        t += 1
+        C, counts = vq_update(X, a, C)
+        a, c = vq_assign(X, C)
+        prev, objv = objv, vq_objective(c)
+        converged = bool(abs(objv - prev) < tol)
+    return KmeansResult(C, a, c, counts, objv, t, converged)
+
+
+def find_precond(x, hXt) -> int:
+    """`find_precond` (Ex20F:39-54): the centroids are zero-padded from nKL_trunc to length(x); 0-based index."""
+    x, hXt = np.asarray(x, dtype=np.float64), np.asarray(hXt, dtype=np.float64)
+    padded = np.zeros((x.size, hXt.shape[1]))
+    padded[:hXt.shape[0]] = hXt
+    return int(vq_assign(x[:, None], padded)[0][0])
+
+
+def _vq_rows(Λ, distance: str) -> int:
+    """Rows the quantizer of this distance works on: all of them, or, for "L2-10%", up to the first α with
+    cumsum(Λ)[α] >= 0.1 (Ex12F:45)."""
+    Λ = np.asarray(Λ, dtype=np.float64)
+    if distance != "L2-10%":
+        return Λ.size
+    hit = np.nonzero(np.cumsum(Λ) >= 0.1)[0]
+    if hit.size == 0:
+        raise ValueError('"L2-10%": cumsum(Λ) never reaches 0.1 (the reference\'s findfirst returns nothing)')
+    return int(hit[0]) + 1
+
+
+def scale_data(ξ, Λ, distance: str):
+    """`scale_data` (Ex20F:24-37) for one vector or for the columns of a matrix; a copy is returned. Distances: "L2" /
+    "L2-full" (ξ .* sqrt(Λ)), "cdf" (cdf.(Normal(), ξ) .* sqrt(Λ), Ex20F:16-18), "cdf-full" (cdf only, Ex12F:52) and "L2-10%"
+    (the rows of _vq_rows, scaled as "L2": Ex12F:44-47)."""
+    from scipy.special import ndtr
+    Λ = np.asarray(Λ, dtype=np.float64)
+    Y = np.array(ξ, dtype=np.float64)
+    sq = np.sqrt(Λ) if Y.ndim == 1 else np.sqrt(Λ)[:, None]
+    if distance in ("L2", "L2-full"):
+        return Y * sq
+    if distance == "cdf":
+        return ndtr(Y) * sq
+    if distance == "cdf-full":
+        return ndtr(Y)
+    if distance == "L2-10%":
+        r = _vq_rows(Λ, distance)
+        return Y[:r] * sq[:r]
+    raise ValueError(f"unknown distance {distance!r}")
+
+
+def unscale_centers(C, Λ, distance: str):
+    """Centres of the scaled data back to ξ (Ex20F:66-71, Ex12F:42, 49, 55): the inverse of scale_data on its rows."""
+    from scipy.special import ndtri
+    C = np.array(C, dtype=np.float64)
+    sq = np.sqrt(np.asarray(Λ, dtype=np.float64)[:C.shape[0]])[:, None]
+    if distance in ("L2", "L2-full", "L2-10%"):
+        return C / sq
+    if distance == "cdf":
+        return ndtri(C / sq)
+    if distance == "cdf-full":
+        return ndtri(C)
+    raise ValueError(f"unknown distance {distance!r}")
+
+
+def get_scaled_data(ns: int, Λ, distance: str, rng: np.random.Generator):
+    """`get_scaled_data` (Ex20F:5-22): ns draws of ξ ~ N(0, I) as columns, scaled for `distance`. The reference seeds Julia's
+    generator with 987_654_321; here the caller brings the generator."""
+    return scale_data(rng.standard_normal((np.asarray(Λ).size, ns)), Λ, distance)
+
+
+def get_deterministic_grid(P: int, nKL: int, Λ, s: float):
+    """`get_deterministic_grid` (Ex20F:75-93) -> (hηt, hξt), nKL x P: column 0 is ξ = 0, column p = 1 .. 2^nKL holds -s / +s by
+    the last nKL bits of p (most significant first; p = 2^nKL gives all -s). The reference leaves further columns undefined;
+    here they are zero."""
+    if P < (1 << nKL) + 1 and nKL > 0:
+        raise ValueError(f"P = {P} columns cannot hold 0 and the 2^{nKL} corners")
+    hξt = np.zeros((nKL, P))
+    if nKL > 0:
+        for p in range(1, (1 << nKL) + 1):
+            for k in range(nKL):
+                hξt[k, p] = s if (p >> (nKL - 1 - k)) & 1 else -s
+    return np.sqrt(np.asarray(Λ, dtype=np.float64)[:nKL])[:, None] * hξt, hξt
+
+
+def get_gain_sequence(γ0: float, α: float, β: float, c: float, ns: int):
+    """`get_gain_sequence` (Ex13F:45-51): γ[t] = γ0 α / (t^c + β), t = 1 .. ns."""
+    t = np.arange(1, ns + 1, dtype=np.float64)
+    return γ0 * α / (t ** c + β)
+
+
+def clvq(X, P: int, γ, init):
+    """`clvq` (Ex13F:71-92): competitive learning, one sample after the other — sequential by construction, so it stays on the
+    host. `init`: P sample indices (the reference's initialize_quantizer draws them at random, Ex13F:23-43) or a d x P
+    codebook. The competitive phase is the strict `<` scan on the loop form of the distance."""
+    X = np.asarray(X, dtype=np.float64)
+    init = np.asarray(init)
+    H = X[:, init.astype(np.int64)].copy() if init.ndim == 1 else np.array(init, dtype=np.float64)
+    if H.shape != (X.shape[0], P):
+        raise ValueError("init: P sample indices or a d x P codebook")
+    for t in range(X.shape[1]):
+        a, _ = vq_scan(vq_dist2(X[:, t:t + 1], H))
+        p = int(a[0])
+        H[:, p] -= γ[t] * (H[:, p] - X[:, t])
+    return H
+
+
+def shepard_coefficients(ξ, interpolators, Λ, distance: str = "L2-full"):
+    """The coefficients of `shepard_interpolating_precond` (Ex14F:174-206), exactly as written there: Δξ = (interpolators[:, i]
+    .- ξ) .* Λ — weighted with Λ, not sqrt.(Λ): the reference's quirk, kept — d_i = sqrt(Δξ'Δξ), W = Σ 1 / d_i²,
+    c_i = (1 / d_i²) / W. A zero distance gives non-finite coefficients, as it does there."""
+    from scipy.special import ndtr
+    ξ, I, Λ = np.asarray(ξ, dtype=np.float64), np.asarray(interpolators, dtype=np.float64), np.asarray(Λ, dtype=np.float64)
+    n = I.shape[1]
+    dist = np.empty(n)
+    W = 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for i in range(n):
+            if distance == "L2-full":
+                Δ = (I[:, i] - ξ) * Λ
+            elif distance == "cdf-full":
+                Δ = ndtr(I[:, i] - ξ)
+            else:
+                raise ValueError(f"unknown distance {distance!r}")
+            dist[i] = np.sqrt(np.dot(Δ, Δ))
+            W += 1.0 / dist[i] ** 2
+        return (1.0 / dist ** 2) / W
