@@ -10,7 +10,13 @@ The reference rebuilds Π_amg_t on the host for every realization. Here one oper
 "Refresh"). Both iteration counts are printed per realization, with the time of the refresh beside the time of the host
 set-up it replaces (`--host-setup` measures that too).
 
-    python examples/example06_amg_realizations.py [--N 100] [--nreals 3] [--host-setup]
+`--device-assembly` keeps the whole realization on the device: ONE `A_op` is created once, and per realization
+ξ -> `KLField.coefficient` -> `FullAssemblyPlan.run` -> `A_op.set_values(values)` and `Π_amg_t.set_values(values)` ->
+`pcg(A_op, b, x0, Π)` with device tensors throughout; only ξ is uploaded. The device assembly has the bits of the host
+assembly (`update_isotropic_elliptic_assembly!`, EllipticPde.jl:291-377) of the same coefficient, so the iteration counts
+are those of the default path; its time is printed beside the host assembly's.
+
+    python examples/example06_amg_realizations.py [--N 100] [--nreals 3] [--host-setup] [--device-assembly]
 """
 import argparse
 import os
@@ -29,6 +35,7 @@ def main():
     ap.add_argument("--nreals", type=int, default=3)
     ap.add_argument("--seed", type=int, default=481456)
     ap.add_argument("--host-setup", action="store_true", help="also time fem.prepare_amg_precond(A_t) per realization")
+    ap.add_argument("--device-assembly", action="store_true", help="assemble A_t, b_t on the device and refresh one A_op in place")
     args = ap.parse_args()
     pkg = graft.load_package()
     fem, api = pkg.fem, pkg.api
@@ -38,7 +45,8 @@ def main():
     assemble = lambda a: fem.do_isotropic_elliptic_assembly(mesh.cells, mesh.points, dinds, mesh.point_marker, a, f, uexact)
     kl = fem.synthetic_kl(mesh.points)
     rng = np.random.default_rng(args.seed)
-    gs = [fem.draw(kl, rng)[1] for _ in range(args.nreals)]                               # :158-162
+    draws = [fem.draw(kl, rng) for _ in range(args.nreals)]                               # :158-162
+    gs = [g for _, g in draws]
     A_0, _ = assemble(np.ones(mesh.points.shape[1]))                                      # :96-103, exp.(g_0) with g_0 = 0
     n = A_0.shape[0]
     print(f"nnode = {mesh.points.shape[1]}\nnel = {mesh.cells.shape[1]}\nn = {n}")
@@ -52,6 +60,11 @@ def main():
     print(f"Π_amg_t: aggregation on A_0, plan and first numeric phase {time.time() - t:.2f} s")
     x0 = np.zeros(n)
     iters_0, iters_t = [], []
+    if args.device_assembly:
+        device_loop(args, fem, api, ctx, mesh, dinds, f, uexact, kl, [ξ for ξ, _ in draws], assemble, A_0, Π_amg_0, Π_amg_t)
+        Π_amg_t.close(); Π_amg_0.close()
+        ctx.close()
+        return
     for ireal, g in enumerate(gs, 1):
         A, b = assemble(np.exp(g))                                                        # :175-179
         A_op = api.SparseMatrixCSC(ctx, A)
@@ -72,6 +85,38 @@ def main():
     print(f"iters_0 = {iters_0}\niters_t = {iters_t}")
     Π_amg_t.close(); Π_amg_0.close()
     ctx.close()
+
+
+def device_loop(args, fem, api, ctx, mesh, dinds, f, uexact, kl, ξs, assemble, A_0, Π_amg_0, Π_amg_t):
+    import torch
+    plan = api.FullAssemblyPlan(ctx, fem.make_full_assembly_plan(mesh.cells, mesh.points, dinds, mesh.point_marker, f, uexact))
+    field = api.KLField(ctx, kl.Λ, kl.Ψ)
+    A_op = api.SparseMatrixCSC(ctx, A_0)                                                  # once: refreshed in place below
+    n = A_0.shape[0]
+    iters_0, iters_t = [], []
+    for ireal, ξ in enumerate(ξs, 1):
+        a = field.coefficient(torch.from_numpy(ξ).cuda())                                 # :175, exp.(g) on the device
+        ctx.synchronize()
+        t = time.perf_counter()
+        values, b = plan.run(a)                                                           # :176-179
+        ctx.synchronize()
+        dt_dev = time.perf_counter() - t
+        t = time.perf_counter()
+        assemble(a.cpu().numpy())
+        dt_host = time.perf_counter() - t
+        A_op.set_values(values)
+        t = time.perf_counter()
+        Π_amg_t.set_values(values)                                                        # :182
+        dt = time.perf_counter() - t
+        x0 = torch.zeros(n, dtype=torch.float64, device=a.device)
+        _, it_0, _ = api.pcg(A_op, b, x0.clone(), Π_amg_0)
+        u, it_t, _ = api.pcg(A_op, b, x0, Π_amg_t)
+        iters_0.append(int(it_0)); iters_t.append(int(it_t))
+        r = b - A_op * u
+        print(f"realization {ireal}: assembly {1e3 * dt_dev:.3f} ms on the device (host: {dt_host:.2f} s), set_values {1e3 * dt:.2f} ms; "
+              f"pcg it = {it_0} with Π_amg_0, {it_t} with Π_amg_t, |b - A u| / |b| = {float(torch.linalg.norm(r) / torch.linalg.norm(b)):.3e}")
+    print(f"iters_0 = {iters_0}\niters_t = {iters_t}")
+    A_op.close(); plan.close()
 
 
 if __name__ == "__main__":

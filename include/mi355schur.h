@@ -440,6 +440,40 @@ int mi_assembly_plan_create(mi_ctx_t ctx, int64_t nel, int64_t n_node, const int
                             int64_t n_matrix_entries, const int64_t *cptr, const int64_t *ccode, mi_plan_t *plan);
 int mi_assembly_run(mi_plan_t plan, const double *a_nodal, double *values);
 int mi_assembly_plan_destroy(mi_plan_t plan);
+/* ---------------------------------------------------------------- on-device FULL-system assembly (per-realization update)
+ * `do_isotropic_elliptic_assembly` / `update_isotropic_elliptic_assembly!(A_mat, b_vec, ..., coeff, f, u_exact)`
+ * (Fem/EllipticPde.jl:187-275 / :291-377) when only the nodal coefficient `a` changes: the loop of Examples 06, 09, 12-17,
+ * 19 and 20 in front of `pcg(A_t, b_t, 0, Π)`.
+ * mi_full_assembly_plan_create: the ROW-OWNED index plan (csrc/full_assembly_plan.hpp), derived here from
+ *   cells         3 x nel node indices (row i contiguous), `index_base` 0 or 1;  points  2 x n_node (x row, then y row)
+ *   point_marker  n_node, 1 = Dirichlet node; the free nodes, ascending, are the rows of A (`not_dirichlet_inds_g2l`)
+ *   n, rowptr, colidx   the CSR pattern the caller holds for A (sorted rows, `index_base`; A is bitwise symmetric, so the CSC
+ *                 arrays of Julia's A_mat are the same arrays): it must be the pattern the mesh produces
+ *   ue, be        3 x nel, as for mi_assembly_plan_create
+ *   The handle is a mi_plan_t: mi_assembly_plan_destroy frees it; mi_assembly_run on it is MI_ERR_BAD_ARG, as is
+ *   mi_full_assembly_run on a plan of mi_assembly_plan_create. MI_ERR_BAD_ARG, with a message that names the number, for:
+ *   a cell index outside the mesh, an element with a repeated vertex, a zero-area element, a row with more stored entries
+ *   than one workgroup's segment (4096), 4 nel >= 2^31, a pattern that is not the mesh's.
+ * mi_full_assembly_run: a_nodal (n_node) -> values (nnz(A), CSR order) and b (n); pointers per the context's pointer mode
+ *   (device pointers: asynchronous on the context's stream, legal inside a stream capture). One thread owns one row and adds
+ *   the contributions of the elements around its node in ascending element number, the order of `sparse(I,J,V)` and
+ *   `b[k] +=`: no atomics, bit-identical to the host loop and from run to run.
+ * mi_full_assembly_update: the same numbers; the values go straight into the device array of the mi_csr_create operator A
+ *   (same context, same pattern: checked in full the first time a plan meets an operator), b per the pointer mode.
+ * mi_full_assembly_stats: row blocks, incidences (free element vertices) and the device bytes the plan keeps.
+ * mi_csr_set_values: new values (nnz, pointer mode) on the pattern of mi_csr_create, into the same device array: solve
+ *   graphs captured for the operator stay valid. MI_ERR_BAD_ARG for any other operator.
+ * mi_diag_set_from_csr: dinv[r] = 1.0 / A[r, r] on the device, into the same device array of the mi_diag_create operator M.
+ *   MI_ERR_BAD_ARG (M unchanged) if M is the identity or not diagonal, of another size or context than A, or if a row of A
+ *   stores no diagonal entry. Synchronous. */
+int mi_full_assembly_plan_create(mi_ctx_t ctx, int64_t nel, int64_t n_node, const int64_t *cells, int index_base,
+                                 const double *points, const int64_t *point_marker, int64_t n, const int64_t *rowptr,
+                                 const int64_t *colidx, const double *ue, const double *be, mi_plan_t *plan);
+int mi_full_assembly_run(mi_plan_t plan, const double *a_nodal, double *values, double *b);
+int mi_full_assembly_update(mi_plan_t plan, const double *a_nodal, mi_op_t A, double *b);
+int mi_full_assembly_stats(mi_plan_t plan, int64_t *row_blocks, int64_t *incidences, int64_t *bytes_kept);
+int mi_csr_set_values(mi_op_t op, const double *val);
+int mi_diag_set_from_csr(mi_op_t M, mi_op_t A);
 int mi_schur_matfree_set_values(mi_op_t op, const double *ii_val, const double *ig_val, const double *gg_val);
 int mi_schur_matfree_rhs(mi_op_t op, const double *b_I, const double *b_gamma, double *b_schur);
 /* `get_subdomain_solutions(u_Γ, A_IId, A_IΓd, b_Id)` (EPDD.jl:1014-1025): u_Id = A_IIdd \ (b_Id - A_IΓdd u_Γd) for the

@@ -105,6 +105,12 @@ SIGNATURES = {
     "mi_assembly_plan_create": [vp, i64, i64, i64p, C.c_int, f64p, f64p, f64p, f64p, i64, i64, i64p, i64p, C.POINTER(vp)],
     "mi_assembly_run": [vp, vp, vp],
     "mi_assembly_plan_destroy": [vp],
+    "mi_full_assembly_plan_create": [vp, i64, i64, i64p, C.c_int, f64p, i64p, i64, i64p, i64p, f64p, f64p, C.POINTER(vp)],
+    "mi_full_assembly_run": [vp, vp, vp, vp],
+    "mi_full_assembly_update": [vp, vp, vp, vp],
+    "mi_full_assembly_stats": [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)],
+    "mi_csr_set_values": [vp, vp],
+    "mi_diag_set_from_csr": [vp, vp],
     "mi_schur_matfree_set_values": [vp, vp, vp, vp],
     "mi_schur_setup_create": [vp, i64, i64p, i64p, i64pp, i64pp, i64pp, i64pp, i64pp, i64pp, C.c_int, C.POINTER(vp)],
     "mi_schur_setup_run": [vp, vp, vp, vp, vp, vp, vp],

@@ -376,7 +376,34 @@ def SparseMatrixCSC(ctx: Context, A, index_base: int = 0) -> Operator:
     h = vp()
     check(ctx._L.mi_csr_create(ctx._h, i64(n), i64(n), ptr.ctypes.data_as(i64p), idx.ctypes.data_as(i64p),
                                val.ctypes.data_as(f64p), C.c_int(index_base), C.byref(h)))
-    return Operator(ctx, h)
+    op = CsrOperator(ctx, h)
+    op.nnz = int(val.size)
+    return op
+
+
+class CsrOperator(Operator):
+    """What `SparseMatrixCSC` returns: the matrix operator, whose values can be replaced in place."""
+    nnz = 0
+
+    def set_values(self, A_or_nzval) -> None:
+        """A new realization on the pattern of construction: a scipy sparse matrix, or its CSR values (sorted rows; the CSC
+        values of a symmetric matrix) as a numpy array or a torch CUDA tensor (`mi_csr_set_values`). The values go into the
+        same device array, so the solve graphs captured for this operator stay valid. A torch tensor is copied
+        asynchronously on the context's stream."""
+        v = A_or_nzval
+        if sp.issparse(v):
+            v = sp.csr_matrix(v)
+            v.sum_duplicates()
+            v.sort_indices()
+            v = _f64(v.data)
+        count = v.numel() if _is_torch(v) else np.size(v)
+        if count != self.nnz:                       # the C call takes the length on trust: refused here, in its name
+            raise MiError(_lib.MI_ERR_BAD_ARG, f"mi_csr_set_values: {count} values for {self.nnz} stored entries")
+        self.ctx._mode_for(v)
+        k, p = self.ctx._ptr(v, self.nnz)
+        self.ctx._order((k,), after=False)
+        check(self.ctx._L.mi_csr_set_values(self._h, p))
+        self.ctx._record(k)
 
 
 def IdentityPreconditioner(ctx: Context, n: int) -> Operator:
@@ -386,11 +413,21 @@ def IdentityPreconditioner(ctx: Context, n: int) -> Operator:
 
 
 def JacobiPreconditioner(ctx: Context, diag) -> Operator:
-    """z = r ./ diag(A) — config 2's stand-in for Example01's AMG preconditioner (`AMGPreconditioner` is the V-cycle itself)."""
+    """z = r ./ diag(A) — config 2's stand-in for Example01's AMG preconditioner (`AMGPreconditioner` is the V-cycle itself).
+    `.refresh(A_op)` follows a matrix operator whose values have changed, on the device."""
     dinv = _f64(1.0 / np.asarray(diag, dtype=np.float64))
     h = vp()
     check(ctx._L.mi_diag_create(ctx._h, i64(dinv.size), dinv.ctypes.data_as(f64p), C.byref(h)))
-    return Operator(ctx, h)
+    return JacobiOperator(ctx, h)
+
+
+class JacobiOperator(Operator):
+    """What `JacobiPreconditioner` returns."""
+
+    def refresh(self, A: "CsrOperator") -> None:
+        """dinv[r] = 1 / A[r, r] from the values the `SparseMatrixCSC` operator `A` holds now (`mi_diag_set_from_csr`): no
+        host round trip, same device array (solve graphs stay valid). Synchronous."""
+        check(self.ctx._L.mi_diag_set_from_csr(self._h, getattr(A, "_h", None)))
 
 
 class SparseDirectPreconditioner(Operator):
@@ -1093,6 +1130,78 @@ class AssemblyPlan:
             return values[L[name][lo][0]:L[name][hi - 1][0] + L[name][hi - 1][1]]
         off, cnt = L["bΓ"]
         return span("II"), span("IΓ"), span("ΓΓ"), span("bI"), values[off:off + cnt]
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self.ctx._L.mi_assembly_plan_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FullAssemblyPlan:
+    """Device executor of a `fem.FullAssemblyPlan` (`mi_full_assembly_plan_create`): the numeric half of
+    `do_isotropic_elliptic_assembly(cells, points, dinds, point_marker, a, f, uexact)` (EllipticPde.jl:187-275) for a new
+    nodal coefficient vector, bit for bit. `run(a) -> (values, b)` (CSR values of A on `plan.rowptr` / `plan.colidx`);
+    `update(a, A_op) -> b` writes the values straight into a `SparseMatrixCSC` operator of that pattern — the reference's
+    `update_isotropic_elliptic_assembly!` (:291-377)."""
+
+    def __init__(self, ctx: Context, plan, index_base: int = 0):
+        self.ctx, self.plan = ctx, plan
+        h = vp()
+        cells = _i64(plan.cells) + index_base      # index_base=1: node numbers as Julia's `cells` holds them
+        rowptr, colidx = _i64(plan.rowptr) + index_base, _i64(plan.colidx) + index_base
+        points, marker, ue, be = _f64(plan.points), _i64(plan.point_marker), _f64(plan.ue), _f64(plan.be)
+        check(ctx._L.mi_full_assembly_plan_create(
+            ctx._h, i64(cells.shape[1]), i64(plan.n_node), cells.ctypes.data_as(i64p), C.c_int(index_base),
+            points.ctypes.data_as(f64p), marker.ctypes.data_as(i64p), i64(plan.n), rowptr.ctypes.data_as(i64p),
+            colidx.ctypes.data_as(i64p), ue.ctypes.data_as(f64p), be.ctypes.data_as(f64p), C.byref(h)))
+        self._h = h
+        self.n, self.nnz = plan.n, plan.nnz
+
+    def _b_like(self, a_nodal):
+        if _is_torch(a_nodal):
+            import torch
+            return torch.empty(self.n, dtype=torch.float64, device=a_nodal.device)
+        return np.empty(self.n)
+
+    def run(self, a_nodal):
+        """(values[nnz], b[n]): numpy in -> numpy out; torch CUDA tensor in -> torch CUDA tensors out (no host copy)."""
+        self.ctx._mode_for(a_nodal)
+        ka, pa = self.ctx._ptr(a_nodal, self.plan.n_node)
+        b = self._b_like(ka)
+        if _is_torch(ka):
+            import torch
+            values = torch.empty(self.nnz, dtype=torch.float64, device=ka.device)
+        else:
+            values = np.empty(self.nnz)
+        _, pv = self.ctx._ptr(values, writable=True)
+        _, pb = self.ctx._ptr(b, writable=True)
+        self.ctx._order((ka,), after=False)
+        check(self.ctx._L.mi_full_assembly_run(self._h, pa, pv, pb))
+        self.ctx._record(ka, values, b)
+        return values, b
+
+    def update(self, a_nodal, A: "CsrOperator"):
+        """b; the values of A(a) go into the device array of the operator `A` (its solve graphs stay valid)."""
+        self.ctx._mode_for(a_nodal)
+        ka, pa = self.ctx._ptr(a_nodal, self.plan.n_node)
+        b = self._b_like(ka)
+        _, pb = self.ctx._ptr(b, writable=True)
+        self.ctx._order((ka,), after=False)
+        check(self.ctx._L.mi_full_assembly_update(self._h, pa, getattr(A, "_h", None), pb))
+        self.ctx._record(ka, b)
+        return b
+
+    def stats(self) -> dict:
+        """dict(row_blocks, incidences, bytes_kept) (`mi_full_assembly_stats`)"""
+        a, b, c = i64(), i64(), i64()
+        check(self.ctx._L.mi_full_assembly_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(row_blocks=int(a.value), incidences=int(b.value), bytes_kept=int(c.value))
 
     def close(self) -> None:
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
@@ -2080,7 +2189,8 @@ class InterpolatingPreconditioner(Operator):
 def get_centroidal_preconds(ctx: Context, centroids, field: KLField, assemble: Callable, A0, **amg_kw):
     """`get_centroidal_preconds(centroids, Λ, Ψ)` (Ex12F:85-113): one constant AMG preconditioner per centroid. For column p,
     a = field.coefficient(ξ_p) (`set!` + `exp.(g)`; a centroid with fewer rows than the field has modes is zero-padded, as
-    Ex20F:100-101 does), A_p = assemble(a) — a scipy sparse matrix on the pattern of A0, or its CSR values — and
+    Ex20F:100-101 does), A_p = assemble(a) — a scipy sparse matrix on the pattern of A0, or its CSR values, e.g.
+    `lambda a: FullAssemblyPlan(ctx, plan).run(a)[0]` for an assembly that stays on the device — and
     `AMGPreconditioner(ctx, A0, device_setup=True)` + `.set_values(A_p)`: the aggregates are those of A0 for every centroid."""
     centroids = np.asarray(centroids, dtype=np.float64)
     Π = []

@@ -66,4 +66,13 @@ struct mi_plan_s {
   mi::DevBuf<int> cells, ccode;
   mi::DevBuf<long long> cptr;
   mi::DevBuf<double> G, area, ue, be, da, a_stage, out_stage;
+  // a plan of mi_full_assembly_plan_create (full_assembly.hpp) instead: the row-owned plan of the full system
+  bool full = false;
+  int n = 0, nblk = 0;
+  int64_t nnz = 0, ninc = 0, bytes_kept = 0;
+  mi::DevBuf<int> rowptr, diag_pos, inc_ptr, inc_code, blk_row;
+  mi::DevBuf<unsigned> inc_pos;
+  mi::DevBuf<double> points, b_stage;
+  std::vector<int> rowptr_h, colidx_h;   // the pattern, to compare an operator's with (mi_full_assembly_update)
+  const void *checked_op = nullptr;      // the operator's device column array that has been compared, and found equal
 };

@@ -18,6 +18,7 @@
 #include "kl.hpp"
 #include "kl_field.hpp"
 #include "vq.hpp"
+#include "full_assembly.hpp"
 
 namespace mi {
 
@@ -206,7 +207,7 @@ using namespace mi;
 
 extern "C" {
 
-int mi_version(void) { return 300; }  // 0.3.0
+int mi_version(void) { return 400; }  // 0.4.0
 const char *mi_last_error(void) { return last_error().c_str(); }
 
 int mi_device_count(int *count) {
@@ -1520,6 +1521,7 @@ int mi_assembly_plan_create(mi_ctx_t ctx, int64_t nel, int64_t n_node, const int
 }
 int mi_assembly_run(mi_plan_t plan, const double *a_nodal, double *values) {
   if (!plan || !a_nodal || (plan->n_entries && !values)) return fail(MI_ERR_BAD_ARG, "mi_assembly_run: NULL argument");
+  if (plan->full) return fail(MI_ERR_BAD_ARG, "mi_assembly_run: this is a plan of mi_full_assembly_plan_create; mi_full_assembly_run executes it");
   mi_ctx_s *c = plan->ctx;
   return guarded([&]() -> int {
     c->use();
@@ -1543,6 +1545,137 @@ int mi_assembly_plan_destroy(mi_plan_t plan) {
     plan->ctx->use();
     (void)hipStreamSynchronize(plan->ctx->stream);
     delete plan;
+    return MI_OK;
+  });
+}
+// ---------------------------------------------------------------- on-device full-system assembly
+int mi_full_assembly_plan_create(mi_ctx_t ctx, int64_t nel, int64_t n_node, const int64_t *cells, int index_base, const double *points,
+                                 const int64_t *point_marker, int64_t n, const int64_t *rowptr, const int64_t *colidx, const double *ue,
+                                 const double *be, mi_plan_t *plan) {
+  const char *me = "mi_full_assembly_plan_create";
+  if (!plan) return fail(MI_ERR_BAD_ARG, "%s: plan is NULL", me);
+  *plan = nullptr;
+  if (!ctx || !rowptr || !colidx || !ue || !be) return fail(MI_ERR_BAD_ARG, "%s: ctx, rowptr, colidx, ue or be is NULL", me);
+  return guarded([&]() -> int {
+    fap::Plan pl;
+    std::string err;
+    if (fap::make_plan(nel, n_node, cells, index_base, points, point_marker, n, rowptr, colidx, pl, err) != fap::OK)
+      return fail(MI_ERR_BAD_ARG, "%s: %s", me, err.c_str());
+    ctx->use();
+    std::unique_ptr<mi_plan_s> p(new mi_plan_s);
+    p->ctx = ctx; p->full = true; p->nel = pl.nel; p->n_node = pl.n_node; p->n = pl.n; p->nblk = pl.nblk();
+    p->nnz = pl.nnz(); p->ninc = pl.ninc(); p->bytes_kept = pl.bytes();
+    hipStream_t s = ctx->stream;
+    p->cells.upload(pl.cells, s); p->rowptr.upload(pl.rowptr, s); p->diag_pos.upload(pl.diag_pos, s); p->inc_ptr.upload(pl.inc_ptr, s);
+    p->inc_code.upload(pl.inc_code, s); p->inc_pos.upload(pl.inc_pos, s); p->blk_row.upload(pl.blk_row, s);
+    p->points.upload(points, (size_t)2 * pl.n_node, s); p->ue.upload(ue, (size_t)3 * pl.nel, s); p->be.upload(be, (size_t)3 * pl.nel, s);
+    MI_HIP(hipStreamSynchronize(s));
+    p->rowptr_h.swap(pl.rowptr); p->colidx_h.swap(pl.colidx);
+    *plan = p.release();
+    return MI_OK;
+  });
+}
+// values_dev, b_dev: device pointers
+static void full_assembly_launch(mi_plan_s *p, const double *a_dev, double *values_dev, double *b_dev) {
+  if (!p->nblk) return;
+  const int per = (p->nblk + 7) / 8;
+  hipLaunchKernelGGL(k_assemble_full, dim3(8 * per), dim3(FA_ROWS), 0, p->ctx->stream, p->nblk, per, p->nel, (int)p->n_node, p->blk_row.p,
+                     p->rowptr.p, p->diag_pos.p, p->inc_ptr.p, p->inc_code.p, p->inc_pos.p, p->cells.p, p->points.p, p->ue.p, p->be.p,
+                     a_dev, values_dev, b_dev);
+  MI_HIP(hipGetLastError());
+}
+int mi_full_assembly_run(mi_plan_t plan, const double *a_nodal, double *values, double *b) {
+  const char *me = "mi_full_assembly_run";
+  if (!plan || !a_nodal) return fail(MI_ERR_BAD_ARG, "%s: NULL argument", me);
+  if (!plan->full) return fail(MI_ERR_BAD_ARG, "%s: this is a plan of mi_assembly_plan_create; mi_assembly_run executes it", me);
+  if ((plan->nnz && !values) || (plan->n && !b)) return fail(MI_ERR_BAD_ARG, "%s: values or b is NULL", me);
+  mi_ctx_s *c = plan->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    In ai(c, a_nodal, (size_t)plan->n_node, plan->a_stage);
+    InOut vo(c, values, (size_t)plan->nnz, plan->out_stage, false);
+    InOut bo(c, b, (size_t)plan->n, plan->b_stage, false);
+    full_assembly_launch(plan, ai.dev, vo.dev, bo.dev);
+    vo.finish();
+    bo.finish();
+    return MI_OK;
+  });
+}
+int mi_full_assembly_update(mi_plan_t plan, const double *a_nodal, mi_op_t A, double *b) {
+  const char *me = "mi_full_assembly_update";
+  if (!plan || !a_nodal) return fail(MI_ERR_BAD_ARG, "%s: NULL argument", me);
+  if (!plan->full) return fail(MI_ERR_BAD_ARG, "%s: this is a plan of mi_assembly_plan_create", me);
+  CsrOp *op = A && A->impl ? dynamic_cast<CsrOp *>(A->impl.get()) : nullptr;
+  if (!op) return fail(MI_ERR_BAD_ARG, "%s: A is not a sparse matrix operator (mi_csr_create)", me);
+  if (plan->n && !b) return fail(MI_ERR_BAD_ARG, "%s: b is NULL", me);
+  mi_ctx_s *c = plan->ctx;
+  if (op->ctx != c) return fail(MI_ERR_BAD_ARG, "%s: A belongs to another context", me);
+  if (op->A.n_rows != plan->n || op->A.nnz != plan->nnz)
+    return fail(MI_ERR_BAD_ARG, "%s: A is %d x %d with %lld stored entries, the plan's system %d x %d with %lld", me, op->A.n_rows, op->A.n_cols,
+                (long long)op->A.nnz, plan->n, plan->n, (long long)plan->nnz);
+  return guarded([&]() -> int {
+    c->use();
+    if (plan->checked_op != (const void *)op->A.col.p) {   // once per operator: the whole pattern (synchronous)
+      std::vector<int> rp((size_t)plan->n + 1), ci((size_t)plan->nnz);
+      MI_HIP(hipMemcpyAsync(rp.data(), op->A.rowptr.p, rp.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      if (plan->nnz) MI_HIP(hipMemcpyAsync(ci.data(), op->A.col.p, ci.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      MI_HIP(hipStreamSynchronize(c->stream));
+      if (rp != plan->rowptr_h || ci != plan->colidx_h) return fail(MI_ERR_BAD_ARG, "%s: the pattern of A is not the plan's", me);
+      plan->checked_op = op->A.col.p;
+    }
+    In ai(c, a_nodal, (size_t)plan->n_node, plan->a_stage);
+    InOut bo(c, b, (size_t)plan->n, plan->b_stage, false);
+    full_assembly_launch(plan, ai.dev, op->A.val.p, bo.dev);
+    bo.finish();
+    return MI_OK;
+  });
+}
+int mi_full_assembly_stats(mi_plan_t plan, int64_t *row_blocks, int64_t *incidences, int64_t *bytes_kept) {
+  if (!plan || !plan->full) return fail(MI_ERR_BAD_ARG, "mi_full_assembly_stats: not a plan of mi_full_assembly_plan_create");
+  if (row_blocks) *row_blocks = plan->nblk;
+  if (incidences) *incidences = plan->ninc;
+  if (bytes_kept) *bytes_kept = plan->bytes_kept;
+  return MI_OK;
+}
+int mi_csr_set_values(mi_op_t op, const double *val) {
+  const char *me = "mi_csr_set_values";
+  CsrOp *m = op && op->impl ? dynamic_cast<CsrOp *>(op->impl.get()) : nullptr;
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s: not a sparse matrix operator (mi_csr_create)", me);
+  if (m->A.nnz && !val) return fail(MI_ERR_BAD_ARG, "%s: val is NULL", me);
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    if (!m->A.nnz) return MI_OK;
+    const bool dev = c->ptr_mode == MI_PTR_DEVICE;
+    MI_HIP(hipMemcpyAsync(m->A.val.p, val, (size_t)m->A.nnz * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if (!dev) MI_HIP(hipStreamSynchronize(c->stream));   // the caller's array may change right after
+    return MI_OK;
+  });
+}
+int mi_diag_set_from_csr(mi_op_t M, mi_op_t A) {
+  const char *me = "mi_diag_set_from_csr";
+  DiagOp *d = M && M->impl ? dynamic_cast<DiagOp *>(M->impl.get()) : nullptr;
+  CsrOp *a = A && A->impl ? dynamic_cast<CsrOp *>(A->impl.get()) : nullptr;
+  if (!d || d->identity) return fail(MI_ERR_BAD_ARG, "%s: M is not a diagonal operator with values (mi_diag_create with dinv)", me);
+  if (!a) return fail(MI_ERR_BAD_ARG, "%s: A is not a sparse matrix operator (mi_csr_create)", me);
+  if (a->ctx != d->ctx) return fail(MI_ERR_BAD_ARG, "%s: M and A belong to different contexts", me);
+  if (a->n != d->n) return fail(MI_ERR_BAD_ARG, "%s: M is of size %lld, A of size %lld", me, (long long)d->n, (long long)a->n);
+  mi_ctx_s *c = d->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    if (!d->n) return MI_OK;
+    DevBuf<int> flag(1);
+    int missing = -1;
+    MI_HIP(hipMemcpyAsync(flag.p, &missing, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    const int grid = grid_for(d->n);
+    hipLaunchKernelGGL(k_diag_from_csr, dim3(grid), dim3(NT), 0, c->stream, (int)d->n, 0, a->A.rowptr.p, a->A.col.p, a->A.val.p, d->dinv.p, flag.p);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipMemcpyAsync(&missing, flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    if (missing >= 0) return fail(MI_ERR_BAD_ARG, "%s: row %d of A stores no diagonal entry", me, missing);
+    hipLaunchKernelGGL(k_diag_from_csr, dim3(grid), dim3(NT), 0, c->stream, (int)d->n, 1, a->A.rowptr.p, a->A.col.p, a->A.val.p, d->dinv.p, flag.p);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipStreamSynchronize(c->stream));   // `flag` goes back to the pool
     return MI_OK;
   });
 }

@@ -650,6 +650,208 @@ def make_assembly_plan(cells, points, epart, sub: Subdomains, f, uexact) -> Asse
 
 
 # --------------------------------------------------------------------------------------
+# Row-owned plan of the full-system assembly (Fem/EllipticPde.jl:187-275, in place :291-377)
+# --------------------------------------------------------------------------------------
+FA_ROWS = 256        # csrc/full_assembly_plan.hpp: rows of a row block (one thread each)
+FA_SEG = 4096        # stored entries of a row block (one workgroup's LDS segment)
+FA_DIR = 0xFFFF      # "Dirichlet" in a 16-bit row position
+
+
+@dataclass
+class FullAssemblyPlan:
+    """The index half of `do_isotropic_elliptic_assembly` / `update_isotropic_elliptic_assembly!` (EllipticPde.jl:187-275 /
+    :291-377) for a FIXED mesh, Dirichlet maps, `f` and `uexact`: what Example06's realization loop redoes for every draw
+    although only `a` changes. The python mirror of csrc/full_assembly_plan.hpp, array for array.
+
+    Row-owned: free node r is row r of A; everything in row r and in b[r] comes from the elements incident to that node, in
+    ascending element number (the order of `sparse(I,J,V)` and `b[k] +=`). `inc_code[inc_ptr[r]:inc_ptr[r+1]]` = 4 e + i
+    (the row's node is vertex i of element e); `inc_pos` holds, for the two other vertices in ascending local index, the
+    position of their column in the row (low / high 16 bits) or FA_DIR: a Dirichlet vertex, whose pair is a lifting term of
+    b[r]. `blk_row`: row blocks of at most FA_ROWS rows and FA_SEG stored entries, never a split row.
+    `api.FullAssemblyPlan(ctx, plan)` runs it on the GPU."""
+    cells: np.ndarray      # (3, nel) int64, 0-based
+    points: np.ndarray     # (2, n_node)
+    point_marker: np.ndarray
+    ue: np.ndarray         # (3, nel)
+    be: np.ndarray         # (3, nel)
+    node_row: np.ndarray
+    rowptr: np.ndarray
+    colidx: np.ndarray
+    diag_pos: np.ndarray
+    inc_ptr: np.ndarray
+    inc_code: np.ndarray
+    inc_pos: np.ndarray
+    blk_row: np.ndarray
+
+    @property
+    def n(self) -> int:
+        return self.rowptr.size - 1
+
+    @property
+    def nnz(self) -> int:
+        return self.colidx.size
+
+    @property
+    def n_node(self) -> int:
+        return self.points.shape[1]
+
+    @property
+    def n_entries(self) -> int:
+        return self.nnz + self.n
+
+    def bytes(self) -> int:
+        """Device bytes of the plan: index arrays, ue, be, points (full_assembly_plan.hpp `Plan::bytes`)."""
+        nel = self.cells.shape[1]
+        ints = (3 * nel + self.rowptr.size + self.diag_pos.size + self.inc_ptr.size + self.inc_code.size + self.inc_pos.size
+                + self.blk_row.size)
+        return 4 * ints + 8 * (6 * nel + 2 * self.n_node)
+
+    def system(self, values, b):
+        """(A csr, b) from the CSR values and the right-hand side of a run."""
+        A = sp.csr_matrix((np.array(values, dtype=np.float64), self.colidx.copy(), self.rowptr.copy()), shape=(self.n, self.n))
+        A.has_sorted_indices = True
+        return A, np.array(b, dtype=np.float64)
+
+    def run(self, a):
+        """(values, b): numpy restatement of `k_assemble_full`. Row r walks its incidence list; per incidence the element's
+        terms are recomputed in the order of `_element_terms`, and each ΔK_ij is added to the row's entry or, for a Dirichlet
+        vertex j, as -(ue_j ΔK_ij) to b[r] (j ascending), then Δb_i. Every accumulator starts at -0.0, the exact additive
+        identity, so the first contribution is an assignment in effect (`_segment_sums`)."""
+        a = np.asarray(a, dtype=np.float64)
+        n, nel = self.n, self.cells.shape[1]
+        vals = np.full(self.nnz, -0.0)
+        b = np.full(n, -0.0)
+        cnt = np.diff(self.inc_ptr)
+        for p in range(int(cnt.max()) if n else 0):
+            r = np.flatnonzero(cnt > p)
+            q = self.inc_ptr[r] + p
+            e, i = self.inc_code[q] >> 2, self.inc_code[q] & 3
+            c = self.cells[:, e]
+            x, y, av = self.points[0][c], self.points[1][c], a[c]
+            Δa = ((av[0] + av[1]) + av[2]) / 3.0
+            Δx = np.stack([x[2] - x[1], x[0] - x[2], x[1] - x[0]])
+            Δy = np.stack([y[1] - y[2], y[2] - y[0], y[0] - y[1]])
+            Area = (Δx[2] * Δy[1] - Δx[1] * Δy[2]) / 2.0
+            k = np.arange(r.size)
+            Δxi, Δyi = Δx[i, k], Δy[i, k]
+            slot = np.zeros(r.size, dtype=np.int64)
+            for j in range(3):
+                K = Δa * (Δyi * Δy[j] + Δxi * Δx[j]) / 4 / Area
+                own = i == j
+                pos = np.where(own, self.diag_pos[r], (self.inc_pos[q] >> (16 * slot)) & 0xFFFF)
+                slot = slot + ~own
+                lift = pos == FA_DIR
+                t = self.rowptr[r[~lift]] + pos[~lift]
+                vals[t] = vals[t] + K[~lift]
+                b[r[lift]] = b[r[lift]] + -(self.ue[j, e[lift]] * K[lift])
+            b[r] = b[r] + self.be[i, e]
+        b[cnt == 0] = 0.0
+        return vals, b
+
+    def as_block_plan(self) -> AssemblyPlan:
+        """The same system as a generic `AssemblyPlan`: entries = the CSR values of A followed by b, one contribution code per
+        term (12 e + 3 i + j, or 12 e + 9 + i). `oracle.run_assembly_plan` and `api.AssemblyPlan` execute it unchanged: the
+        independent cross-check of `run` and of the device kernel."""
+        nel = self.cells.shape[1]
+        x, y = self.points[0][self.cells], self.points[1][self.cells]
+        G, Area = _element_geometry(x, y)
+        row = np.repeat(np.arange(self.n), np.diff(self.inc_ptr))
+        e, i = self.inc_code >> 2, self.inc_code & 3
+        target, code = [], []
+        slot = np.zeros(row.size, dtype=np.int64)
+        for j in range(3):
+            own = i == j
+            pos = np.where(own, self.diag_pos[row], (self.inc_pos >> (16 * slot)) & 0xFFFF)
+            slot = slot + ~own
+            lift = pos == FA_DIR
+            target.append(np.where(lift, self.nnz + row, self.rowptr[row] + np.where(lift, 0, pos)))
+            code.append(np.where(lift, 12 * e + 3 * j + i, 12 * e + 3 * i + j))
+        target.append(self.nnz + row)
+        code.append(12 * e + 9 + i)
+        target, code = np.concatenate(target), np.concatenate(code)
+        order = np.lexsort((code, target))
+        cptr = np.zeros(self.n_entries + 1, dtype=np.int64)
+        np.cumsum(np.bincount(target, minlength=self.n_entries), out=cptr[1:])
+        return AssemblyPlan(np.ascontiguousarray(self.cells, dtype=np.int64), np.ascontiguousarray(G.reshape(9, -1)),
+                            np.ascontiguousarray(Area), np.ascontiguousarray(self.ue), np.ascontiguousarray(self.be), cptr,
+                            code[order].astype(np.int64), self.nnz, {}, {}, self.n_node)
+
+
+def make_full_assembly_plan(cells, points, dinds: DirichletInds, point_marker, f, uexact) -> FullAssemblyPlan:
+    """Python mirror of `mi::fap::make_plan` (csrc/full_assembly_plan.hpp); `f` and `uexact` enter through `be` and `ue`
+    only. Refusals raise ValueError with the text of the C++ plan."""
+    cells = np.ascontiguousarray(cells, dtype=np.int64)
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    marker = np.ascontiguousarray(point_marker, dtype=np.int64).ravel()
+    nel, n_node = cells.shape[1], points.shape[1]
+    if nel < 1:
+        raise ValueError(f"full assembly plan: nel = {nel} elements (at least 1 expected)")
+    if 4 * nel >= 2 ** 31:
+        raise ValueError(f"full assembly plan: nel = {nel} elements: 4 nel = {4 * nel} does not fit 31 bits")
+    bad = np.argwhere(((cells < 0) | (cells >= n_node)).T)
+    if bad.size:
+        e, i = bad[0]
+        raise ValueError(f"full assembly plan: element {e}, vertex {i}: node {cells[i, e]} is outside the mesh")
+    rep = (cells[0] == cells[1]) | (cells[1] == cells[2]) | (cells[0] == cells[2])
+    x, y = points[0][cells], points[1][cells]
+    _, Area = _element_geometry(x, y)
+    flat = ~((Area != 0.0) & np.isfinite(Area))
+    first = np.flatnonzero(rep | flat)
+    if first.size:
+        e = int(first[0])
+        if rep[e]:
+            c = cells[:, e]
+            raise ValueError(f"full assembly plan: element {e} lists node {c[0] if c[0] in (c[1], c[2]) else c[1]} twice")
+        raise ValueError(f"full assembly plan: element {e} has zero area (or coordinates that are not finite)")
+    node_row = np.full(n_node, -1, dtype=np.int64)
+    free = np.flatnonzero(marker != 1)
+    node_row[free] = np.arange(free.size)
+    if not np.array_equal(node_row, dinds.not_dirichlet_g2l):
+        raise ValueError("full assembly plan: dinds.not_dirichlet_g2l is not the ascending numbering of the nodes with point_marker != 1")
+    n = free.size
+    loc = node_row[cells]                                      # (3, nel)
+    el = np.arange(nel)
+    rows = np.concatenate([loc[i] for i in range(3)])
+    codes = np.concatenate([4 * el + i for i in range(3)])
+    keep = rows >= 0
+    rows, codes = rows[keep], codes[keep]
+    order = np.lexsort((codes, rows))
+    rows, codes = rows[order], codes[order]
+    inc_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=inc_ptr[1:])
+    e, i = codes >> 2, codes & 3
+    cols = loc[:, e]                                           # (3, ninc): columns of the three vertices, -1 = Dirichlet
+    key = np.unique(np.concatenate([(rows * n + cols[j])[cols[j] >= 0] for j in range(3)])) if rows.size else np.zeros(0, dtype=np.int64)
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // max(n, 1), minlength=n), out=rowptr[1:])
+    length = np.diff(rowptr)
+    if n and length.max() > FA_SEG:
+        r = int(np.argmax(length > FA_SEG))
+        raise ValueError(f"full assembly plan: row {r} has {length[r]} stored entries, more than FA_SEG = {FA_SEG}")
+    colidx = key % max(n, 1)
+    diag_pos = np.searchsorted(key, np.arange(n) * n + np.arange(n)) - rowptr[:-1]
+    inc_pos = np.zeros(rows.size, dtype=np.int64)
+    slot = np.zeros(rows.size, dtype=np.int64)
+    for j in range(3):
+        other = i != j
+        pos = np.where(cols[j] >= 0, np.searchsorted(key, rows * n + np.maximum(cols[j], 0)) - rowptr[rows], FA_DIR)
+        inc_pos = inc_pos | np.where(other, pos << (16 * slot), 0)
+        slot = slot + other
+    blk = [0]
+    while blk[-1] < n:
+        r0 = blk[-1]
+        blk.append(int(min(r0 + FA_ROWS, np.searchsorted(rowptr, rowptr[r0] + FA_SEG, side="right") - 1)))
+    fv = _eval(f, x, y)
+    be = np.empty((3, nel))
+    for v in range(3):
+        j, k = (v + 1) % 3, (v + 2) % 3
+        be[v] = (2 * fv[v] + fv[j] + fv[k]) * Area / 12
+    ue = _eval(uexact, x, y)
+    return FullAssemblyPlan(cells, points, marker, np.ascontiguousarray(ue), np.ascontiguousarray(be), node_row, rowptr, colidx,
+                            diag_pos, inc_ptr, codes, inc_pos, np.asarray(blk, dtype=np.int64))
+
+
+# --------------------------------------------------------------------------------------
 # Interior solves and assembled local Schur complements
 # --------------------------------------------------------------------------------------
 class InteriorSolver:

@@ -37,7 +37,7 @@ export MiContext, MiOperator, MiPrecond,
        keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!,
        SparseDirectPreconditioner, spd_direct_stats, bj_set_values!, MiLorasc, set_correction!, MiNNInduced, set_coupling!,
        mi_eigsolve, mi_geneigsolve, MiAMGPreconditioner, amg_stats,
-       MiKlField, MiMcmcSampler, coefficient!, klfield_stats
+       MiKlField, MiMcmcSampler, coefficient!, klfield_stats, MiFullAssembly, jacobi_refresh!
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -412,6 +412,54 @@ end
 function assemble!(values::Vector{Float64}, p::AssemblyPlan, a::Vector{Float64})
   check(ccall((:mi_assembly_run, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), p.h, a, values)); values
 end
+# On-device FULL-system assembly (DESIGN §6k): the element loop of `update_isotropic_elliptic_assembly!`
+# (Fem/EllipticPde.jl:291-377) for a new coefficient vector, into the device operator of A_mat. `MiFullAssembly(ctx, A_mat,
+# cells, points, point_marker, f, u_exact)` prepares the row-owned index plan ONCE (A_mat: the matrix of
+# `do_isotropic_elliptic_assembly`, for its pattern; it is symmetric, so its CSC arrays are the CSR arrays the library takes);
+# per realization `update_isotropic_elliptic_assembly!(A_op, plan, b_vec, coeff)` then replaces the reference's call. The
+# handle is the library's `mi_plan_t`, freed by `mi_assembly_plan_destroy` like an `AssemblyPlan`'s.
+mutable struct MiFullAssembly
+  h::Ptr{Cvoid}; n_node::Int; n::Int; nnz::Int; ctx
+end
+function MiFullAssembly(ctx::MiContext, A_mat::SparseMatrixCSC{Float64,Int}, cells::Array{Int,2}, points::Array{Float64,2},
+                        point_marker::Array{Int,2}, f::Function, u_exact::Function)
+  nel, n_node = size(cells, 2), size(points, 2)
+  ue, be = Matrix{Float64}(undef, nel, 3), Matrix{Float64}(undef, nel, 3)   # nel x 3 column-major: the library's 3 x nel rows
+  for iel in 1:nel
+    c = cells[:, iel]
+    x, y = points[1, c], points[2, c]
+    Area = ((x[2] - x[1]) * (y[3] - y[1]) - (x[1] - x[3]) * (y[1] - y[2])) / 2.      # :331, Δx[3] Δy[2] - Δx[2] Δy[3]
+    for i in 1:3
+      j, k = mod1(i + 1, 3), mod1(i + 2, 3)
+      ue[iel, i] = u_exact(x[i], y[i])                                                # :357
+      be[iel, i] = (2 * f(x[i], y[i]) + f(x[j], y[j]) + f(x[k], y[k])) * Area / 12   # :371-373
+    end
+  end
+  h = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:mi_full_assembly_plan_create, lib), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Cint, Ptr{Float64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+        ctx.h, nel, n_node, permutedims(cells), 1, permutedims(points), Vector{Int64}(vec(point_marker)), A_mat.n,
+        Vector{Int64}(A_mat.colptr), Vector{Int64}(A_mat.rowval), ue, be, h))
+  p = MiFullAssembly(h[], n_node, A_mat.n, length(A_mat.nzval), ctx)
+  finalizer(q -> ccall((:mi_assembly_plan_destroy, lib), Cint, (Ptr{Cvoid},), q.h), p)
+  return p
+end
+"""`assemble!(values, b_vec, p::MiFullAssembly, coeff)`: `A_mat.nzval` and `b_vec` of the new realization, on the host."""
+function assemble!(values::Vector{Float64}, b_vec::Vector{Float64}, p::MiFullAssembly, coeff::Vector{Float64})
+  check(ccall((:mi_full_assembly_run, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), p.h, coeff, values, b_vec))
+  values, b_vec
+end
+"""`update_isotropic_elliptic_assembly!(A_op, p, b_vec, coeff)`: the reference's in-place update (EllipticPde.jl:291-377) with
+the device operator of A_mat and the plan in place of the mesh arguments: the new values go straight into `A_op` (its solve
+graphs stay valid), `b_vec` is overwritten."""
+function Fem.update_isotropic_elliptic_assembly!(A_op::MiOperator, p::MiFullAssembly, b_vec::Vector{Float64}, coeff::Vector{Float64})
+  check(ccall((:mi_full_assembly_update, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}), p.h, coeff, A_op.h, b_vec))
+  b_vec
+end
+"""`set_values!(A_op, nzval)`: new values on the pattern of `MiOperator(ctx, A)` (`mi_csr_set_values`)."""
+set_values!(A_op::MiOperator, nzval::Vector{Float64}) = check(ccall((:mi_csr_set_values, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), A_op.h, nzval))
+"""`jacobi_refresh!(M, A_op)`: `dinv = 1 ./ diag(A)` of the values `A_op` holds now, on the device (`mi_diag_set_from_csr`)."""
+jacobi_refresh!(M::MiOperator, A_op::MiOperator) = check(ccall((:mi_diag_set_from_csr, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), M.h, A_op.h))
 set_values!(S::MiOperator, ii, ig, gg) =
   check(ccall((:mi_schur_matfree_set_values, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
               S.h, ii === nothing ? C_NULL : ii, ig === nothing ? C_NULL : ig, gg === nothing ? C_NULL : gg))
