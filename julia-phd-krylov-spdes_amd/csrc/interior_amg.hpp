@@ -8,7 +8,8 @@
 // diagonal (an aggregate that holds nodes of two subdomains is refused), so M is a block-diagonal SPD operator and the
 // subdomains' CG iterations stay independent; the coarsest GEMV keeps to the columns of the row's own subdomain
 // (k_amg_coarse_dom), so that a right-hand side that is not finite in one subdomain does not reach the others.
-// The loop: operators.hpp InteriorCg (pl_op), kernels.hpp IcgZ. The partials of r'z come from the level-0 post-smoothing
+// The loop: operators.hpp InteriorCg (pl == ICG_PL_EXT), the EXT instantiations of kernels.hpp's k_icg_init / k_icg_start /
+// k_icg_update / k_icg_direction<IcgPl>. The partials of r'z come from the level-0 post-smoothing
 // launch (k_amg_post_dot) on row blocks cut at the subdomain boundaries — the row blocks of the interior CG's own SpMV.
 #pragma once
 #include "amg_setup.hpp"
@@ -85,12 +86,16 @@ inline void interior_amg_select(mi_ctx_s *c, InteriorCg &icg, int64_t nlevels, c
     }
   }
   AmgPlanOp *raw = P.get();
-  icg.select_pl(std::move(P), [raw](const double *r, double *z, double *part, const int *done) { raw->cycle(r, z, done, part); },
-                [raw](const double *a0) { raw->refresh(a0, "mi_schur_matfree_set_values"); }, q0, q1, nparts);
+  IcgExtPl e;
+  e.op = std::move(P);
+  e.cycle = [raw](const double *r, double *z, double *part, const int *done) { raw->cycle(r, z, done, part); };
+  e.refresh = [raw](const double *a0) { raw->refresh(a0, "mi_schur_matfree_set_values"); };
+  e.q0 = std::move(q0); e.q1 = std::move(q1); e.nparts = nparts;
+  icg.select(ICG_PL_EXT, std::move(e));
 }
 
 inline bool interior_amg_stats(const InteriorCg &icg, InteriorAmgStats *st) {
-  const AmgPlanOp *P = icg.pl_op ? dynamic_cast<const AmgPlanOp *>(icg.pl_op.get()) : nullptr;
+  const AmgPlanOp *P = icg.pl == ICG_PL_EXT ? dynamic_cast<const AmgPlanOp *>(icg.ext.op.get()) : nullptr;
   if (!P) return false;
   st->levels = P->nlev; st->coarse_n = P->nc;
   st->bytes_kept = P->kept + 8 * (int64_t)(icg.zv.n + icg.p_rzq.n) + 4 * (int64_t)(P->coarse_dom.n + icg.dom_q0.n + icg.dom_q1.n);

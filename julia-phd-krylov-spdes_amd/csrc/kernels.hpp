@@ -476,9 +476,18 @@ __global__ __launch_bounds__(NT) void k_csrfold_start(int n, int g_vec, SolverSt
 //         beta = residual^2 / prev_residual^2;  u = r + beta u;  c = A u
 //         alpha = residual^2 / (u'c);  x += alpha u;  r -= alpha c;  prev_residual = residual;  residual = ||r||
 // All local subdomains are solved at once on the block-diagonal A_II with per-subdomain scalars; row blocks never
-// straddle subdomains. One iteration = k_spmv_csr<0,true> (c = A u with the u'c partials) + k_icg_update +
-// k_icg_direction. Per-subdomain scalars are double-buffered (cur/nxt) so no launch reads what it writes;
+// straddle subdomains. One iteration = k_spmv_csr<0,true> (c = A u with the u'c partials) + k_icg_update<PL> +
+// k_icg_direction<PL>. Per-subdomain scalars are double-buffered (cur/nxt) so no launch reads what it writes;
 // a converged subdomain is frozen (its workgroups return), the others keep iterating.
+// The left preconditioner `Pl` of `cg(A, b; Pl, reltol)`: c = Pl \ r, rho = dot(c, r), beta = rho / rho_prev, u = c + beta u,
+// alpha = rho / u'c. The four kernels are instantiated per kind; the kind decides what is read, never a pointer that is NULL.
+enum IcgPl {
+  ICG_PL_NONE,  // z = r: rho = residual^2
+  ICG_PL_DIAG,  // z = dinv .* r, made where it is used
+  ICG_PL_EXT    // z = Pl \ r lies in memory as a vector over all subdomains, made by launches of the preconditioner's own
+                // between k_icg_update and k_icg_direction (the AMG V-cycle of the stacked A_II, interior_amg.hpp), which also
+                // leave partial sums of r'z, a fixed run of them per subdomain
+};
 // A "piece" of the interior CG's vector kernels: a run of rows of ONE subdomain inside one XCD's share of the SpMV row blocks
 struct IcgPiece {
   int lo, hi, dom, slot;  // rows [lo, hi) of subdomain dom; partial slot (consecutive within the subdomain)
@@ -493,12 +502,43 @@ struct IcgMeta {
   double *tol;
   int *done_cur, *done_nxt, *iters;
   int maxiter_cap;             // 0: maxiter = n_i of the subdomain
-  // `Pl` = Diagonal(A): c = Pl \ r, rho = dot(c, r), beta = rho / rho_prev, u = c + beta u, alpha = rho / u'c
-  const double *dinv;          // nullptr: unpreconditioned (rho = residual^2)
+  const double *dinv;          // 1 / diagonal of A; read by the DIAG instantiations only
   double *rho_cur, *rho_nxt;
-  double *p_rz;                // per-piece partials of r'z
+  double *p_rz;                // per-piece partials of r'z (DIAG)
   const int *dom_p0, *dom_p1;  // partial-slot range of every subdomain (pieces of the vector kernels)
+  // EXT only (nullptr otherwise)
+  const double *z;             // z = Pl \ r, all subdomains
+  const double *p_rzq;         // partials of r'z left by the preconditioner's launches
+  const int *dom_q0, *dom_q1;  // their range per subdomain, summed in icg_dom_sum's fixed order
+  // 1 once every subdomain has stopped: the `done` word of the SpMV and of the preconditioner's launches, so the rest of a
+  // graph replay returns at once. It is written by workgroup 0 of k_icg_update<EXT> from the flags the direction kernel of the
+  // iteration before left, i.e. never by the launch that reads it.
+  int *all_done;
+  int ndl;
 };
+// `while residual > tol`: a NaN residual ends the solve where it stands (at x = 0 when the right-hand side holds it)
+__device__ __forceinline__ bool icg_converged(double res, double tol) { return !(res > tol); }
+// `while residual > tol && iteration < maxiter`: the one stop rule of the 3-launch and the 2-launch form
+__device__ __forceinline__ bool icg_stop(double res, double tol, int it, int maxiter) { return icg_converged(res, tol) || it >= maxiter; }
+// the scalars of subdomain d when a solve starts: residual = ||b||, rho, tol = reltol * residual, flags
+__device__ __forceinline__ void icg_dom_start(const IcgMeta &m, int d, double res, double rho, double reltol) {
+  m.res_cur[d] = res; m.res_nxt[d] = res;
+  m.rho_cur[d] = rho; m.rho_nxt[d] = rho;
+  m.tol[d] = reltol * res;
+  m.iters[d] = 0;
+  const int dn = icg_converged(res, m.tol[d]);
+  m.done_cur[d] = dn; m.done_nxt[d] = dn;
+}
+// ... and when an iteration ends: its count, the residual, rho (without `Pl` it is residual^2 and not kept), the stop test
+template <IcgPl PL>
+__device__ __forceinline__ void icg_dom_next(const IcgMeta &m, int d, double res, double rho, const int *__restrict__ n_i) {
+  const int it = m.iters[d] + 1;
+  m.iters[d] = it;
+  m.res_nxt[d] = res;
+  if constexpr (PL != ICG_PL_NONE) m.rho_nxt[d] = rho;
+  const int maxiter = m.maxiter_cap > 0 ? m.maxiter_cap : n_i[d];
+  m.done_nxt[d] = icg_stop(res, m.tol[d], it, maxiter);
+}
 __device__ __forceinline__ double icg_dom_sum(const double *part, int b0, int b1, double *sm) {
   double v = 0.0;
   for (int i0 = b0 + (int)threadIdx.x; i0 < b1; i0 += 8 * NT) {  // eight loads in flight per thread, added in order
@@ -513,83 +553,128 @@ __device__ __forceinline__ double icg_dom_sum(const double *part, int b0, int b1
 // The vector kernels work on "pieces" (IcgPiece: a run of ~2 000 rows of ONE subdomain inside one XCD's share of the SpMV
 // row blocks, ~512 workgroups in all, first rows requested ahead of the reduction) instead of one small workgroup per SpMV
 // row block (6 800 workgroups of ~146 rows at 1 M DoF, each a chain of round trips): 46 -> 41 us per iteration.
-// r = rhs; x = 0; u = z_0 (beta*0); partials of r'r (and r'z)
+// r = rhs; x = 0; u = z_0 (beta*0); partials of r'r (and r'z). EXT: z_0 = Pl \ b is not made yet, so u waits for k_icg_start;
+// all_done = 0 (the first z = Pl \ b always runs)
+template <IcgPl PL>
 __global__ __launch_bounds__(NT) void k_icg_init(IcgMeta m, const IcgPiece *__restrict__ pieces, const double *__restrict__ rhs,
                                                  double *__restrict__ x, double *__restrict__ r, double *__restrict__ u,
                                                  double *__restrict__ p_rr) {
   __shared__ double sm[NT / 64 + 1];
+  if constexpr (PL == ICG_PL_EXT)
+    if (blockIdx.x == 0 && threadIdx.x == 0) *m.all_done = 0;
   const IcgPiece pc = pieces[blockIdx.x];
   if (pc.hi <= pc.lo) return;
   double s = 0.0, sz = 0.0;
   for (int i = pc.lo + threadIdx.x; i < pc.hi; i += NT) {
     const double v = rhs[i];
-    const double z = m.dinv ? m.dinv[i] * v : v;
-    r[i] = v; u[i] = z; x[i] = 0.0;
+    r[i] = v; x[i] = 0.0;
     s += v * v;
-    sz += v * z;
+    if constexpr (PL == ICG_PL_NONE) u[i] = v;
+    if constexpr (PL == ICG_PL_DIAG) {
+      const double z = m.dinv[i] * v;
+      u[i] = z;
+      sz += v * z;
+    }
   }
   s = block_sum(s, sm);
-  if (m.dinv) sz = block_sum(sz, sm);
-  if (threadIdx.x == 0) { p_rr[pc.slot] = s; if (m.dinv) m.p_rz[pc.slot] = sz; }
-}
-// one workgroup per subdomain: residual = ||b||, tol = reltol*residual, flags
-__global__ __launch_bounds__(NT) void k_icg_start(IcgMeta m, const double *p_rr, double reltol) {
-  __shared__ double sm[NT / 64 + 1];
-  const int d = blockIdx.x;
-  const double rr = icg_dom_sum(p_rr, m.dom_p0[d], m.dom_p1[d], sm);
-  const double rz = m.dinv ? icg_dom_sum(m.p_rz, m.dom_p0[d], m.dom_p1[d], sm) : 0.0;
+  if constexpr (PL == ICG_PL_DIAG) sz = block_sum(sz, sm);
   if (threadIdx.x == 0) {
-    const double res = sqrt(rr);
-    m.res_cur[d] = res; m.res_nxt[d] = res;
-    const double rho = m.dinv ? rz : res * res;
-    m.rho_cur[d] = rho; m.rho_nxt[d] = rho;
-    m.tol[d] = reltol * res;
-    m.iters[d] = 0;
-    const int dn = !(res > m.tol[d]);   // `while residual > tol`: a NaN residual ends the solve at x = 0, as in k_icg_spmv
-    m.done_cur[d] = dn; m.done_nxt[d] = dn;
+    p_rr[pc.slot] = s;
+    if constexpr (PL == ICG_PL_DIAG) m.p_rz[pc.slot] = sz;
   }
 }
-// alpha = rho / (u'c); x += alpha u; r -= alpha c; partials of r'r (and r'z)
+// one workgroup per subdomain: residual = ||b||, rho, tol = reltol*residual, flags. EXT (after z_0 = Pl \ b): the grid is
+// npieces + ndl; workgroups [0, npieces): u = z_0 on the piece; workgroup npieces + d: subdomain d with rho = b'z_0
+template <IcgPl PL>
+__global__ __launch_bounds__(NT) void k_icg_start(IcgMeta m, const IcgPiece *__restrict__ pieces, const double *p_rr, double reltol,
+                                                  double *__restrict__ u, int npieces) {
+  __shared__ double sm[NT / 64 + 1];
+  int d = blockIdx.x;
+  if constexpr (PL == ICG_PL_EXT) {
+    if (d < npieces) {
+      const IcgPiece pc = pieces[d];
+      for (int i = pc.lo + threadIdx.x; i < pc.hi; i += NT) u[i] = m.z[i];
+      return;
+    }
+    d -= npieces;
+  }
+  const int p0 = m.dom_p0[d], p1 = m.dom_p1[d];
+  const double rr = icg_dom_sum(p_rr, p0, p1, sm);
+  double rz = 0.0;
+  // (DIAG sums the same range twice. An empty one sums to 0; leaving it out also keeps the second sum in a basic block of its
+  // own, as the run-time test of dinv used to: one VGPR fewer than with both sums in one block. k_icg_direction likewise.)
+  if constexpr (PL == ICG_PL_DIAG) { if (p1 > p0) rz = icg_dom_sum(m.p_rz, p0, p1, sm); }
+  if constexpr (PL == ICG_PL_EXT) rz = icg_dom_sum(m.p_rzq, m.dom_q0[d], m.dom_q1[d], sm);
+  if (threadIdx.x == 0) {
+    const double res = sqrt(rr);
+    icg_dom_start(m, d, res, PL == ICG_PL_NONE ? res * res : rz, reltol);
+  }
+}
+// alpha = rho / (u'c); x += alpha u; r -= alpha c; partials of r'r (DIAG: and r'z; EXT: r'z comes from the preconditioner's
+// launches, and workgroup 0 writes all_done)
+template <IcgPl PL>
 __global__ __launch_bounds__(NT) void k_icg_update(IcgMeta m, const IcgPiece *__restrict__ pieces, const double *__restrict__ p_uc,
                                                    const double *__restrict__ u, const double *__restrict__ c, double *__restrict__ x,
                                                    double *__restrict__ r, double *__restrict__ p_rr) {
   __shared__ double sm[NT / 64 + 1];
+  if constexpr (PL == ICG_PL_EXT) {
+    if (blockIdx.x == 0) {
+      int a = 1;
+      for (int i = threadIdx.x; i < m.ndl; i += NT) a &= m.done_nxt[i] != 0;
+      a = __syncthreads_and(a);
+      if (threadIdx.x == 0) *m.all_done = a;
+    }
+  }
   const IcgPiece pc = pieces[blockIdx.x];
   if (pc.hi <= pc.lo) return;
   const int d = pc.dom;
   const bool lead = pc.lead && threadIdx.x == 0;
   const int dn = m.done_nxt[d];
-  const double res = m.res_nxt[d], rho_n = m.rho_nxt[d];
+  const double res = m.res_nxt[d];
+  double rho = 0.0;
+  if constexpr (PL != ICG_PL_NONE) rho = m.rho_nxt[d];
   // the first four rows of this thread: requested together with the scalars, ahead of the reduction
-  double uv[4], cv[4], xv[4], rv[4], dv[4];
+  double uv[4], cv[4], xv[4], rv[4];
+  [[maybe_unused]] double dv[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int rw = pc.lo + k * NT + (int)threadIdx.x;
     const bool ok = rw < pc.hi;
     uv[k] = ok ? u[rw] : 0.0; cv[k] = ok ? c[rw] : 0.0; xv[k] = ok ? x[rw] : 0.0; rv[k] = ok ? r[rw] : 0.0;
-    dv[k] = ok && m.dinv ? m.dinv[rw] : 1.0;
+    if constexpr (PL == ICG_PL_DIAG) dv[k] = ok ? m.dinv[rw] : 1.0;
   }
   if (dn) { if (lead) m.done_cur[d] = 1; return; }
   const double uc = icg_dom_sum(p_uc, pc.b0, pc.b1, sm);
-  const double rho = m.dinv ? rho_n : res * res;
+  if constexpr (PL == ICG_PL_NONE) rho = res * res;
   const double alpha = rho / uc;
   double s = 0.0, sz = 0.0;
   for (int rw = pc.lo + (int)threadIdx.x, i = 0; rw < pc.hi; rw += NT, ++i) {
-    double u_, c_, x_, r_, d_;
-    if (i < 4) { u_ = uv[i]; c_ = cv[i]; x_ = xv[i]; r_ = rv[i]; d_ = dv[i]; }
-    else { u_ = u[rw]; c_ = c[rw]; x_ = x[rw]; r_ = r[rw]; d_ = m.dinv ? m.dinv[rw] : 1.0; }
+    double u_, c_, x_, r_;
+    [[maybe_unused]] double d_;
+    if (i < 4) {
+      u_ = uv[i]; c_ = cv[i]; x_ = xv[i]; r_ = rv[i];
+      if constexpr (PL == ICG_PL_DIAG) d_ = dv[i];
+    } else {
+      u_ = u[rw]; c_ = c[rw]; x_ = x[rw]; r_ = r[rw];
+      if constexpr (PL == ICG_PL_DIAG) d_ = m.dinv[rw];
+    }
     x[rw] = x_ + alpha * u_;
     const double ri = r_ - alpha * c_;
     r[rw] = ri;
     s += ri * ri;
-    if (m.dinv) sz += ri * (d_ * ri);
+    if constexpr (PL == ICG_PL_DIAG) sz += ri * (d_ * ri);
   }
   s = block_sum(s, sm);
-  if (m.dinv) sz = block_sum(sz, sm);
-  if (threadIdx.x == 0) { p_rr[pc.slot] = s; if (m.dinv) m.p_rz[pc.slot] = sz; }
+  if constexpr (PL == ICG_PL_DIAG) sz = block_sum(sz, sm);
+  if (threadIdx.x == 0) {
+    p_rr[pc.slot] = s;
+    if constexpr (PL == ICG_PL_DIAG) m.p_rz[pc.slot] = sz;
+  }
   if (lead) { m.res_cur[d] = res; m.rho_cur[d] = rho; m.done_cur[d] = 0; }
 }
-// residual = ||r||; beta = residual^2 / prev_residual^2 (rho / rho_prev with Pl); u = z + beta u; iteration count and stop test
+// residual = ||r||; beta = residual^2 / prev_residual^2 (rho / rho_prev with Pl, rho = r'z from the partials); u = z + beta u;
+// iteration count and stop test. `r` is read where z is made from it (NONE, DIAG)
+template <IcgPl PL>
 __global__ __launch_bounds__(NT) void k_icg_direction(IcgMeta m, const IcgPiece *__restrict__ pieces, const double *__restrict__ p_rr,
                                                       const double *__restrict__ r, double *__restrict__ u,
                                                       const int *__restrict__ n_i) {
@@ -598,167 +683,43 @@ __global__ __launch_bounds__(NT) void k_icg_direction(IcgMeta m, const IcgPiece 
   if (pc.hi <= pc.lo) return;
   const int d = pc.dom;
   const int dc = m.done_cur[d];
-  const double prev = m.res_cur[d], rho_c = m.rho_cur[d];
-  double rv[4], uv[4], dv[4];
+  [[maybe_unused]] const double prev = m.res_cur[d], rho_c = m.rho_cur[d];
+  const double *__restrict__ zr = PL == ICG_PL_EXT ? m.z : r;
+  int q0 = pc.p0, q1 = pc.p1;   // where the partials of r'z lie
+  if constexpr (PL == ICG_PL_EXT) { q0 = m.dom_q0[d]; q1 = m.dom_q1[d]; }
+  double zv[4], uv[4];
+  [[maybe_unused]] double dv[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int rw = pc.lo + k * NT + (int)threadIdx.x;
     const bool ok = rw < pc.hi;
-    rv[k] = ok ? r[rw] : 0.0; uv[k] = ok ? u[rw] : 0.0; dv[k] = ok && m.dinv ? m.dinv[rw] : 1.0;
+    zv[k] = ok ? zr[rw] : 0.0; uv[k] = ok ? u[rw] : 0.0;
+    if constexpr (PL == ICG_PL_DIAG) dv[k] = ok ? m.dinv[rw] : 1.0;
   }
   if (dc) return;
   const double rr = icg_dom_sum(p_rr, pc.p0, pc.p1, sm);
   const double res = sqrt(rr);
-  double beta = (res * res) / (prev * prev), rho = 0.0;
-  if (m.dinv) {
-    rho = icg_dom_sum(m.p_rz, pc.p0, pc.p1, sm);
+  double beta, rho = 0.0;
+  if constexpr (PL == ICG_PL_NONE) {
+    beta = (res * res) / (prev * prev);
+  } else {
+    if (q1 > q0) rho = icg_dom_sum(PL == ICG_PL_EXT ? m.p_rzq : m.p_rz, q0, q1, sm);   // (the test: see k_icg_start)
     beta = rho / rho_c;
   }
   for (int rw = pc.lo + (int)threadIdx.x, i = 0; rw < pc.hi; rw += NT, ++i) {
-    double r_, u_, d_;
-    if (i < 4) { r_ = rv[i]; u_ = uv[i]; d_ = dv[i]; }
-    else { r_ = r[rw]; u_ = u[rw]; d_ = m.dinv ? m.dinv[rw] : 1.0; }
-    u[rw] = (m.dinv ? d_ * r_ : r_) + beta * u_;
-  }
-  if (pc.lead && threadIdx.x == 0) {
-    const int it = m.iters[d] + 1;
-    m.iters[d] = it;
-    m.res_nxt[d] = res;
-    if (m.dinv) m.rho_nxt[d] = rho;
-    const int maxiter = m.maxiter_cap > 0 ? m.maxiter_cap : n_i[d];
-    m.done_nxt[d] = !(res > m.tol[d]) || (it >= maxiter);
-  }
-}
-
-// ---- `Pl` = a preconditioner applied by launches of its own between k_icg_update and the direction kernel (the AMG V-cycle
-// of the stacked A_II, interior_amg.hpp): z = Pl \ r lies in memory as a vector over all subdomains, and the launches that
-// make it also leave partial sums of r'z, a fixed run of them per subdomain. The recurrences are those of the diagonal `Pl`
-// above. `all_done` is 1 once every subdomain has stopped: the `done` word of the SpMV and of the preconditioner's launches,
-// so the rest of a graph replay returns at once. It is written by workgroup 0 of k_icg_update_z from the flags the direction
-// kernel of the iteration before left, i.e. never by the launch that reads it.
-struct IcgZ {
-  const double *z;        // z = Pl \ r, all subdomains
-  const double *p_rz;     // partials of r'z left by the preconditioner's launches
-  const int *q0, *q1;     // their range per subdomain, summed in icg_dom_sum's fixed order
-  int *all_done;
-  int ndl;
-};
-// r = rhs; x = 0; partials of r'r; all_done = 0 (the first z = Pl \ b always runs)
-__global__ __launch_bounds__(NT) void k_icg_init_z(IcgZ zz, const IcgPiece *__restrict__ pieces, const double *__restrict__ rhs,
-                                                   double *__restrict__ x, double *__restrict__ r, double *__restrict__ p_rr) {
-  __shared__ double sm[NT / 64 + 1];
-  if (blockIdx.x == 0 && threadIdx.x == 0) *zz.all_done = 0;
-  const IcgPiece pc = pieces[blockIdx.x];
-  if (pc.hi <= pc.lo) return;
-  double s = 0.0;
-  for (int i = pc.lo + threadIdx.x; i < pc.hi; i += NT) {
-    const double v = rhs[i];
-    r[i] = v; x[i] = 0.0;
-    s += v * v;
-  }
-  s = block_sum(s, sm);
-  if (threadIdx.x == 0) p_rr[pc.slot] = s;
-}
-// after z_0 = Pl \ b: workgroups [0, npieces): u = z_0 on the piece; workgroups npieces + d: the scalars of subdomain d
-// (residual = ||b||, rho = b'z_0, tol, flags), as k_icg_start
-__global__ __launch_bounds__(NT) void k_icg_start_z(IcgMeta m, IcgZ zz, int npieces, const IcgPiece *__restrict__ pieces,
-                                                    const double *p_rr, double reltol, double *__restrict__ u) {
-  __shared__ double sm[NT / 64 + 1];
-  if ((int)blockIdx.x < npieces) {
-    const IcgPiece pc = pieces[blockIdx.x];
-    for (int i = pc.lo + threadIdx.x; i < pc.hi; i += NT) u[i] = zz.z[i];
-    return;
-  }
-  const int d = (int)blockIdx.x - npieces;
-  const double rr = icg_dom_sum(p_rr, m.dom_p0[d], m.dom_p1[d], sm);
-  const double rz = icg_dom_sum(zz.p_rz, zz.q0[d], zz.q1[d], sm);
-  if (threadIdx.x == 0) {
-    const double res = sqrt(rr);
-    m.res_cur[d] = res; m.res_nxt[d] = res;
-    m.rho_cur[d] = rz; m.rho_nxt[d] = rz;
-    m.tol[d] = reltol * res;
-    m.iters[d] = 0;
-    const int dn = !(res > m.tol[d]);
-    m.done_cur[d] = dn; m.done_nxt[d] = dn;
-  }
-}
-// alpha = rho / (u'c); x += alpha u; r -= alpha c; partials of r'r (r'z comes from the preconditioner's launches)
-__global__ __launch_bounds__(NT) void k_icg_update_z(IcgMeta m, IcgZ zz, const IcgPiece *__restrict__ pieces, const double *__restrict__ p_uc,
-                                                     const double *__restrict__ u, const double *__restrict__ c, double *__restrict__ x,
-                                                     double *__restrict__ r, double *__restrict__ p_rr) {
-  __shared__ double sm[NT / 64 + 1];
-  if (blockIdx.x == 0) {
-    int a = 1;
-    for (int i = threadIdx.x; i < zz.ndl; i += NT) a &= m.done_nxt[i] != 0;
-    a = __syncthreads_and(a);
-    if (threadIdx.x == 0) *zz.all_done = a;
-  }
-  const IcgPiece pc = pieces[blockIdx.x];
-  if (pc.hi <= pc.lo) return;
-  const int d = pc.dom;
-  const bool lead = pc.lead && threadIdx.x == 0;
-  const int dn = m.done_nxt[d];
-  const double res = m.res_nxt[d], rho = m.rho_nxt[d];
-  double uv[4], cv[4], xv[4], rv[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int rw = pc.lo + k * NT + (int)threadIdx.x;
-    const bool ok = rw < pc.hi;
-    uv[k] = ok ? u[rw] : 0.0; cv[k] = ok ? c[rw] : 0.0; xv[k] = ok ? x[rw] : 0.0; rv[k] = ok ? r[rw] : 0.0;
-  }
-  if (dn) { if (lead) m.done_cur[d] = 1; return; }
-  const double uc = icg_dom_sum(p_uc, pc.b0, pc.b1, sm);
-  const double alpha = rho / uc;
-  double s = 0.0;
-  for (int rw = pc.lo + (int)threadIdx.x, i = 0; rw < pc.hi; rw += NT, ++i) {
-    double u_, c_, x_, r_;
-    if (i < 4) { u_ = uv[i]; c_ = cv[i]; x_ = xv[i]; r_ = rv[i]; }
-    else { u_ = u[rw]; c_ = c[rw]; x_ = x[rw]; r_ = r[rw]; }
-    x[rw] = x_ + alpha * u_;
-    const double ri = r_ - alpha * c_;
-    r[rw] = ri;
-    s += ri * ri;
-  }
-  s = block_sum(s, sm);
-  if (threadIdx.x == 0) p_rr[pc.slot] = s;
-  if (lead) { m.res_cur[d] = res; m.rho_cur[d] = rho; m.done_cur[d] = 0; }
-}
-// residual = ||r||; rho = r'z from the partials; beta = rho / rho_prev; u = z + beta u; iteration count and stop test
-__global__ __launch_bounds__(NT) void k_icg_direction_z(IcgMeta m, IcgZ zz, const IcgPiece *__restrict__ pieces, const double *__restrict__ p_rr,
-                                                        double *__restrict__ u, const int *__restrict__ n_i) {
-  __shared__ double sm[NT / 64 + 1];
-  const IcgPiece pc = pieces[blockIdx.x];
-  if (pc.hi <= pc.lo) return;
-  const int d = pc.dom;
-  const int dc = m.done_cur[d];
-  const double rho_c = m.rho_cur[d];
-  const int q0 = zz.q0[d], q1 = zz.q1[d];
-  double zv[4], uv[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int rw = pc.lo + k * NT + (int)threadIdx.x;
-    const bool ok = rw < pc.hi;
-    zv[k] = ok ? zz.z[rw] : 0.0; uv[k] = ok ? u[rw] : 0.0;
-  }
-  if (dc) return;
-  const double rr = icg_dom_sum(p_rr, pc.p0, pc.p1, sm);
-  const double res = sqrt(rr);
-  const double rho = icg_dom_sum(zz.p_rz, q0, q1, sm);
-  const double beta = rho / rho_c;
-  for (int rw = pc.lo + (int)threadIdx.x, i = 0; rw < pc.hi; rw += NT, ++i) {
     double z_, u_;
-    if (i < 4) { z_ = zv[i]; u_ = uv[i]; }
-    else { z_ = zz.z[rw]; u_ = u[rw]; }
-    u[rw] = z_ + beta * u_;
+    [[maybe_unused]] double d_;
+    if (i < 4) {
+      z_ = zv[i]; u_ = uv[i];
+      if constexpr (PL == ICG_PL_DIAG) d_ = dv[i];
+    } else {
+      z_ = zr[rw]; u_ = u[rw];
+      if constexpr (PL == ICG_PL_DIAG) d_ = m.dinv[rw];
+    }
+    if constexpr (PL == ICG_PL_DIAG) u[rw] = (d_ * z_) + beta * u_;
+    else u[rw] = z_ + beta * u_;
   }
-  if (pc.lead && threadIdx.x == 0) {
-    const int it = m.iters[d] + 1;
-    m.iters[d] = it;
-    m.res_nxt[d] = res;
-    m.rho_nxt[d] = rho;
-    const int maxiter = m.maxiter_cap > 0 ? m.maxiter_cap : n_i[d];
-    m.done_nxt[d] = !(res > m.tol[d]) || (it >= maxiter);
-  }
+  if (pc.lead && threadIdx.x == 0) icg_dom_next<PL>(m, d, res, rho, n_i);
 }
 
 // ---- the same interior CG in 2 launches per iteration (round 2): the config-2 loop above with per-subdomain scalars.
@@ -826,7 +787,7 @@ __global__ __launch_bounds__(NT, 8) void k_icg_spmv(int nblocks, IcgFold m, cons
   const double res = sqrt(rr);
   const double rho = m.dinv ? rz : res * res;          // IterativeSolvers: residual^2, resp. dot(c, r) with Pl
   const double tol = S.it == 0 ? m.reltol * res : S.tol;
-  const bool stop = !(res > tol) || S.it >= inf.maxit;  // `while residual > tol && iteration < maxiter`, maxiter = size(A, 2)
+  const bool stop = icg_stop(res, tol, S.it, inf.maxit);  // maxiter = size(A, 2)
   if (inf.lead && threadIdx.x == 0) {
     IcgDomState N;
     N.rho_prev = rho; N.tol = tol; N.res = res; N.it = S.it + (stop ? 0 : 1); N.done = stop;

@@ -1710,7 +1710,7 @@ int mi_schur_interior_precond(mi_op_t op, int kind) {
   if (kind != 0 && kind != 1) return fail(MI_ERR_BAD_ARG, "mi_schur_interior_precond: kind must be 0 (none) or 1 (diagonal)");
   return guarded([&]() -> int {
     op->impl->ctx->use();
-    icg->set_jacobi(kind == 1);
+    icg->select(kind == 1 ? ICG_PL_DIAG : ICG_PL_NONE);
     return MI_OK;
   });
 }

@@ -666,6 +666,14 @@ struct HostStage {
 };
 
 // ------------------------------------------------------------------ interior CG on the device (kernels.hpp, IcgMeta)
+// what InteriorCg needs of a `Pl` applied by launches of its own (ICG_PL_EXT)
+struct IcgExtPl {
+  std::unique_ptr<Operator> op;                                                 // owns the hierarchy
+  std::function<void(const double *, double *, double *, const int *)> cycle;   // z = Pl \ r with the partials of r'z
+  std::function<void(const double *)> refresh;   // the hierarchy for new device values of A_II; raises, keeps the old one
+  std::vector<int> q0, q1;                       // the partials of r'z of subdomain d are p_rzq[q0[d] .. q1[d])
+  size_t nparts = 0;
+};
 struct InteriorCg {
   mi_ctx_s *ctx = nullptr;
   CsrDev A;  // block-diagonal A_II of the local subdomains
@@ -691,15 +699,13 @@ struct InteriorCg {
   IcgDomState *dst_host = nullptr;
   std::vector<int> ioff_h;
   int npieces_grid = 0;
-  bool jacobi = false;       // `Pl` = Diagonal(A_II) (mi_schur_matfree_interior_precond)
-  // `Pl` = the AMG hierarchy of the stacked A_II (mi_schur_interior_amg; interior_amg.hpp fills these). While pl_op is set:
-  // the 3-launch loop with the z-kernels of kernels.hpp (IcgZ) whatever MI355_ICG_FUSED says, and a chunk of its own.
-  std::unique_ptr<Operator> pl_op;                                     // owns the hierarchy
-  std::function<void(const double *, double *, double *, const int *)> pl_cycle;   // z = Pl \ r with the partials of r'z
-  std::function<void(const double *)> pl_refresh;                      // the hierarchy for new device values of A_II; raises, keeps the old one
+  // The `Pl` selected, changed by select() alone: none, Diagonal(A_II) (mi_schur_interior_precond), or EXT = the AMG hierarchy
+  // of the stacked A_II (mi_schur_interior_amg; interior_amg.hpp makes what `ExtPl` holds). EXT has the 3-launch loop whatever
+  // MI355_ICG_FUSED says, and a chunk of its own.
+  IcgPl pl = ICG_PL_NONE;
+  IcgExtPl ext;   // empty unless pl == ICG_PL_EXT
   DevBuf<double> zv, p_rzq;
   DevBuf<int> dom_q0, dom_q1, all_done;
-  IcgZ zm{};
   int chunk_plain = 64, chunk_pl = ICG_CHUNK_PL;
   // iterations per replay with the AMG `Pl`: a solve takes 10 to 30 iterations; a replay costs one host wait (~16 us), an
   // iteration launched after all subdomains have stopped ~40 us of empty launches. Tried 2 / 4 / 8 / 16 / 32 at config 3:
@@ -731,8 +737,6 @@ struct InteriorCg {
     chunk_pl = std::max(1, env_int("MI355_ICG_CHUNK", ICG_CHUNK_PL));
     chunk = chunk_plain;
     rho.alloc(2 * (size_t)ndl + 2); part_rz.alloc((size_t)A.nblocks + 1);
-    meta = IcgMeta{A.blk.p, blk_dom.p, dom_b0.p, dom_b1.p, res_cur.p, res_nxt.p, tol.p, done_cur.p, done_nxt.p, iters.p, 0,
-                   nullptr, rho.p, rho.p + ndl + 1, part_rz.p, nullptr, nullptr};
     {  // 1 / diagonal of A_II (for the optional Jacobi `Pl`)
       std::vector<double> dg((size_t)n + 1, 1.0);
       for (int r_ = 0; r_ < a.n_rows; ++r_)
@@ -743,7 +747,8 @@ struct InteriorCg {
     folded = env_int("MI355_ICG_FUSED", 0) != 0;
     ioff_h = ioff;
     build_fold(a, b0, b1);   // the pieces serve both forms
-    meta.p_rz = part_rz.p; meta.dom_p0 = dom_p0.p; meta.dom_p1 = dom_p1.p;
+    meta = IcgMeta{A.blk.p, blk_dom.p, dom_b0.p, dom_b1.p, res_cur.p, res_nxt.p, tol.p, done_cur.p, done_nxt.p, iters.p, 0,
+                   dinv.p, rho.p, rho.p + ndl + 1, part_rz.p, dom_p0.p, dom_p1.p, nullptr, nullptr, nullptr, nullptr, nullptr, ndl};
   }
   // Pieces of the vector kernel: rows cut at subdomain boundaries and at the XCD boundaries of the SpMV's block dealing,
   // then into runs of <= `rows_per` rows; workgroup k works on XCD k & 7, so the pieces are interleaved per XCD.
@@ -813,83 +818,78 @@ struct InteriorCg {
   void drop_graph() {
     if (graph) { (void)hipGraphExecDestroy(graph); graph = nullptr; }
   }
-  // deselects the AMG `Pl` and releases its hierarchy (the stream is idle: every solve ends with a host synchronisation)
-  void drop_pl() {
-    if (!pl_op) return;
-    drop_graph();
-    pl_cycle = nullptr; pl_refresh = nullptr;
-    pl_op.reset();
+  // The one place that changes the `Pl`; `e` is what EXT needs. The stream is idle: every solve ends with a host
+  // synchronisation. NONE or DIAG selected again changes nothing.
+  void select(IcgPl kind, IcgExtPl e = {}) {
+    if (kind == pl && kind != ICG_PL_EXT) return;
+    drop_graph();   // the instantiations and their arguments are captured
     zv.release(); p_rzq.release(); dom_q0.release(); dom_q1.release(); all_done.release();
-    zm = IcgZ{};
-    chunk = chunk_plain;
+    ext = std::move(e);   // releases the previous hierarchy
+    if (kind == ICG_PL_EXT) {
+      hipStream_t s = ctx->stream;
+      zv.alloc((size_t)n + 1); p_rzq.alloc(ext.nparts + 1); all_done.alloc(1);
+      zv.zero(s); p_rzq.zero(s); all_done.zero(s);
+      dom_q0.upload(ext.q0, s); dom_q1.upload(ext.q1, s);
+    }
+    meta.z = zv.p; meta.p_rzq = p_rzq.p; meta.dom_q0 = dom_q0.p; meta.dom_q1 = dom_q1.p; meta.all_done = all_done.p;
+    fm.dinv = kind == ICG_PL_DIAG ? dinv.p : nullptr;   // the 2-launch kernels: nullptr is "no Pl"
+    chunk = kind == ICG_PL_EXT ? chunk_pl : chunk_plain;
+    pl = kind;
   }
-  // selects it: the partials of r'z of subdomain d are p_rzq[q0[d] .. q1[d])
-  void select_pl(std::unique_ptr<Operator> op, std::function<void(const double *, double *, double *, const int *)> cyc,
-                 std::function<void(const double *)> refresh, const std::vector<int> &q0, const std::vector<int> &q1, size_t nparts) {
-    drop_pl();
-    drop_graph();
-    set_jacobi(false);
-    hipStream_t s = ctx->stream;
-    zv.alloc((size_t)n + 1); p_rzq.alloc(nparts + 1); all_done.alloc(1);
-    zv.zero(s); p_rzq.zero(s); all_done.zero(s);
-    dom_q0.upload(q0, s); dom_q1.upload(q1, s);
-    zm = IcgZ{zv.p, p_rzq.p, dom_q0.p, dom_q1.p, all_done.p, ndl};
-    pl_op = std::move(op); pl_cycle = std::move(cyc); pl_refresh = std::move(refresh);
-    chunk = chunk_pl;
-  }
-  void set_jacobi(bool on) {
-    drop_pl();
-    if (on != jacobi) drop_graph();   // kernel arguments are captured
-    jacobi = on;
-    fm.dinv = on ? dinv.p : nullptr;
-    meta.dinv = on ? dinv.p : nullptr;
-  }
+  // 2 launches per iteration (MI355_ICG_FUSED=1), which EXT does not have
+  bool two_launch() const { return folded && pl != ICG_PL_EXT; }
   // after new values of A_II: 1 / diagonal again (device side)
   void refresh_diagonal() {
     if (n == 0) return;
     hipLaunchKernelGGL(k_csr_inv_diag, dim3((n + NT - 1) / NT), dim3(NT), 0, ctx->stream, n, A.rowptr.p, A.col.p, A.val.p, dinv.p);
     MI_HIP(hipGetLastError());
   }
+// LAUNCH(PL) with the instantiation of the `Pl` selected
+#define MI_ICG_PL_DISPATCH(LAUNCH)                        \
+  do {                                                    \
+    if (pl == ICG_PL_NONE) { LAUNCH(ICG_PL_NONE); }       \
+    else if (pl == ICG_PL_DIAG) { LAUNCH(ICG_PL_DIAG); }  \
+    else { LAUNCH(ICG_PL_EXT); }                          \
+    MI_HIP(hipGetLastError());                            \
+  } while (0)
+
   void iteration(double *x) {
     hipStream_t s = ctx->stream;
-    if (pl_op) {
-      A.launch(0, u.p, nullptr, c.p, all_done.p, s, u.p, p_uc.p);  // c = A u, partial u'c
-      hipLaunchKernelGGL(k_icg_update_z, dim3(npieces_grid), dim3(NT), 0, s, meta, zm, pieces.p, p_uc.p, u.p, c.p, x, r.p, p_rr.p);
-      MI_HIP(hipGetLastError());
-      pl_cycle(r.p, zv.p, p_rzq.p, all_done.p);
-      hipLaunchKernelGGL(k_icg_direction_z, dim3(npieces_grid), dim3(NT), 0, s, meta, zm, pieces.p, p_rr.p, u.p, n_i.p);
-      MI_HIP(hipGetLastError());
-      return;
-    }
-    if (folded) {
+    if (two_launch()) {
       const int grid = ((A.nblocks + 7) / 8) * 8;
       hipLaunchKernelGGL(k_icg_spmv, dim3(grid), dim3(NT), 0, s, A.nblocks, fm, A.rowptr.p, A.col.p, A.val.p);
       hipLaunchKernelGGL(k_icg_update_blk, dim3(npieces_grid), dim3(NT), 0, s, fm, pieces.p, x);
       MI_HIP(hipGetLastError());
       return;
     }
-    A.launch(0, u.p, nullptr, c.p, nullptr, s, u.p, p_uc.p);  // c = A u, partial u'c
-    hipLaunchKernelGGL(k_icg_update, dim3(npieces_grid), dim3(NT), 0, s, meta, pieces.p, p_uc.p, u.p, c.p, x, r.p, p_rr.p);
-    hipLaunchKernelGGL(k_icg_direction, dim3(npieces_grid), dim3(NT), 0, s, meta, pieces.p, p_rr.p, r.p, u.p, n_i.p);
-    MI_HIP(hipGetLastError());
+    const bool is_ext = pl == ICG_PL_EXT;
+    A.launch(0, u.p, nullptr, c.p, is_ext ? all_done.p : nullptr, s, u.p, p_uc.p);  // c = A u, partial u'c
+#define MI_CALL(PL) hipLaunchKernelGGL((k_icg_update<PL>), dim3(npieces_grid), dim3(NT), 0, s, meta, pieces.p, p_uc.p, u.p, c.p, x, r.p, p_rr.p)
+    MI_ICG_PL_DISPATCH(MI_CALL);
+#undef MI_CALL
+    if (is_ext) ext.cycle(r.p, zv.p, p_rzq.p, all_done.p);
+#define MI_CALL(PL) hipLaunchKernelGGL((k_icg_direction<PL>), dim3(npieces_grid), dim3(NT), 0, s, meta, pieces.p, p_rr.p, r.p, u.p, n_i.p)
+    MI_ICG_PL_DISPATCH(MI_CALL);
+#undef MI_CALL
   }
   // x = A_II^{-1} rhs for every local subdomain (device pointers), to the relative tolerance
   void solve(const double *rhs, double *x) {
     if (A.nblocks == 0) return;
     hipStream_t s = ctx->stream;
-    const bool folded = this->folded && !pl_op;   // the AMG `Pl` has the 3-launch form only
-    if (pl_op) {
-      hipLaunchKernelGGL(k_icg_init_z, dim3(npieces_grid), dim3(NT), 0, s, zm, pieces.p, rhs, x, r.p, p_rr.p);
-      MI_HIP(hipGetLastError());
-      pl_cycle(r.p, zv.p, p_rzq.p, nullptr);
-      hipLaunchKernelGGL(k_icg_start_z, dim3(npieces_grid + ndl), dim3(NT), 0, s, meta, zm, npieces_grid, pieces.p, p_rr.p, reltol, u.p);
-    } else if (folded) {
+    if (two_launch()) {
       hipLaunchKernelGGL(k_icg_fold_init, dim3(npieces_grid), dim3(NT), 0, s, fm, pieces.p, rhs, x);
+      MI_HIP(hipGetLastError());
     } else {
-      hipLaunchKernelGGL(k_icg_init, dim3(npieces_grid), dim3(NT), 0, s, meta, pieces.p, rhs, x, r.p, u.p, p_rr.p);
-      hipLaunchKernelGGL(k_icg_start, dim3(ndl), dim3(NT), 0, s, meta, p_rr.p, reltol);
+      const bool is_ext = pl == ICG_PL_EXT;
+      const int nstart = is_ext ? npieces_grid : 0;   // EXT: these workgroups of k_icg_start copy u = z_0
+#define MI_CALL(PL) hipLaunchKernelGGL((k_icg_init<PL>), dim3(npieces_grid), dim3(NT), 0, s, meta, pieces.p, rhs, x, r.p, u.p, p_rr.p)
+      MI_ICG_PL_DISPATCH(MI_CALL);
+#undef MI_CALL
+      if (is_ext) ext.cycle(r.p, zv.p, p_rzq.p, nullptr);
+#define MI_CALL(PL) hipLaunchKernelGGL((k_icg_start<PL>), dim3(nstart + ndl), dim3(NT), 0, s, meta, pieces.p, p_rr.p, reltol, u.p, nstart)
+      MI_ICG_PL_DISPATCH(MI_CALL);
+#undef MI_CALL
     }
-    MI_HIP(hipGetLastError());
     if (!graph || graph_x != x) {  // `chunk` iterations per replay
       drop_graph();
       graph = capture_graph(s, "", [&] { for (int k = 0; k < chunk; ++k) iteration(x); });
@@ -900,7 +900,7 @@ struct InteriorCg {
     bool all = false;
     for (long long l = 0; l <= max_replays; ++l) {
       all = true;
-      if (folded) {
+      if (two_launch()) {
         MI_HIP(hipMemcpyAsync(dst_host, dst.p, sizeof(IcgDomState) * ndl, hipMemcpyDeviceToHost, s));   // cur[]
         MI_HIP(hipStreamSynchronize(s));
         for (int d = 0; d < ndl; ++d) all = all && dst_host[d].done;
@@ -915,7 +915,7 @@ struct InteriorCg {
     }
     // k_icg_spmv meets the stop rule one launch after the iteration that reached it, so the 2-launch form may replay once
     // more than its iterations fill: count the replays the slowest subdomain's own iterations needed, like the 3-launch form
-    if (folded && all) {
+    if (two_launch() && all) {
       long long it_max = 0;
       for (int d = 0; d < ndl; ++d) it_max = std::max<long long>(it_max, dst_host[d].it);
       replays = std::min(replays, (it_max + chunk - 1) / chunk);
@@ -1068,7 +1068,7 @@ struct MatfreeSchurOp : InteriorSchurOp {
       if (!icg) raise(MI_ERR_BAD_ARG, "set_values: A_II lives in the interior-solve callback of this operator");
       // AMG `Pl`: its hierarchy first, from the caller's values. A refusal (MI_ERR_SINGULAR) leaves this call before anything of
       // the operator has changed: matrices, diagonal and hierarchy are those of the call before.
-      if (icg->pl_refresh) icg->pl_refresh(ii_val);
+      if (icg->pl == ICG_PL_EXT) icg->ext.refresh(ii_val);
       if (icg->A.nnz) MI_HIP(hipMemcpyAsync(icg->A.val.p, ii_val, sizeof(double) * icg->A.nnz, hipMemcpyDeviceToDevice, s));
       icg->refresh_diagonal();
     }

@@ -1,5 +1,5 @@
-"""GPU suite of `Pl` = AMG in the device interior CG (`mi_schur_interior_amg`; csrc/interior_amg.hpp, the z-kernels of
-csrc/kernels.hpp, k_amg_post_dot / k_amg_coarse_dom of csrc/amg.hpp), against the numpy restatement of
+"""GPU suite of `Pl` = AMG in the device interior CG (`mi_schur_interior_amg`; csrc/interior_amg.hpp, the ICG_PL_EXT
+instantiations of the k_icg_* kernels of csrc/kernels.hpp, k_amg_post_dot / k_amg_coarse_dom of csrc/amg.hpp), against the numpy restatement of
 tests/interior_amg_ref.py. The cases, their seeds and why an iteration count is comparable at all: that file and
 tests/test_interior_amg_cpu.py::test_counts_are_not_marginal.
 
