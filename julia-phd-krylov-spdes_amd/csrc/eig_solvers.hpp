@@ -30,7 +30,7 @@ struct EigKrylov {
   bool first_restart = true;
 
   EigKrylov(mi_ctx_s *c, Operator *A, Operator *M, EigKind kind_, int nvec_, int spdim_)
-      : k(c, A, M, (kind_ == EIGDEFCG || kind_ == EIGDEFPCG) ? nvec_ : 0, /*generic=*/kind_ == EIGDEFPCG, /*allow_fold=*/false),
+      : k(c, A, M, (kind_ == EIGDEFCG || kind_ == EIGDEFPCG) ? nvec_ : 0, /*generic=*/kind_ == EIGDEFPCG, /*recording=*/true),
         kind(kind_), nvec(nvec_),
         spdim(spdim_), pre(M != nullptr), deflated(kind_ == EIGDEFCG || kind_ == EIGDEFPCG), has_tvec(!deflated), ws(k.ws),
         s(c->stream), n(k.n), g(k.g) {}

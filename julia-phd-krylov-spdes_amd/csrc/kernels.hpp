@@ -50,6 +50,57 @@ struct SolveArgs {
   unsigned long long seq;
 };
 
+// ------------------------------------------------------------------ the loop's scalar rules, written once
+// k_spmv_pcg and k_gemv_pcg<., 0> (the first launch of the two-launch forms, solvers.hpp enum Loop) keep the same rules
+// written out: their instruction streams are held to the measured ones (profiles/NOTES.md). A change here goes there too.
+// beta = (1/old)*new (cg.jl:39,44 / 96,102): two roundings, as the reference's `beta = 1. / old; beta *= new`.
+__device__ __forceinline__ double krylov_beta(double old, double rz) {
+  double beta = 1. / old; beta *= rz; return beta;
+}
+// The stop rule after iteration `it_new` (cg.jl:34,91). over: the reference's `res_norm[it] = ...` throws BoundsError there and
+// the loop ends. The negated form stops on a NaN residual.
+struct StopRule { bool over, stop; };
+__device__ __forceinline__ StopRule krylov_stop(long long it_new, long long maxit, long long cap, double res, double tol) {
+  const bool over = it_new > cap;
+  return StopRule{over, over || !((it_new < maxit) && (res > tol))};
+}
+// ... and its stores, by the one thread that writes the state block (GENERIC, FUSED: the counter is `it`).
+__device__ __forceinline__ void krylov_count(SolverState *st, double *res_norm, long long it_new, double res, StopRule s) {
+  if (!s.over) res_norm[it_new - 1] = res; else st->overflow = 1;
+  st->it = it_new; st->done = s.stop;
+}
+// Start at it = 1 (GENERIC, FUSED; cg.jl:26-33 / 81-89): res_norm[1] and the stop rule. rTr and bnorm are the caller's.
+__device__ __forceinline__ void krylov_start_one(SolverState *st, double *res_norm, double rr, double rz, double tol, long long maxit, long long cap) {
+  st->rTz = rz; st->rTr_prev = rr; st->rTz_prev = rz; st->tol = tol;
+  st->d = 0.0; st->alpha = 0.0; st->beta = 0.0; st->overflow = 0;
+  const double res = sqrt(rr);
+  krylov_count(st, res_norm, 1, res, krylov_stop(1, maxit, cap, res, tol));
+}
+// Start at it = 0 (the two-launch forms): the first launch of the loop counts to 1, stores res_norm[1], applies the stop rule. The folded
+// loop passes (rTz, rTr_prev) = (0, r'r); the sparse one (r'z, 1): without M its first beta is r'r / rTr_prev, times p = 0, and 1 / r'r can be Inf.
+__device__ __forceinline__ void krylov_start_zero(SolverState *st, double rr, double bb, double eps, double rTz, double rTr_prev) {
+  st->rTr = rr; st->bnorm = sqrt(bb); st->tol = eps * st->bnorm;
+  st->it = 0; st->it_nxt = 0; st->done = 0; st->overflow = 0;
+  st->rTz = rTz; st->rTz_prev = 1.0; st->rTr_prev = rTr_prev;
+  st->d = 0.0; st->alpha = 0.0; st->beta = 0.0;
+}
+// Entry of a whole-solve graph: the pinned argument block, read with system-scope loads into `a` (LDS) by every workgroup.
+__device__ __forceinline__ unsigned long long sys_load_u64(const void *p) { return __hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+constexpr unsigned SOLVE_ARGS_WORDS = sizeof(SolveArgs) / 8;
+static_assert(sizeof(SolveArgs) % 8 == 0 && SOLVE_ARGS_WORDS <= 64, "SolveArgs is a block of 8-byte fields");
+__device__ __forceinline__ const SolveArgs &load_solve_args(const SolveArgs *pin, unsigned long long *a) {
+  if (threadIdx.x < SOLVE_ARGS_WORDS) a[threadIdx.x] = sys_load_u64((const unsigned long long *)pin + threadIdx.x);
+  __syncthreads();
+  return *reinterpret_cast<const SolveArgs *>(a);
+}
+// Hand-over of a whole-solve graph, by one thread: the flags, a release to system scope, then ONE store of the solve number.
+__device__ __forceinline__ void publish_flags(PinnedFlags *fl, long long it, int done, int overflow, int respec, int x0z, bool stamp_exit, unsigned long long seq) {
+  fl->it = it; fl->done = done; fl->overflow = overflow; fl->respec = respec; fl->x0z = x0z;
+  if (stamp_exit) fl->t_exit = wall_clock64();
+  __threadfence_system();
+  __hip_atomic_store(&fl->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // ------------------------------------------------------------------ reductions
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -460,10 +511,7 @@ __global__ __launch_bounds__(NT) void k_csrfold_start(int n, int g_vec, SolverSt
     const double rz = part_rz_in ? sum_partials(part_rz_in, g_in, sm) : rr;
     if (threadIdx.x == 0) {
       part_rr[0] = rr; part_rz[0] = rz;
-      st->rTr = rr; st->rTz = rz; st->rTr_prev = 1.0; st->rTz_prev = 1.0;
-      st->bnorm = sqrt(bb); st->tol = eps * st->bnorm;
-      st->it = 0; st->it_nxt = 0; st->done = 0; st->overflow = 0;
-      st->d = 0.0; st->alpha = 0.0; st->beta = 0.0;
+      krylov_start_zero(st, rr, bb, eps, rz, 1.0);
     }
   }
 }
@@ -1721,13 +1769,7 @@ __global__ __launch_bounds__(NT) void k_fold_start(SolverState *st, const double
   const double eps = st->eps;
   const double rr = sum_partials(part_rr, g, sm);
   const double bb = sum_partials(part_bb, g, sm);
-  if (threadIdx.x == 0) {
-    st->rTr = rr; st->bnorm = sqrt(bb);
-    st->tol = eps * st->bnorm;
-    st->it = 0; st->it_nxt = 0; st->done = 0; st->overflow = 0;
-    st->rTz = 0.0; st->rTz_prev = 1.0; st->rTr_prev = rr;
-    st->d = 0.0; st->alpha = 0.0; st->beta = 0.0;
-  }
+  if (threadIdx.x == 0) krylov_start_zero(st, rr, bb, eps, 0.0, rr);
 }
 // Set-up: it = 1; res_norm[1] = sqrt(r'r); tol = eps*norm2(b) (cg.jl:26-32 / 81-89). eps, maxit and
 // res_cap were written into the state block by the host.
@@ -1740,15 +1782,8 @@ __global__ __launch_bounds__(NT) void k_init_state(SolverState *st, const double
   const double bb = sum_partials(part_bb, g, sm);
   const double rz = part_rz ? sum_partials(part_rz, g, sm) : rr;
   if (threadIdx.x == 0) {
-    st->rTr = rr; st->rTz = rz; st->rTr_prev = rr; st->rTz_prev = rz;
-    st->bnorm = sqrt(bb);
-    st->tol = eps * st->bnorm;
-    st->it = 1;
-    st->d = 0.0; st->alpha = 0.0; st->beta = 0.0;
-    const double res = sqrt(rr);
-    st->overflow = 0;
-    if (res_cap >= 1) res_norm[0] = res; else st->overflow = 1;
-    st->done = !((1 < maxit) && (res > st->tol));
+    st->rTr = rr; st->bnorm = sqrt(bb);
+    krylov_start_one(st, res_norm, rr, rz, eps * st->bnorm, maxit, res_cap);
   }
 }
 // Loop step 1:  d = p'Ap (from partials); alpha = num/d; x += alpha p; r -= alpha Ap; partial r'r.
@@ -1839,8 +1874,7 @@ __global__ __launch_bounds__(NT) void k_update_p(int n, SolverState *st, const d
   const double rr = sum_partials(part_rr, g_in, sm);
   const double rz = precond ? sum_partials(part_rz, g_in, sm) : rr;
   const double old = precond ? st->rTz_prev : st->rTr_prev;
-  double beta = 1. / old;
-  beta *= rz;
+  const double beta = krylov_beta(old, rz);
   for (;;) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -1858,11 +1892,8 @@ __global__ __launch_bounds__(NT) void k_update_p(int n, SolverState *st, const d
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     st->rTr = rr; st->rTz = rz; st->beta = beta;
     const long long it = st->it + 1;
-    st->it = it;
     const double res = sqrt(rr);
-    const bool over = it > st->res_cap;  // the reference's `res_norm[it] = ...` throws BoundsError here: stop
-    if (!over) res_norm[it - 1] = res; else st->overflow = 1;
-    st->done = over || !((it < st->maxit) && (res > st->tol));
+    krylov_count(st, res_norm, it, res, krylov_stop(it, st->maxit, st->res_cap, res, st->tol));
   }
 }
 // Entry and exit of a solve, one launch each instead of a handful of small copies (each a separate blit on the stream):
@@ -1883,17 +1914,11 @@ __global__ __launch_bounds__(NT) void k_solve_begin(int n, const double *__restr
 // The same entry / exit pair as graph nodes: arguments through the pinned block instead of kernel parameters, and the
 // exit kernel ends with a release of everything it wrote followed by ONE store of the solve number, which is what the
 // host waits for (no stream synchronisation on the critical path of a solve).
-__device__ __forceinline__ unsigned long long sys_load_u64(const void *p) {
-  return __hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 __global__ __launch_bounds__(NT) void k_solve_begin_g(int n, const SolveArgs *pin, double *__restrict__ b, double *__restrict__ x,
                                                       SolverState *st, SolveArgs *dev, PinnedFlags *flags) {
-  __shared__ unsigned long long a[sizeof(SolveArgs) / 8];
+  __shared__ unsigned long long a[SOLVE_ARGS_WORDS];
   if (blockIdx.x == 0 && threadIdx.x == 0) flags->t_entry = wall_clock64();
-  static_assert(sizeof(SolveArgs) % 8 == 0 && sizeof(SolveArgs) / 8 <= 64, "SolveArgs is a block of 8-byte fields");
-  if (threadIdx.x < sizeof(SolveArgs) / 8) a[threadIdx.x] = sys_load_u64((const unsigned long long *)pin + threadIdx.x);
-  __syncthreads();
-  const SolveArgs &q = *reinterpret_cast<const SolveArgs *>(a);
+  const SolveArgs &q = load_solve_args(pin, a);
   const double *b_in = q.b_in, *x_in = q.x_in;
   int nz = 0;
   for (int i = blockIdx.x * NT + threadIdx.x; i < n; i += gridDim.x * NT) {
@@ -1903,7 +1928,7 @@ __global__ __launch_bounds__(NT) void k_solve_begin_g(int n, const SolveArgs *pi
   }
   if (__syncthreads_or(nz) && threadIdx.x == 0) st->x0_zero = 0;
   if (blockIdx.x == 0) {
-    if (threadIdx.x < sizeof(SolveArgs) / 8) ((unsigned long long *)dev)[threadIdx.x] = a[threadIdx.x];
+    if (threadIdx.x < SOLVE_ARGS_WORDS) ((unsigned long long *)dev)[threadIdx.x] = a[threadIdx.x];
     if (threadIdx.x == 0) { st->eps = q.eps; st->maxit = q.maxit; st->res_cap = q.res_cap; st->done = 0; }
   }
 }
@@ -1930,11 +1955,9 @@ __global__ __launch_bounds__(NT) void k_solve_end_g(int n, SolverState *st, cons
   __syncthreads();
   if (last && threadIdx.x == 0) {
     *end_count = 0;
-    flags->it = it; flags->done = st->done; flags->overflow = st->overflow; flags->respec = 0; flags->x0z = *x0_zero;
-    flags->t_exit = wall_clock64();
+    const int x0z = *x0_zero;
     *x0_zero = 1;
-    __threadfence_system();
-    __hip_atomic_store(&flags->seq, q.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_flags(flags, it, st->done, st->overflow, 0, x0z, true, q.seq);
   }
 }
 // out: x -> caller's vector (device), `it` / done / overflow and the first min(it, ncap) residual norms -> pinned host memory.
@@ -2218,8 +2241,7 @@ __global__ __launch_bounds__(NTF) void k_fused_p(int n, SolverState *st, AsmView
   }
   const double rz = precond ? block_sum_f(s, sm) : rr;
   if (!precond) __syncthreads();  // mu_s visible (block_sum_f has barriers of its own)
-  double beta = 1. / old;
-  beta *= rz;
+  const double beta = krylov_beta(old, rz);
   double wm[EPT];
 #pragma unroll
   for (int k = 0; k < EPT; ++k) wm[k] = 0.0;
@@ -2255,11 +2277,8 @@ __global__ __launch_bounds__(NTF) void k_fused_p(int n, SolverState *st, AsmView
   __syncthreads();
   if (threadIdx.x == 0) {
     st->rTz = rz; st->beta = beta;
-    const long long it = it0 + 1;
-    st->it = it;
     const double res = sqrt(rr);
-    if (it <= cap) res_norm[it - 1] = res; else st->overflow = 1;
-    st->done = it > cap || !((it < maxit) && (res > tol));  // it > cap: BoundsError in the reference, the loop ends there
+    krylov_count(st, res_norm, it0 + 1, res, krylov_stop(it0 + 1, maxit, cap, res, tol));
   }
 }
 // Unpreconditioned cg (cg.jl:35-47): both halves of the iteration in ONE single-workgroup launch — z is r,
@@ -2298,8 +2317,7 @@ __global__ __launch_bounds__(NTF) void k_fused_cg(int n, SolverState *st, AsmVie
     }
   }
   const double rr = block_sum_f(srr, sm);
-  double beta = 1. / rTr0;
-  beta *= rr;
+  const double beta = krylov_beta(rTr0, rr);
 #pragma unroll
   for (int k = 0; k < EPT; ++k) {
     const int e = k * NTF + threadIdx.x;
@@ -2309,11 +2327,8 @@ __global__ __launch_bounds__(NTF) void k_fused_cg(int n, SolverState *st, AsmVie
     st->d = d; st->alpha = alpha; st->beta = beta;
     st->rTr_prev = rTr0; st->rTz_prev = rTr0;
     st->rTr = rr; st->rTz = rr;
-    const long long it = it0 + 1;
-    st->it = it;
     const double res = sqrt(rr);
-    if (it <= cap) res_norm[it - 1] = res; else st->overflow = 1;
-    st->done = it > cap || !((it < maxit) && (res > tol));  // it > cap: BoundsError in the reference, the loop ends there
+    krylov_count(st, res_norm, it0 + 1, res, krylov_stop(it0 + 1, maxit, cap, res, tol));
   }
 }
 
@@ -2340,13 +2355,8 @@ __global__ __launch_bounds__(NTF) void k_fused_residual(int n, SolverState *st, 
   srr = block_sum_f(srr, sm);
   sbb = block_sum_f(sbb, sm);
   if (threadIdx.x == 0) {
-    st->rTr = srr; st->bnorm = sqrt(sbb);
-    if (FOLD) {
-      st->tol = eps * st->bnorm;
-      st->it = 0; st->it_nxt = 0; st->done = 0; st->overflow = 0;
-      st->rTz = 0.0; st->rTz_prev = 1.0; st->rTr_prev = srr;
-      st->d = 0.0; st->alpha = 0.0; st->beta = 0.0;
-    }
+    if (FOLD) krylov_start_zero(st, srr, sbb, eps, 0.0, srr);
+    else { st->rTr = srr; st->bnorm = sqrt(sbb); }
   }
 }
 // Entry of a whole-solve graph of the folded loop that was built for x0 == 0 (the usual call, `pcg(S, b, zeros, M)`): the
@@ -2357,12 +2367,10 @@ __global__ __launch_bounds__(NTF) void k_fused_residual(int n, SolverState *st, 
 template <int EPT>
 __global__ __launch_bounds__(NTF) void k_entry_zero(int n, const SolveArgs *pin, double *__restrict__ b, double *__restrict__ x,
                                                     double *__restrict__ r, SolverState *st, SolveArgs *dev, PinnedFlags *flags) {
-  __shared__ unsigned long long a[sizeof(SolveArgs) / 8];
+  __shared__ unsigned long long a[SOLVE_ARGS_WORDS];
   __shared__ double sm[NTF / 64 + 1];
   if (threadIdx.x == 0) flags->t_entry = wall_clock64();
-  if (threadIdx.x < sizeof(SolveArgs) / 8) a[threadIdx.x] = sys_load_u64((const unsigned long long *)pin + threadIdx.x);
-  __syncthreads();
-  const SolveArgs &q = *reinterpret_cast<const SolveArgs *>(a);
+  const SolveArgs &q = load_solve_args(pin, a);
   const double *b_in = q.b_in, *x_in = q.x_in;
   double bv[EPT], xv[EPT];
   int nz = 0;
@@ -2373,13 +2381,11 @@ __global__ __launch_bounds__(NTF) void k_entry_zero(int n, const SolveArgs *pin,
     if (e < n) { bv[k] = b_in[e]; xv[k] = x_in[e]; nz |= xv[k] != 0.0; }
   }
   nz = __syncthreads_or(nz);
-  if (threadIdx.x < sizeof(SolveArgs) / 8) ((unsigned long long *)dev)[threadIdx.x] = a[threadIdx.x];
+  if (threadIdx.x < SOLVE_ARGS_WORDS) ((unsigned long long *)dev)[threadIdx.x] = a[threadIdx.x];
   if (nz) {
     if (threadIdx.x == 0) {
       st->done = 1; st->x0_zero = 0;
-      flags->it = 0; flags->done = 0; flags->overflow = 0; flags->respec = 1; flags->x0z = 0;
-      __threadfence_system();
-      __hip_atomic_store(&flags->seq, q.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      publish_flags(flags, 0, 0, 0, 1, 0, false, q.seq);
     }
     return;
   }
@@ -2399,11 +2405,7 @@ __global__ __launch_bounds__(NTF) void k_entry_zero(int n, const SolveArgs *pin,
   sbb = block_sum_f(sbb, sm);
   if (threadIdx.x == 0) {
     st->eps = q.eps; st->maxit = q.maxit; st->res_cap = q.res_cap; st->x0_zero = 1;
-    st->rTr = srr; st->bnorm = sqrt(sbb);
-    st->tol = q.eps * st->bnorm;
-    st->it = 0; st->it_nxt = 0; st->done = 0; st->overflow = 0;
-    st->rTz = 0.0; st->rTz_prev = 1.0; st->rTr_prev = srr;
-    st->d = 0.0; st->alpha = 0.0; st->beta = 0.0;
+    krylov_start_zero(st, srr, sbb, q.eps, 0.0, srr);
   }
 }
 // Set-up, second half: z = view; r'z; p = z; it = 1; res_norm[1]; tol; stop rule (cg.jl:26-33 / 81-89).
@@ -2426,17 +2428,7 @@ __global__ __launch_bounds__(NTF) void k_fused_start(int n, SolverState *st, Asm
     }
   }
   const double rz = precond ? block_sum_f(s, sm) : rr;
-  if (threadIdx.x == 0) {
-    st->rTz = rz; st->rTr_prev = rr; st->rTz_prev = rz;
-    const double tol = eps * bnorm;
-    st->tol = tol;
-    st->it = 1;
-    st->d = 0.0; st->alpha = 0.0; st->beta = 0.0;
-    const double res = sqrt(rr);
-    st->overflow = 0;
-    if (cap >= 1) res_norm[0] = res; else st->overflow = 1;
-    st->done = !((1 < maxit) && (res > tol));
-  }
+  if (threadIdx.x == 0) krylov_start_one(st, res_norm, rr, rz, eps * bnorm, maxit, cap);
 }
 
 // Set-up of the deflated solvers: p = z - W mu (defcg.jl:61 / 285); plain copy when nvec == 0.

@@ -29,7 +29,7 @@ constexpr int CF_VEC_GRID = 256;  // workgroups of the vector half of the 2-laun
 struct GraphKey {
   const Operator *A, *M;
   int nvec, chunk;  // chunk > 0: that many iterations; chunk < 0: set-up + (-chunk) iterations
-  int tag = 0;      // 4*(0: cg/pcg/defcg/defpcg; eigCG family: 1 + kind + 8*spdim) + loop form (fused, folded)
+  int tag = 0;      // whatever else decides the launches of a graph, set by Krylov::graph (0 in the keys of `predicted` / `zero_x0`)
   bool operator<(const GraphKey &o) const {
     return std::tie(A, M, nvec, chunk, tag) < std::tie(o.A, o.M, o.nvec, o.chunk, o.tag);
   }
@@ -119,15 +119,10 @@ struct SolverWorkspace {
     graphs.clear();
   }
   void drop_graphs_of(const Operator *op) {
-    for (auto it = graphs.begin(); it != graphs.end();)
-      if (it->first.A == op || it->first.M == op) { (void)hipGraphExecDestroy(it->second); it = graphs.erase(it); }
-      else ++it;
-    for (auto it = predicted.begin(); it != predicted.end();)
-      if (it->first.A == op || it->first.M == op) it = predicted.erase(it);
-      else ++it;
-    for (auto it = zero_x0.begin(); it != zero_x0.end();)
-      if (it->first.A == op || it->first.M == op) it = zero_x0.erase(it);
-      else ++it;
+    auto of_op = [op](const GraphKey &k) { return k.A == op || k.M == op; };
+    for (auto &kv : graphs) if (of_op(kv.first)) (void)hipGraphExecDestroy(kv.second);
+    auto erase_of = [&](auto &map) { for (auto it = map.begin(); it != map.end();) it = of_op(it->first) ? map.erase(it) : std::next(it); };
+    erase_of(graphs); erase_of(predicted); erase_of(zero_x0);
   }
   void ensure_deflation(int nvec) {
     if (nvec <= nvec_cap) return;
@@ -180,18 +175,25 @@ inline int host_lu(int n, std::vector<double> &a, std::vector<int> &piv) {
   return 0;
 }
 
+// The form of the loop: which kernels make one iteration. Exclusive, chosen once per solver by Krylov::select_form (table: DESIGN §3).
+// GENERIC: multi-workgroup vector kernels around plain applies. FUSED: n <= FUSED_MAX_N, single-workgroup vector kernels over slot views. FOLD:
+// pcg, both operators dense on the same maps, the vector work inside the two GEMVs; FOLD_BIG: the same beyond FUSED_MAX_N. CSRFOLD: cg / diagonal pcg on a CSR matrix.
+enum class Loop { GENERIC, FUSED, FOLD, FOLD_BIG, CSRFOLD };
+
 struct Krylov {
   mi_ctx_s *ctx;
   Operator *A, *M;  // M == nullptr: unpreconditioned (z is r)
+  const int pre;    // M != nullptr
   SolverWorkspace &ws;
   int nvec;
   int n, g;
   hipStream_t s;
-  bool fused;  // single-workgroup loop kernels (small Γ systems)
-  bool fold;   // pcg with both operators dense on the same maps: vector work folded into the two GEMVs
-  CsrDev *Ac = nullptr;  // cg / pcg with a diagonal M on a plain sparse matrix: the 2-launch loop (k_spmv_pcg, k_update_xr_blk)
-  bool csrfold() const { return Ac != nullptr && !eig.tag; }
-  DenseBlockOp *Ad = nullptr, *Md = nullptr;
+  Loop form = Loop::GENERIC;
+  CsrDev *Ac = nullptr;                        // CSRFOLD: A
+  DenseBlockOp *Ad = nullptr, *Md = nullptr;   // FOLD, FOLD_BIG: A and M
+  bool two_launch() const { return form == Loop::FOLD || form == Loop::FOLD_BIG || form == Loop::CSRFOLD; }  // the host reads it_nxt
+  bool folded() const { return form == Loop::FOLD || form == Loop::FOLD_BIG; }
+  bool single_wg() const { return form == Loop::FUSED || form == Loop::FOLD; }  // the single-workgroup kernels leave z, Ap as slot views
   int capture_whole = 0;  // while a whole-solve graph is being captured: 1 general entry, 2 entry for x0 == 0 (folded loop)
   // eigCG family: recording kernels after every iteration (eig_solvers.hpp fills this in)
   struct EigHook {
@@ -201,18 +203,23 @@ struct Krylov {
   } eig;
   std::vector<double> gram_host;  // WtAW as computed (before LU), kept for VtAV[1:nvec,1:nvec] (defcg.jl:158 / 391)
 
-  Krylov(mi_ctx_s *c, Operator *A_, Operator *M_, int nvec_, bool generic = false, bool allow_fold = true)
-      : ctx(c), A(A_), M(M_), ws(workspace(c, A_->n)), nvec(nvec_), n((int)A_->n), g(ws.g), s(c->stream),
-        fused(!generic && A_->n <= FUSED_MAX_N && !env_int("MI355_NO_FUSED", 0)), fold(false) {
+  // generic: GENERIC whatever the size. recording: the eigCG family reads z and Ap after every iteration, so no two-launch form.
+  Krylov(mi_ctx_s *c, Operator *A_, Operator *M_, int nvec_, bool generic = false, bool recording = false)
+      : ctx(c), A(A_), M(M_), pre(M_ != nullptr), ws(workspace(c, A_->n)), nvec(nvec_), n((int)A_->n), g(ws.g), s(c->stream) {
+    select_form(generic, recording);
+  }
+  void select_form(bool generic, bool recording) {
+    const bool fused = !generic && A->n <= FUSED_MAX_N && !env_int("MI355_NO_FUSED", 0);
+    form = fused ? Loop::FUSED : Loop::GENERIC;
     // (the folded launches themselves are multi-workgroup: beyond FUSED_MAX_N only the start-up differs — the
     // reference's own partitions, 80-500 subdomains, have n_Γ of 10-40 k; undeflated solves only there)
-    const bool big_fold = !fused && !generic && nvec_ == 0 && !env_int("MI355_NO_FUSED", 0) && !env_int("MI355_NO_BIG_FOLD", 0);
-    if ((fused || big_fold) && allow_fold && M && nvec <= 64 && !env_int("MI355_NO_FOLD", 0) && !(nvec > 0 && env_int("MI355_NO_FOLD_DEFL", 0))) {
+    const bool big_fold = !fused && !generic && nvec == 0 && !env_int("MI355_NO_FUSED", 0) && !env_int("MI355_NO_BIG_FOLD", 0);
+    if ((fused || big_fold) && !recording && M && nvec <= 64 && !env_int("MI355_NO_FOLD", 0) && !(nvec > 0 && env_int("MI355_NO_FOLD_DEFL", 0))) {
       Ad = A->as_dense(); Md = M->as_dense();
       // multi-GPU: S may be sharded (built on the maps of all subdomains, inactive tiles for the other ranks' blocks)
       // while the Neumann-Neumann blocks are replicated: the S launch is then followed by one all-reduce
       // ... or sharded as well (both on the maps of all subdomains): then the ΠS launch is followed by an exchange too
-      fold = Ad && Md && (!Ad->reduce_over_ranks || (Ad->full_maps && nvec == 0)) &&
+      const bool fold = Ad && Md && (!Ad->reduce_over_ranks || (Ad->full_maps && nvec == 0)) &&
              (!Md->reduce_over_ranks || (Md->full_maps && Md->fold_p1_off && nvec == 0 && !env_int("MI355_NO_FOLD_SHARDED_NN", 0))) &&
              !Ad->scale && Md->scale && Ad->same_maps(*Md) && Ad->ntiles > 0 && Ad->max_ld <= GEMV_PANEL && Md->max_ld <= GEMV_PANEL &&
              Ad->maps.slot_width <= 4 &&
@@ -220,15 +227,16 @@ struct Krylov {
              // fp32 ΠS takes the unfolded loop (plain applies + all-reduce) — its launch has no peer-exchange form
              !(Md->f32() && Md->reduce_over_ranks) &&
              (Ad->max_ld + 64 * Ad->waves - 1) / (64 * Ad->waves) <= 8 && (Md->max_ld + 64 * Md->waves - 1) / (64 * Md->waves) <= 8;
+      if (fold) form = fused ? Loop::FOLD : Loop::FOLD_BIG;
     }
     const double *dv = nullptr;
-    if (!fused && nvec == 0 && A->as_csr() && A->as_csr()->nblocks > 0 && (!M || M->diag_kind(&dv) != 0) && !env_int("MI355_NO_CSRFOLD", 0))
-      Ac = A->as_csr();
+    if (form == Loop::GENERIC && !recording && nvec == 0 && A->as_csr() && A->as_csr()->nblocks > 0 && (!M || M->diag_kind(&dv) != 0) &&
+        !env_int("MI355_NO_CSRFOLD", 0)) { Ac = A->as_csr(); form = Loop::CSRFOLD; }
   }
   // peer exchange with the waits inside the launches: every sharded operator of the loop stores into the arenas itself
   bool inwait() const {
     // (an fp32-stored ΠS launch cannot wait inside itself: the one-wave wait kernel runs behind the S launch instead)
-    return fold && !Md->f32() && ctx->peer_inwait && ctx->use_peer() && (Ad->reduce_over_ranks || Md->reduce_over_ranks) &&
+    return folded() && !Md->f32() && ctx->peer_inwait && ctx->use_peer() && (Ad->reduce_over_ranks || Md->reduce_over_ranks) &&
            (!Ad->reduce_over_ranks || (Ad->xt_on() && Ad->xt_direct)) && (!Md->reduce_over_ranks || (Md->xt_on() && Md->xt_direct));
   }
   PcgFold fold_args(int phase) const {
@@ -282,12 +290,11 @@ struct Krylov {
   // loop, plain vectors in the multi-workgroup one
   AsmView z_view() const {
     if (!M) return AsmView{ws.r, 0};
-    return fused && nvec == 0 ? M->view_of(ws.z) : AsmView{ws.z, 0};
+    return single_wg() && nvec == 0 ? M->view_of(ws.z) : AsmView{ws.z, 0};
   }
-  AsmView Ap_view() const { return fused ? A->view_of(ws.Ap) : AsmView{ws.Ap, 0}; }
+  AsmView Ap_view() const { return single_wg() ? A->view_of(ws.Ap) : AsmView{ws.Ap, 0}; }
   // Lanczos bookkeeping of the eigCG family for the iteration just enqueued
   void eig_record() {
-    const int pre = M != nullptr;
     double *tv = eig.has_tvec ? ws.etvec.p : nullptr;
     hipLaunchKernelGGL(k_eig_vec, dim3(g), dim3(NT), 0, s, n, ws.st, ws.ees.p, pre, eig.spdim, z_view(), Ap_view(), ws.eV.p, tv);
     if (eig.has_tvec)
@@ -298,84 +305,84 @@ struct Krylov {
     MI_HIP(hipGetLastError());
   }
 
-#define MI_EPT_DISPATCH(CALL)            \
-  do {                                   \
-    if (n <= NTF) { CALL(1); }           \
-    else if (n <= 2 * NTF) { CALL(2); }  \
-    else if (n <= 4 * NTF) { CALL(4); }  \
-    else { CALL(8); }                    \
-  } while (0)
-
+  // launch(std::integral_constant<int, EPT>): the single-workgroup kernels are instantiated per elements per thread, 1, 2, 4 or 8
+  template <class F>
+  void with_ept(F launch) const {
+    if (n <= NTF) launch(std::integral_constant<int, 1>{});
+    else if (n <= 2 * NTF) launch(std::integral_constant<int, 2>{});
+    else if (n <= 4 * NTF) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, 8>{});
+  }
   // One loop iteration (cg.jl:35-47 / 92-106; defcg.jl:68-80 / 291-305), enqueued on the stream.
   void iteration() {
-    const int *dn = done();
-    const int pre = M != nullptr;
-    const double *Wp = nvec > 0 ? ws.W.p : nullptr, *mup = nvec > 0 ? ws.mu.p : nullptr;
-    if (fold) {
-      // 2 launches per iteration: (alpha, x, r, z, r'z, r'r) in the ΠS GEMV; (stop rule, beta, p, Ap, p'Ap) in the S GEMV
-      Md->gemv_pcg(1, fold_args(1));
-      if (Md->reduce_over_ranks) Md->reduce_fold(dn, inwait());  // ΠS contributions + partial r'r, r'z: union over the ranks
-      if (nvec > 0) {  // mu = WtAW \ (WtA * z); W*mu in local order for the S launch (defcg.jl:301-303)
-        hipLaunchKernelGGL(k_defl_mu, dim3((Ad->maps.nloc + 1023) / 1024), dim3(1024), 0, s, ws.st, nvec, Md->ntiles, ws.fold_mu.p,
-                           ws.LU.p, ws.piv.p, Ad->maps.nloc, Ad->maps.gidx.p, ws.W.p, (long long)n, ws.fold_wm.p, ws.mu.p, ws.fold_wloc.p);
-        MI_HIP(hipGetLastError());
-      }
-      Ad->gemv_pcg(0, fold_args(0));
-      if (Ad->reduce_over_ranks) Ad->reduce_fold(dn, inwait());  // S contributions + partial p'Ap: union over the ranks
-      return;
+    switch (form) {
+      case Loop::FOLD: case Loop::FOLD_BIG: return iter_fold();
+      case Loop::FUSED: return iter_fused();
+      case Loop::CSRFOLD: return iter_csrfold();
+      case Loop::GENERIC: return iter_generic();
     }
-    if (fused) {
-      // small Γ systems: 4 launches per iteration (GEMV, fused, GEMV, fused)
-      const AsmView vAp = A->apply_view(ws.p, ws.Ap, dn);             // mul!(Ap, A, p), Γ-sum deferred
-      if (!pre && nvec == 0) {                                        // cg: 2 launches per iteration
-#define MI_CALL(E) hipLaunchKernelGGL((k_fused_cg<E>), dim3(1), dim3(NTF), 0, s, n, ws.st, vAp, ws.p, ws.x, ws.r, ws.res_norm.p)
-        MI_EPT_DISPATCH(MI_CALL);
-#undef MI_CALL
-        if (eig.tag) eig_record();
-        MI_HIP(hipGetLastError());
-        return;
-      }
-#define MI_CALL(E) hipLaunchKernelGGL((k_fused_xr<E>), dim3(1), dim3(NTF), 0, s, n, ws.st, vAp, ws.p, ws.x, ws.r, pre)
-      MI_EPT_DISPATCH(MI_CALL);                                       // alpha; x += alpha p; r -= alpha Ap; r'r
-#undef MI_CALL
-      AsmView vz{ws.r, 0};
-      if (pre) vz = M->apply_view(ws.r, ws.z, dn);                    // z .= M \ r, Γ-sum deferred
-      const bool wave_lu = nvec > 0 && nvec <= 64;                    // mu solved inside k_fused_p by one wave
-      if (wave_lu) {
-#define MI_CALL(E) hipLaunchKernelGGL((k_multi_dot_view<E>), dim3(nvec), dim3(NTF), 0, s, n, ws.AW.p, vz, ws.part_mu.p, dn)
-        MI_EPT_DISPATCH(MI_CALL);                                     // WtA * z
-#undef MI_CALL
-      } else if (nvec > 0) {
-        if (vz.width) {  // materialise z for the generic projection kernels
-          hipLaunchKernelGGL(k_assemble_slots, dim3(vec_grid(n)), dim3(NT), 0, s, n, vz.width, vz.src, ws.z, dn);
-          vz = AsmView{ws.z, 0};
-        }
-        project(ws.AW.p, vz.src, dn);                                 // mu .= WtAW \ (WtA * z)
-      }
-      const double *lup = wave_lu ? ws.LU.p : nullptr;
-      const int *pivp = wave_lu ? ws.piv.p : nullptr;
-#define MI_CALL(E) hipLaunchKernelGGL((k_fused_p<E>), dim3(1), dim3(NTF), 0, s, n, ws.st, vz, ws.r, ws.p, Wp, mup, nvec, ws.res_norm.p, pre, lup, pivp, ws.part_mu.p)
-      MI_EPT_DISPATCH(MI_CALL);                                       // beta; [mu;] p; it += 1; res_norm[it]; stop rule
-#undef MI_CALL
+  }
+  // 2 launches per iteration: (alpha, x, r, z, r'z, r'r) in the ΠS GEMV; (stop rule, beta, p, Ap, p'Ap) in the S GEMV
+  void iter_fold() {
+    const int *dn = done();
+    Md->gemv_pcg(1, fold_args(1));
+    if (Md->reduce_over_ranks) Md->reduce_fold(dn, inwait());  // ΠS contributions + partial r'r, r'z: union over the ranks
+    if (nvec > 0) {  // mu = WtAW \ (WtA * z); W*mu in local order for the S launch (defcg.jl:301-303)
+      hipLaunchKernelGGL(k_defl_mu, dim3((Ad->maps.nloc + 1023) / 1024), dim3(1024), 0, s, ws.st, nvec, Md->ntiles, ws.fold_mu.p,
+                         ws.LU.p, ws.piv.p, Ad->maps.nloc, Ad->maps.gidx.p, ws.W.p, (long long)n, ws.fold_wm.p, ws.mu.p, ws.fold_wloc.p);
+      MI_HIP(hipGetLastError());
+    }
+    Ad->gemv_pcg(0, fold_args(0));
+    if (Ad->reduce_over_ranks) Ad->reduce_fold(dn, inwait());  // S contributions + partial p'Ap: union over the ranks
+  }
+  // small Γ systems: 4 launches per iteration (GEMV, fused, GEMV, fused)
+  void iter_fused() {
+    const int *dn = done();
+    const double *Wp = nvec > 0 ? ws.W.p : nullptr, *mup = nvec > 0 ? ws.mu.p : nullptr;
+    const AsmView vAp = A->apply_view(ws.p, ws.Ap, dn);             // mul!(Ap, A, p), Γ-sum deferred
+    if (!pre && nvec == 0) {                                        // cg: 2 launches per iteration
+      with_ept([&](auto E) { hipLaunchKernelGGL((k_fused_cg<E()>), dim3(1), dim3(NTF), 0, s, n, ws.st, vAp, ws.p, ws.x, ws.r, ws.res_norm.p); });
       if (eig.tag) eig_record();
       MI_HIP(hipGetLastError());
       return;
     }
-    if (csrfold()) {
-      // sparse A, diagonal or no M: 2 launches per iteration (kernels.hpp, "pcg on a sparse matrix in 2 launches")
-      const double *dinv = nullptr;
-      const int diag = pre ? M->diag_kind(&dinv) : 0;
-      const int grid = ((Ac->nblocks + 7) / 8) * 8;
-      double *pz0 = ws.cf_pz.p, *pz1 = pz0 + 2 * (size_t)n;
-      CsrOp *co = static_cast<CsrOp *>(A);
-      hipLaunchKernelGGL(k_spmv_pcg, dim3(grid), dim3(NT), 0, s, Ac->nblocks, pre, Ac->blk.p, ws.st, ws.cf_rr.p, ws.cf_rz.p, CF_VEC_GRID,
-                         Ac->rowptr.p, Ac->col.p, Ac->val.p, pz0, pz1, ws.Ap, co->dot_part.p, ws.res_norm.p);
-      hipLaunchKernelGGL(k_update_xr_blk, dim3(CF_VEC_GRID), dim3(NT), 0, s, Ac->xcd_row.p, ws.st, co->dot_part.p, Ac->nblocks, pz0,
-                         pz1, ws.Ap, ws.x, ws.r, dinv, diag, pre, ws.cf_rr.p, ws.cf_rz.p);
-      MI_HIP(hipGetLastError());
-      return;
+    // alpha; x += alpha p; r -= alpha Ap; r'r
+    with_ept([&](auto E) { hipLaunchKernelGGL((k_fused_xr<E()>), dim3(1), dim3(NTF), 0, s, n, ws.st, vAp, ws.p, ws.x, ws.r, pre); });
+    AsmView vz{ws.r, 0};
+    if (pre) vz = M->apply_view(ws.r, ws.z, dn);                    // z .= M \ r, Γ-sum deferred
+    const bool wave_lu = nvec > 0 && nvec <= 64;                    // mu solved inside k_fused_p by one wave
+    if (wave_lu) {  // WtA * z
+      with_ept([&](auto E) { hipLaunchKernelGGL((k_multi_dot_view<E()>), dim3(nvec), dim3(NTF), 0, s, n, ws.AW.p, vz, ws.part_mu.p, dn); });
+    } else if (nvec > 0) {
+      if (vz.width) {  // materialise z for the generic projection kernels
+        hipLaunchKernelGGL(k_assemble_slots, dim3(vec_grid(n)), dim3(NT), 0, s, n, vz.width, vz.src, ws.z, dn);
+        vz = AsmView{ws.z, 0};
+      }
+      project(ws.AW.p, vz.src, dn);                                 // mu .= WtAW \ (WtA * z)
     }
-    // large systems (full A): SpMV with the p'Ap partials in its epilogue; r-update with a diagonal M folded in
+    const double *lup = wave_lu ? ws.LU.p : nullptr; const int *pivp = wave_lu ? ws.piv.p : nullptr;
+    // beta; [mu;] p; it += 1; res_norm[it]; stop rule
+    with_ept([&](auto E) { hipLaunchKernelGGL((k_fused_p<E()>), dim3(1), dim3(NTF), 0, s, n, ws.st, vz, ws.r, ws.p, Wp, mup, nvec, ws.res_norm.p, pre, lup, pivp, ws.part_mu.p); });
+    if (eig.tag) eig_record();
+    MI_HIP(hipGetLastError());
+  }
+  // sparse A, diagonal or no M: 2 launches per iteration (kernels.hpp, "pcg on a sparse matrix in 2 launches")
+  void iter_csrfold() {
+    const double *dinv = nullptr;
+    const int diag = pre ? M->diag_kind(&dinv) : 0;
+    const int grid = ((Ac->nblocks + 7) / 8) * 8;
+    double *pz0 = ws.cf_pz.p, *pz1 = pz0 + 2 * (size_t)n;
+    CsrOp *co = static_cast<CsrOp *>(A);
+    hipLaunchKernelGGL(k_spmv_pcg, dim3(grid), dim3(NT), 0, s, Ac->nblocks, pre, Ac->blk.p, ws.st, ws.cf_rr.p, ws.cf_rz.p, CF_VEC_GRID,
+                       Ac->rowptr.p, Ac->col.p, Ac->val.p, pz0, pz1, ws.Ap, co->dot_part.p, ws.res_norm.p);
+    hipLaunchKernelGGL(k_update_xr_blk, dim3(CF_VEC_GRID), dim3(NT), 0, s, Ac->xcd_row.p, ws.st, co->dot_part.p, Ac->nblocks, pz0,
+                       pz1, ws.Ap, ws.x, ws.r, dinv, diag, pre, ws.cf_rr.p, ws.cf_rz.p);
+    MI_HIP(hipGetLastError());
+  }
+  // large systems (full A): SpMV with the p'Ap partials in its epilogue; r-update with a diagonal M folded in
+  void iter_generic() {
+    const int *dn = done();
+    const double *Wp = nvec > 0 ? ws.W.p : nullptr, *mup = nvec > 0 ? ws.mu.p : nullptr;
     const double *part = ws.part_pAp;
     int npart = g;
     if (!A->apply_dot(ws.p, ws.Ap, ws.p, &part, &npart, dn)) {       // mul!(Ap, A, p); d = dot(p, Ap)
@@ -409,58 +416,60 @@ struct Krylov {
   // r = b - A x; z = M \ r; p = z [- W mu]; it = 1; res_norm[1]; tol (cg.jl:26-33 / 81-89; defcg.jl:56-66 / 277-288).
   // eps / maxit / res_cap are read from the state block (uploaded by solve()), so this is graph-replayable.
   void setup_tail() {
-    const int pre = M != nullptr;
-    struct Hint {  // `A*x0` may skip streaming A when the device flag says x0 == 0 (k_solve_begin)
-      Operator *op;
-      Hint(Operator *o, const int *flag) : op(o) { op->zero_hint = flag; }
-      ~Hint() { op->zero_hint = nullptr; }
-    };
-    if (fold && !fused) {   // n_Γ > FUSED_MAX_N: multi-workgroup residual, then the scalars of the folded loop
-      { Hint h(A, &ws.st->x0_zero); A->apply(ws.x, ws.Ap, nullptr); }
-      hipLaunchKernelGGL(k_residual, dim3(g), dim3(NT), 0, s, n, ws.b, ws.Ap, ws.r, ws.part_rr, ws.part_bb);
-      hipLaunchKernelGGL(k_fold_start, dim3(1), dim3(NT), 0, s, ws.st, ws.part_rr, ws.part_bb, g);
-      MI_HIP(hipGetLastError());
-      if (inwait()) ctx->peer->begin_inwait(s);
-      return;
+    switch (form) {
+      case Loop::FOLD_BIG: return start_fold_big();
+      case Loop::FOLD: return start_fold();
+      case Loop::FUSED: return nvec == 0 ? start_fused() : start_generic();  // (the deflated set-up has multi-workgroup kernels only)
+      case Loop::CSRFOLD: return start_csrfold();
+      case Loop::GENERIC: return start_generic();
     }
-    if (fold) {
-      AsmView vAp;
-      { Hint h(A, nvec == 0 ? &ws.st->x0_zero : nullptr); vAp = A->apply_view(ws.x, ws.Ap, nullptr); }  // deflated: x0 was updated by W*mu
-#define MI_CALL(E) hipLaunchKernelGGL((k_fused_residual<E, true>), dim3(1), dim3(NTF), 0, s, n, ws.st, vAp, ws.b, ws.r)
-      MI_EPT_DISPATCH(MI_CALL);
-#undef MI_CALL
-      MI_HIP(hipGetLastError());
-      if (inwait()) ctx->peer->begin_inwait(s);
-      return;
-    }
-    if (fused && nvec == 0) {
-      AsmView vAp;
-      { Hint h(A, &ws.st->x0_zero); vAp = A->apply_view(ws.x, ws.Ap, nullptr); }
-#define MI_CALL(E) hipLaunchKernelGGL((k_fused_residual<E, false>), dim3(1), dim3(NTF), 0, s, n, ws.st, vAp, ws.b, ws.r)
-      MI_EPT_DISPATCH(MI_CALL);
-#undef MI_CALL
-      const AsmView vz = pre ? M->apply_view(ws.r, ws.z, nullptr) : AsmView{ws.r, 0};
-#define MI_CALL(E) hipLaunchKernelGGL((k_fused_start<E>), dim3(1), dim3(NTF), 0, s, n, ws.st, vz, ws.r, ws.p, ws.res_norm.p, pre)
-      MI_EPT_DISPATCH(MI_CALL);
-#undef MI_CALL
-      MI_HIP(hipGetLastError());
-      return;
-    }
+  }
+  struct Hint {  // `A*x0` may skip streaming A when the device flag says x0 == 0 (k_solve_begin)
+    Operator *op;
+    Hint(Operator *o, const int *flag) : op(o) { op->zero_hint = flag; }
+    ~Hint() { op->zero_hint = nullptr; }
+  };
+  void start_residual() {  // r = b - A x and the partials of r'r, b'b with the multi-workgroup kernels
     { Hint h(A, nvec == 0 ? &ws.st->x0_zero : nullptr); A->apply(ws.x, ws.Ap, nullptr); }  // deflated: x0 was updated by W*mu
     hipLaunchKernelGGL(k_residual, dim3(g), dim3(NT), 0, s, n, ws.b, ws.Ap, ws.r, ws.part_rr, ws.part_bb);
-    if (csrfold()) {
-      const double *dinv = nullptr;
-      const int diag = pre ? M->diag_kind(&dinv) : 0;
-      if (diag == 2) {
-        M->apply(ws.r, ws.z, nullptr);
-        dot_partial(ws.r, ws.z, ws.part_rz, nullptr);
-      }
-      hipLaunchKernelGGL(k_csrfold_start, dim3(g), dim3(NT), 0, s, n, CF_VEC_GRID, ws.st, ws.part_rr, ws.part_bb,
-                         diag == 2 ? ws.part_rz : (const double *)nullptr, g, diag == 2 ? ws.z : ws.r, ws.cf_pz.p, ws.cf_rr.p,
-                         ws.cf_rz.p);
-      MI_HIP(hipGetLastError());
-      return;
+  }
+  // n_Γ > FUSED_MAX_N (undeflated): multi-workgroup residual, then the scalars of the folded loop
+  void start_fold_big() {
+    start_residual();
+    hipLaunchKernelGGL(k_fold_start, dim3(1), dim3(NT), 0, s, ws.st, ws.part_rr, ws.part_bb, g);
+    MI_HIP(hipGetLastError());
+    if (inwait()) ctx->peer->begin_inwait(s);
+  }
+  void start_fold() {
+    AsmView vAp;
+    { Hint h(A, nvec == 0 ? &ws.st->x0_zero : nullptr); vAp = A->apply_view(ws.x, ws.Ap, nullptr); }  // deflated: x0 was updated by W*mu
+    with_ept([&](auto E) { hipLaunchKernelGGL((k_fused_residual<E(), true>), dim3(1), dim3(NTF), 0, s, n, ws.st, vAp, ws.b, ws.r); });
+    MI_HIP(hipGetLastError());
+    if (inwait()) ctx->peer->begin_inwait(s);
+  }
+  void start_fused() {
+    AsmView vAp;
+    { Hint h(A, &ws.st->x0_zero); vAp = A->apply_view(ws.x, ws.Ap, nullptr); }
+    with_ept([&](auto E) { hipLaunchKernelGGL((k_fused_residual<E(), false>), dim3(1), dim3(NTF), 0, s, n, ws.st, vAp, ws.b, ws.r); });
+    const AsmView vz = pre ? M->apply_view(ws.r, ws.z, nullptr) : AsmView{ws.r, 0};
+    with_ept([&](auto E) { hipLaunchKernelGGL((k_fused_start<E()>), dim3(1), dim3(NTF), 0, s, n, ws.st, vz, ws.r, ws.p, ws.res_norm.p, pre); });
+    MI_HIP(hipGetLastError());
+  }
+  void start_csrfold() {
+    start_residual();
+    const double *dinv = nullptr;
+    const int diag = pre ? M->diag_kind(&dinv) : 0;
+    if (diag == 2) {
+      M->apply(ws.r, ws.z, nullptr);
+      dot_partial(ws.r, ws.z, ws.part_rz, nullptr);
     }
+    hipLaunchKernelGGL(k_csrfold_start, dim3(g), dim3(NT), 0, s, n, CF_VEC_GRID, ws.st, ws.part_rr, ws.part_bb,
+                       diag == 2 ? ws.part_rz : (const double *)nullptr, g, diag == 2 ? ws.z : ws.r, ws.cf_pz.p, ws.cf_rr.p,
+                       ws.cf_rz.p);
+    MI_HIP(hipGetLastError());
+  }
+  void start_generic() {
+    start_residual();
     const double *zz = ws.r;
     if (pre) {
       M->apply(ws.r, ws.z, nullptr);
@@ -480,7 +489,8 @@ struct Krylov {
   // (Splitting a whole-solve graph into a short head and the rest, so that the GPU starts while the host still enqueues,
   // was measured: 432 vs 427 us per solve — one replay is cheaper than two.)
   hipGraphExec_t graph(int chunk, int whole = 0) {
-    GraphKey key{A, M, nvec, chunk, eig.tag * 8 + (fused ? 1 : 0) + (fold ? 2 : 0) + (csrfold() ? 4 : 0) + 1024 * whole};  // the loop form is part of the graph
+    // tag: the loop form (0 ... 4), the whole-solve entry (0: none, 1: general, 2: for x0 == 0), the eigCG family's recording (eig.tag)
+    GraphKey key{A, M, nvec, chunk, (int)form + 8 * (whole + 4 * eig.tag)};
     auto it = ws.graphs.find(key);
     if (it != ws.graphs.end()) return it->second;
     hipGraphExec_t ex = nullptr;
@@ -488,9 +498,7 @@ struct Krylov {
       ex = capture_graph(s, "", [&] {
         capture_whole = whole;
         if (whole == 2) {   // folded loop, x0 == 0: one entry launch
-#define MI_CALL(E) hipLaunchKernelGGL((k_entry_zero<E>), dim3(1), dim3(NTF), 0, s, n, ws.args, ws.b, ws.x, ws.r, ws.st, ws.args_dev.p, &ws.flags[0])
-          MI_EPT_DISPATCH(MI_CALL);
-#undef MI_CALL
+          with_ept([&](auto E) { hipLaunchKernelGGL((k_entry_zero<E()>), dim3(1), dim3(NTF), 0, s, n, ws.args, ws.b, ws.x, ws.r, ws.st, ws.args_dev.p, &ws.flags[0]); });
           MI_HIP(hipGetLastError());
         } else {
           if (whole) {
@@ -502,7 +510,7 @@ struct Krylov {
         for (int k = 0; k < std::abs(chunk); ++k) iteration();
         capture_whole = 0;
         if (whole) {
-          hipLaunchKernelGGL(k_solve_end_g, dim3(g), dim3(NT), 0, s, n, ws.st, ws.args_dev.p, (int)(fold || csrfold()), ws.x, ws.res_norm.p,
+          hipLaunchKernelGGL(k_solve_end_g, dim3(g), dim3(NT), 0, s, n, ws.st, ws.args_dev.p, (int)two_launch(), ws.x, ws.res_norm.p,
                              &ws.flags[0], &ws.st->x0_zero, ws.end_count.p);
           MI_HIP(hipGetLastError());
         }
@@ -531,7 +539,7 @@ struct Krylov {
   }
 
   void fetch_flags(int slot) {
-    MI_HIP(hipMemcpyAsync(&ws.flags[slot].it, (fold || csrfold()) ? &ws.st->it_nxt : &ws.st->it, sizeof(long long),
+    MI_HIP(hipMemcpyAsync(&ws.flags[slot].it, two_launch() ? &ws.st->it_nxt : &ws.st->it, sizeof(long long),
                           hipMemcpyDeviceToHost, s));
     MI_HIP(hipMemcpyAsync(&ws.flags[slot].done, &ws.st->done, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     MI_HIP(hipEventRecord(ws.ev[slot], s));
@@ -547,7 +555,7 @@ struct Krylov {
     MI_HIP(hipGetLastError());
     if (nvec > 0) {
       MI_HIP(hipMemcpyAsync(ws.W.p, W_in, vb * nvec, hipMemcpyDeviceToDevice, s));
-      if (fold) {
+      if (folded()) {
         hipLaunchKernelGGL(k_gather_w_loc, dim3((Ad->maps.nloc + NT - 1) / NT, nvec), dim3(NT), 0, s, nvec, (long long)n, Ad->maps.nloc,
                            Ad->maps.gidx.p, ws.W.p, ws.fold_wloc.p);
         MI_HIP(hipGetLastError());
@@ -573,7 +581,7 @@ struct Krylov {
     cap_dev = std::max<int64_t>(1, std::min<int64_t>(maxit, (int64_t)n));
     if ((size_t)cap_dev + 1 > ws.res_norm.n) { ws.drop_graphs(); ws.res_norm.alloc((size_t)cap_dev + 1); }
     if (nvec > 0) ws.ensure_deflation(nvec);
-    if (nvec > 0 && fold) {
+    if (nvec > 0 && folded()) {
       const size_t need_mu = (size_t)nvec * Md->ntiles + 1, need_wm = (size_t)Ad->maps.nloc + 1;
       const size_t need_wl = (size_t)nvec * Ad->maps.nloc + 1;
       if (ws.fold_mu.n < need_mu || ws.fold_wm.n < need_wm || ws.fold_wloc.n < need_wl) {
@@ -581,7 +589,7 @@ struct Krylov {
         ws.fold_mu.alloc(need_mu); ws.fold_wm.alloc(need_wm); ws.fold_wloc.alloc(need_wl);
       }
     }
-    if (csrfold()) {
+    if (form == Loop::CSRFOLD) {
       const size_t need_pz = 4 * (size_t)n + 2, need_p = (size_t)CF_VEC_GRID + 1;
       if (ws.cf_pz.n < need_pz || ws.cf_rr.n < need_p) {
         ws.drop_graphs();  // buffers move
@@ -624,7 +632,7 @@ struct Krylov {
     const int64_t ncap = std::min<int64_t>(res_cap, cap_dev);
     const bool spec_res = res_host && ncap > 0 && ncap <= RES_STAGE;
     auto enqueue_results = [&](int slot) {
-      hipLaunchKernelGGL(k_solve_end, dim3(g), dim3(NT), 0, s, n, ws.st, (int)(fold || csrfold()), ws.x, x_io, ws.res_norm.p,
+      hipLaunchKernelGGL(k_solve_end, dim3(g), dim3(NT), 0, s, n, ws.st, (int)two_launch(), ws.x, x_io, ws.res_norm.p,
                          spec_res ? ws.res_stage : (double *)nullptr, (long long)ncap, &ws.flags[slot], &ws.st->x0_zero);
       MI_HIP(hipGetLastError());
     };
@@ -638,7 +646,7 @@ struct Krylov {
       first = std::max<int64_t>(1, std::min<int64_t>(first, std::min<int64_t>(maxit, 1024)));
       if (ws.graphs.size() > 48) ws.drop_graphs();
       // folded loop: the entry for x0 == 0 when the previous solve with these operators had one (checked on the device)
-      bool zero_variant = whole && fold && fused && ws.zero_x0[pk] && !env_int("MI355_NO_ZERO_ENTRY", 0);
+      bool zero_variant = whole && form == Loop::FOLD && ws.zero_x0[pk] && !env_int("MI355_NO_ZERO_ENTRY", 0);
       hipGraphExec_t g0 = nullptr;
       try {
         g0 = graph(-(int)first, whole ? (zero_variant ? 2 : 1) : 0);
@@ -665,9 +673,9 @@ struct Krylov {
           ++ctx->n_replays; MI_HIP(hipGraphLaunch(g0, s));
           wait_seq(seq2);
         }
-        if (fold) ws.zero_x0[pk] = ws.flags[0].x0z != 0;
+        if (folded()) ws.zero_x0[pk] = ws.flags[0].x0z != 0;
         if (ws.stats_on) ws.stat(ws.flags[0].t_exit - ws.flags[0].t_entry);
-        if (ws.fold_dbg.p && fold) {   // stamps of the solve that has just finished (100 MHz ticks -> us since the first one)
+        if (ws.fold_dbg.p && folded()) {   // stamps of the solve that has just finished (100 MHz ticks -> us since the first one)
           std::vector<long long> h(512);
           MI_HIP(hipStreamSynchronize(s));
           memcpy_sync(h.data(), ws.fold_dbg.p, 512 * sizeof(long long), hipMemcpyDeviceToHost);
@@ -702,7 +710,7 @@ struct Krylov {
         enqueue_results(0);
         MI_HIP(hipStreamSynchronize(s));
       }
-      predicted = (int)std::max<long long>(1, ws.flags[0].it - ((fold || csrfold()) ? 0 : 1));  // the folded pairs check the stop rule one launch later
+      predicted = (int)std::max<long long>(1, ws.flags[0].it - (two_launch() ? 0 : 1));  // the two-launch forms check the stop rule one launch later
       }
     }
     if (!use_graph) {

@@ -45,7 +45,7 @@ NVEC_EPT2 = (7, 8, 9)
 
 
 def ept(n):
-    """template argument MI_EPT_DISPATCH picks; 0: n leaves the single-workgroup loop"""
+    """template argument Krylov::with_ept picks; 0: n leaves the single-workgroup loop"""
     for e in (1, 2, 4, 8):
         if n <= e * NTF:
             return e

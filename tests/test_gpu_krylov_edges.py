@@ -17,7 +17,7 @@ bar): 755 comparisons with the oracle, `it` equal in all of them and across the 
 sp4096 ... sp8193 from a random x0); res_norm <= 7.3e-4 (d2048w1, pcg from a random x0, folded), x <= 3.5e-7 (d1025w6, cg);
 all 18 chunk comparisons and all 24 replayed-against-eager solves bit-identical.
 Sensitivity, each defect seeded once into a scratch build and this file run against it:
-  * `n <= 2 * NTF + 1` in MI_EPT_DISPATCH: sp2049, d2049w2, d2049w4 fail. (`n < 2 * NTF` changes no bit: n = 2048 then runs
+  * `n <= 2 * NTF + 1` in the EPT dispatch (Krylov::with_ept): sp2049, d2049w2, d2049w4 fail. (`n < 2 * NTF` changes no bit: n = 2048 then runs
     the EPT 4 instantiation, whose guarded extra elements add +0.0 to every thread's sums in the same order.)
   * the partial column group of k_fused_p dropped (`q0 + QB <= nvec`): 87 tests fail — every nvec that is no multiple of 8
     (nloc*, tiles*, d1025w4 7 / 9) or of 4 at EPT 8 (d4097w4 and sp8192 with 3, 5, 9), and every nvec = 65;
