@@ -9,9 +9,9 @@
 // where C_k = A_{k+1,k} and B = A_IΓ[L_0, :] are SPARSE (a P1 node has <= 3-4 neighbours in the adjacent level), so every
 // entry of C' Z C is a sum of a dozen picked entries of Z ("pick" kernels, one thread per entry) and the only dense
 // O(n^3) work per level is the inversion of the SPD matrix T_k: an in-place-style block Gauss-Jordan inversion without
-// pivoting (block size 32; the k-th pivot block of an SPD matrix is its k-th Schur complement, SPD again): the 32 x 32
-// pivot block is inverted by one wave (rows in registers) — for the first block of a level in a launch of its own, for the
-// others inside the previous step's update launch (look-ahead) —, and one launch per block step updates the whole
+// pivoting (block size 64; the k-th pivot block of an SPD matrix is its k-th Schur complement, SPD again): the 64 x 64
+// pivot block is inverted by one workgroup on the matrix cores — for the first block of a level in a launch of its own, for
+// the others inside the previous step's update launch (look-ahead) —, and one launch per block step updates the whole
 // matrix from the previous copy (ping-pong buffers: no launch reads what it writes) —
 //     row panel   P A_Kj,   column panel   -A_iK P,   trailing   A_ij - A_iK (P A_Kj),   pivot block   P.
 // All subdomains advance together (grid.z), aligned so that they reach level 0 in the same step. The launch sequence
@@ -27,15 +27,12 @@ namespace mi {
 
 using SetupDom = setup::Dom;
 
-#ifndef MI355_GJ_B
-#define MI355_GJ_B 64
-#endif
-constexpr int GJ_B = MI355_GJ_B;   // pivot block: 64 (one full-matrix pass per 64 eliminated rows; its inverse from two 32-wide
-                                   // register inversions and 32 x 32 matrix-core products) or 32 (round 2's form)
-constexpr int GJ_H = 32;    // rows one wave inverts in registers
+constexpr int GJ_B = 64;    // pivot block: one full-matrix pass per 64 eliminated rows, its inverse by gj_invert_block64
 constexpr int GJ_T = 64;    // tile of the update launch (256 threads, 4 x 4 outputs each)
 constexpr int GJ_MAX_DOM = 65535;   // subdomains of one plan / blocks of one batch: they are the launches' grid.z
-static_assert(GJ_B == 32 || GJ_B == 64, "pivot block");
+// LDS doubles behind the matrix a workgroup inverts. gj_invert_block64 uses 4 x 68 of them; the size is kept because it sets
+// the update launch's footprint (50 KB, three workgroups per CU): shrinking it changes occupancy and needs its own measurement.
+constexpr int GJ_SCRATCH = 32 * (GJ_T + 1) + 64;
 
 struct GjStep {             // one per (step, subdomain); n0 == 0: the subdomain is not active in this step
   int n1, n0;               // size of the deeper level (dimension of Z_in; 0 at the subdomain's first step) and of this level
@@ -233,75 +230,7 @@ __global__ __launch_bounds__(256) void k_gj_g(int step, int ndom, const GjStep *
 
 // ---- block Gauss-Jordan inversion of T (n0 x n0, SPD), block step kb: source = T (kb == 0) or Z[kb & 1], destination Z[(kb + 1) & 1]
 __device__ __forceinline__ const double *gj_src(const GjDom &dm, int kb) { return kb == 0 ? dm.T : GJ_Z(dm, kb & 1); }
-// P = (pivot block)^{-1}: ONE wave per subdomain, lane r holds row r of the block in registers; a Gauss-Jordan step
-// broadcasts the scaled pivot row with v_readlane (no LDS round trips, no barriers in the 32-step dependency chain).
-// row[c] = lane r's row of a 32 x 32 SPD block (identity beyond the block's size) -> its inverse, in place
-__device__ __forceinline__ void gj_invert_rows(double (&row)[GJ_H], int r) {
-#pragma unroll
-  for (int p = 0; p < GJ_H; ++p) {
-    const double piv = 1.0 / lane_read(row[p], p);
-    if (r == p) {
-#pragma unroll
-      for (int c = 0; c < GJ_H; ++c) row[c] = c == p ? piv : row[c] * piv;
-    }
-    const double f = row[p];
-#pragma unroll
-    for (int c = 0; c < GJ_H; ++c) {
-      const double rp = lane_read(row[c], p);          // the (scaled) pivot row, uniform
-      if (r != p && c != p) row[c] -= f * rp;
-    }
-    if (r != p) row[p] = -f * piv;
-  }
-}
 typedef double gj_d4 __attribute__((ext_vector_type(4)));
-// in-place inverse of the 32 x 32 SPD block at M[o.., o..] by ONE wave, all 64 lanes: lane l holds half a row (row l & 31,
-// columns 16 (l >> 5) .. + 15) in registers. A Gauss-Jordan step passes the pivot row and the pivot column through 64
-// doubles of LDS (`scr`; broadcast reads, no v_readlane chain, no second wave): ~70 instructions per step instead of
-// ~200 with whole rows per lane and 64 v_readlanes — the 32-step chain is the critical path of the whole level elimination
-// (every block step waits for it), so this is the kernel that sets the set-up's time.
-// In-place Gauss-Jordan inverse of the 32 x 32 block at (o, o) of an LDS matrix, by 32 lanes of wave 0: lane r keeps row r
-// in registers (32 doubles); a step broadcasts the pivot row with v_readlane (uniform values, straight into the FMAs'
-// scalar operand) — no LDS round trip and no barrier inside the 32-step chain, which is the serial part of every block
-// step of the elimination (the LDS version with half rows per lane took 0.4 us per step, this one 0.1).
-__device__ __forceinline__ double gj_readlane(double v, int lane) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_readlane(lo, lane);
-  hi = __builtin_amdgcn_readlane(hi, lane);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ void gj_inv32(double *M, int LD, int o, double *scr) {
-  (void)scr;
-  if (threadIdx.x < 64) {
-    const int r = threadIdx.x & 31;          // (lanes 32..63 mirror lanes 0..31: the wave stays convergent, only the lower half stores)
-    double a[32];
-#pragma unroll
-    for (int c = 0; c < 32; ++c) a[c] = M[(o + r) * LD + o + c];
-#pragma unroll
-    for (int p = 0; p < 32; ++p) {
-      const double piv = 1.0 / gj_readlane(a[p], p);
-      const double f = a[p];
-      const double fp = f * piv;
-      const bool me = r == p;
-#pragma unroll
-      for (int c = 0; c < 32; ++c) {
-        const double pr = gj_readlane(a[c], p);        // row p before this step
-        if (c == p) a[c] = me ? piv : -fp;
-        else a[c] = me ? pr * piv : a[c] - fp * pr;
-      }
-    }
-    if (threadIdx.x < 32) {
-#pragma unroll
-      for (int c = 0; c < 32; ++c) M[(o + r) * LD + o + c] = a[c];
-    }
-  }
-}
-#ifndef MI355_GJ_HEAD
-#define MI355_GJ_HEAD 0            // 0 (default): look-ahead — the tile holding the NEXT pivot block inverts it at the END of the launch (161.5 ms per
-                                   // config-3 realization); 1: the pivot block of a step is inverted at the HEAD of its own launch (167.3 ms)
-#endif
-#ifndef MI355_GJ_INV_RECURSIVE
-#define MI355_GJ_INV_RECURSIVE 0   // 1: the 2 x 2 block recursion over two 32-step register inversions (25 us per pivot block instead of 21)
-#endif
 // inverse of a 4 x 4 matrix (row-major m) whose leading 2 x 2 block and its Schur complement are non-singular (pivot blocks of
 // an SPD matrix are): [A B; C D]^{-1} = [Ai + X Si V, -X Si; -Si V, Si],  Ai = A^{-1}, X = Ai B, V = C Ai, S = D - C X, Si = S^{-1}
 __device__ __forceinline__ void gj_inv4(const double (&m)[16], double (&p)[16]) {
@@ -324,14 +253,10 @@ __device__ __forceinline__ void gj_inv4(const double (&m)[16], double (&p)[16]) 
 // 16 block steps instead of 64 scalar ones. A step: every thread inverts the pivot block M[K, K] in registers (redundantly:
 // no broadcast of the result needed); thread (k, j) forms one entry of the row panel R = P M[K, :] (columns K: P itself);
 // then D = C - M[:, K] R is ONE 16 x 16 x 4 matrix-core op per 16 x 16 block (C = M, zero in columns K, so those become the
-// column panel -M[:, K] P); rows K take R. Two barriers per step. `Rb`: 4 x 68 doubles of scratch.
-// (The scalar chain this replaces — two 32-step register inversions — took 24 of the 25 us of a pivot-block inversion; this
-// one takes 21, 1.3 us per block step of which 0.7-0.9 are the four matrix-core ops with their operand moves. A variant that
-// keeps the matrix in registers and moves only the pivot rows / columns through LDS measured the same 21 us: the tiles'
-// LDS traffic is not what a step waits for. tools/probes/inv_probe.hip.)
-#ifndef GJ_STAMP
-#define GJ_STAMP(i)
-#endif
+// column panel -M[:, K] P); rows K take R. Two barriers per step. `Rb`: 4 x 68 doubles of scratch. Beyond the matrix' end
+// the caller puts the identity. The chain of these 16 steps is the serial part of every block step of the elimination
+// (every tile of the next launch waits for it): 21 us per pivot block, 1.3 us per step, of which 0.7-0.9 are the four
+// matrix-core ops with their operand moves; the tiles' LDS traffic is not what a step waits for (tools/probes/inv_probe.hip).
 __device__ __forceinline__ void gj_invert_block64(double *M, int LD, double *Rb, bool mirror) {
   constexpr int RL = 68;
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, lc = l & 15, lk = l >> 4;
@@ -343,9 +268,7 @@ __device__ __forceinline__ void gj_invert_block64(double *M, int LD, double *Rb,
     for (int a = 0; a < 4; ++a)
 #pragma unroll
       for (int b = 0; b < 4; ++b) m[4 * a + b] = M[(k0 + a) * LD + k0 + b];
-    GJ_STAMP(0);
     gj_inv4(m, p);
-    GJ_STAMP(1);
     {
       double q0, q1, q2, q3;                       // row wv of P (wave-uniform choice)
       if (wv == 0) { q0 = p[0]; q1 = p[1]; q2 = p[2]; q3 = p[3]; }
@@ -360,9 +283,7 @@ __device__ __forceinline__ void gj_invert_block64(double *M, int LD, double *Rb,
       const double v2 = inK ? (jj == 2 ? 1.0 : 0.0) : w2, v3 = inK ? (jj == 3 ? 1.0 : 0.0) : w3;
       Rb[wv * RL + j] = ((q0 * v0 + q1 * v1) + q2 * v2) + q3 * v3;
     }
-    GJ_STAMP(2);
     __syncthreads();
-    GJ_STAMP(3);
     const double aop = M[(16 * wv + lc) * LD + k0 + lk];        // M[row block wv][K]: A[row = lc][k = lk]
     const bool krows = wv == (s >> 2);
     const int vk = s & 3;
@@ -388,9 +309,7 @@ __device__ __forceinline__ void gj_invert_block64(double *M, int LD, double *Rb,
 #pragma unroll
       for (int v = 0; v < 4; ++v) M[(16 * wv + lk + 4 * v) * LD + col] = (krows && v == vk) ? rb[bj] : d[bj][v];   // row 16 wv + lk + 4 v is pivot row k0 + lk exactly then
     }
-    GJ_STAMP(4);
     __syncthreads();
-    GJ_STAMP(5);
   }
   // `mirror` (the block is the whole matrix, P the result): symmetric to the last bit, the upper triangle mirrored. NOT when
   // P feeds further block steps: the two triangles of an unpivoted Gauss-Jordan inverse carry errors of order κ eps that
@@ -401,72 +320,6 @@ __device__ __forceinline__ void gj_invert_block64(double *M, int LD, double *Rb,
   for (int e = threadIdx.x; e < 64 * 64; e += 256) {
     const int i = e >> 6, j = e & 63;
     if (j > i) M[j * LD + i] = M[i * LD + j];
-  }
-  __syncthreads();
-}
-// in-place inverse of the SPD GJ_B x GJ_B block in LDS (row stride LD; identity beyond the matrix' end), 256 threads. GJ_B = 64:
-//   [A B; B' D]^{-1} = [P + Y X', -Y; -Y', S^{-1}],  P = A^{-1},  X = P B,  S = D - B' X,  Y = X S^{-1}
-// two 32-step register inversions (the serial part) and five 32 x 32 x 32 products; `W` = 32 x LD doubles of scratch, `scr` = 64 more.
-// `whole`: the block is the whole matrix (one pivot block), its inverse the result (see gj_invert_block64).
-__device__ __forceinline__ void gj_invert_block(double *M, int LD, double *W, double *scr, bool whole) {
-  if (GJ_B == 64 && !MI355_GJ_INV_RECURSIVE) { gj_invert_block64(M, LD, W, whole); return; }
-  if (GJ_B == 32) {
-    gj_inv32(M, LD, 0, scr);
-    __syncthreads();
-    return;
-  }
-  gj_inv32(M, LD, 0, scr);                                              // P = A^{-1}                        (M11)
-  __syncthreads();
-  // X = P B -> W (32 x 32)
-  {
-    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, lc = l & 15, lk = l >> 4, bi = wv >> 1, bj = wv & 1;
-    gj_d4 d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 32; kk += 4)
-      d = __builtin_amdgcn_mfma_f64_16x16x4f64(M[(16 * bi + lc) * LD + kk + lk], M[(kk + lk) * LD + 32 + 16 * bj + lc], d, 0, 0, 0);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) W[(16 * bi + lk + 4 * v) * LD + 16 * bj + lc] = d[v];
-  }
-  __syncthreads();
-  // S = D - B' X   (B' = M21 as stored: the block is symmetric; read M12 transposed)      -> M22
-  {
-    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, lc = l & 15, lk = l >> 4, bi = wv >> 1, bj = wv & 1;
-    gj_d4 d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 32; kk += 4)
-      d = __builtin_amdgcn_mfma_f64_16x16x4f64(M[(kk + lk) * LD + 32 + 16 * bi + lc], W[(kk + lk) * LD + 16 * bj + lc], d, 0, 0, 0);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) M[(32 + 16 * bi + lk + 4 * v) * LD + 32 + 16 * bj + lc] -= d[v];
-  }
-  __syncthreads();
-  gj_inv32(M, LD, 32, scr);                                             // S^{-1}                            (M22)
-  __syncthreads();
-  // Y = X S^{-1} -> M12 (B is no longer needed), then M21 = -Y', M12 = -Y, M11 = P + Y X'
-  {
-    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, lc = l & 15, lk = l >> 4, bi = wv >> 1, bj = wv & 1;
-    gj_d4 d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 32; kk += 4)
-      d = __builtin_amdgcn_mfma_f64_16x16x4f64(W[(16 * bi + lc) * LD + kk + lk], M[(32 + kk + lk) * LD + 32 + 16 * bj + lc], d, 0, 0, 0);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) M[(16 * bi + lk + 4 * v) * LD + 32 + 16 * bj + lc] = d[v];      // Y (sign below)
-  }
-  __syncthreads();
-  {
-    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, lc = l & 15, lk = l >> 4, bi = wv >> 1, bj = wv & 1;
-    gj_d4 d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 32; kk += 4)                                   // Y X' : A = Y[i][k], B = X'[k][j] = X[j][k]
-      d = __builtin_amdgcn_mfma_f64_16x16x4f64(M[(16 * bi + lc) * LD + 32 + kk + lk], W[(16 * bj + lc) * LD + kk + lk], d, 0, 0, 0);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) M[(16 * bi + lk + 4 * v) * LD + 16 * bj + lc] += d[v];
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 32 * 32; e += 256) {
-    const int i = e >> 5, j = e & 31;
-    const double y = M[i * LD + 32 + j];
-    M[i * LD + 32 + j] = -y;
-    M[(32 + j) * LD + i] = -y;
   }
   __syncthreads();
 }
@@ -481,63 +334,45 @@ __global__ __launch_bounds__(256) void k_gj_pivot(int step, int kb, int ndom, co
   const double *A = gj_src(dm, kb);
   constexpr int LD = GJ_B + 1;
   __shared__ double Mb[GJ_B * LD];
-  __shared__ double Wb[GJ_H * LD + 64];
+  __shared__ double Wb[GJ_SCRATCH];
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) {
     const int r = e % GJ_B, c = e / GJ_B;
     Mb[r * LD + c] = (r < bs && c < bs) ? A[(k0 + r) + (size_t)(k0 + c) * n] : (r == c ? 1.0 : 0.0);
   }
   __syncthreads();
-  gj_invert_block(Mb, LD, Wb, Wb + GJ_H * LD, st.nb == 1);
+  gj_invert_block64(Mb, LD, Wb, st.nb == 1);   // one pivot block: its inverse is the result, mirrored to symmetry
   double *Pd = dm.P + (kb & 1) * (GJ_B * GJ_B);
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) Pd[e] = Mb[(e % GJ_B) * LD + e / GJ_B];   // column-major GJ_B x GJ_B
 }
 // one 64 x 64 tile of the updated matrix from the previous copy, on the fp64 matrix cores (v_mfma_f64_16x16x4_f64:
-// A[l & 15][k = l >> 4], B[k = l >> 4][l & 15], D: col = l & 15, row = (l >> 4) + 4 reg). R = P A[K, J] (32 x 64) first, then
+// A[l & 15][k = l >> 4], B[k = l >> 4][l & 15], D: col = l & 15, row = (l >> 4) + 4 reg). R = P A[K, J] (64 x 64) first, then
 // the trailing update computed TRANSPOSED — the instruction's row index runs over the tile's columns j, its column index
 // over the tile's rows i — so that a lane's four results sit in 16-lane groups of consecutive i: loads and stores of the
 // column-major matrix are 128-byte segments. Wave v owns rows 16 v .. 16 v + 15 of the tile.
-__device__ __forceinline__ unsigned *gj_ready_flag(const GjDom &dm) { return reinterpret_cast<unsigned *>(dm.P + 2 * GJ_B * GJ_B); }
-__global__ void k_gj_reset(int ndom, const GjDom *__restrict__ doms) {
-  const int d = blockIdx.x * blockDim.x + threadIdx.x;
-  if (d < ndom) *gj_ready_flag(doms[d]) = 0u;
-}
-template <bool HEAD_T>
 __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom, const GjStep *__restrict__ steps,
-                                                   const GjDom *__restrict__ doms, unsigned seq, int tiles_x) {
-  // HEAD (MI355_GJ_HEAD=1, measured and not the default): the pivot block of THIS step is inverted at the head of the launch
-  // by its own workgroup while every other tile loads its operands (the bandwidth-bound 7-10 us of a launch); the others
-  // then wait for a per-subdomain flag and fetch P; no separate first-pivot launch per level. Small levels gain (37 us per
-  // launch against ~45), the large ones lose more: their waiting tiles keep compute units that the look-ahead form uses.
-  constexpr bool HEAD = HEAD_T && GJ_B == GJ_T;
-  // HEAD: a 1-D grid whose FIRST ndom workgroups are the pivot tiles of the subdomains — dispatched before any tile that
-  // will wait for them, whatever the number of resident workgroups (with the pivot tile merely first in its subdomain's
-  // slab, slabs beyond the resident set started their inversion only when earlier slabs had finished: 128 us launches).
-  // `tiles_x` = tiles per row of the (square) tile grid.
-  int dz, gbx, gby;
-  if (HEAD) {
-    const int b = blockIdx.x;
-    if (b < ndom) { dz = b; gbx = gby = kb; }
-    else { const int t = b - ndom; gbx = t % tiles_x; gby = (t / tiles_x) % tiles_x; dz = t / (tiles_x * tiles_x); }
-  } else { dz = blockIdx.z; gbx = blockIdx.x; gby = blockIdx.y; }
+                                                   const GjDom *__restrict__ doms) {
+  // a pivot block as wide as a tile: every lane keeps its share of A[I, K] in registers, and the tiles of block column K
+  // are a zero-start product with P (both below)
+  static_assert(GJ_B == GJ_T, "pivot block and tile have one width");
+  const int dz = blockIdx.z, gbx = blockIdx.x, gby = blockIdx.y;
   const GjStep st = steps[(size_t)step * ndom + dz];
   const int n = st.n0;
   if (kb >= st.nb || gbx * GJ_T >= n || gby * GJ_T >= n) return;   // (the swap below stays inside the grid: td * GJ_T < n)
-  if (HEAD && (int)blockIdx.x >= ndom && gbx == kb && gby == kb) return;   // the pivot tile is one of the first ndom workgroups
   const GjDom dm = doms[dz];
   const int k0 = kb * GJ_B, bs = min(GJ_B, n - k0);
   const double *A = gj_src(dm, kb);
   double *O = GJ_Z(dm, (kb + 1) & 1);
   // Look-ahead: the tile that holds the NEXT pivot block (diagonal tile td) also inverts it once it has updated it, so that
-  // the next block step needs no pivot launch of its own (16 us of a serial 32-step chain per step, 5 400 steps per
+  // the next block step needs no pivot launch of its own (a serial chain of 21 us per step, 5 400 steps per
   // realization at config 3). That tile is dealt first (swapped with tile (0, 0)) so that its longer life stays inside the launch.
-  const int k1 = k0 + GJ_B, td = HEAD ? kb : k1 / GJ_T;
-  const bool ahead = HEAD || kb + 1 < st.nb;
+  const int k1 = k0 + GJ_B, td = k1 / GJ_T;
+  const bool ahead = kb + 1 < st.nb;
   int bx = gbx, by = gby;
-  if (ahead && !HEAD) {
+  if (ahead) {
     if (bx == 0 && by == 0) bx = by = td;
     else if (bx == td && by == td) bx = by = 0;
   }
-  const bool special = HEAD ? (int)blockIdx.x < ndom : (ahead && bx == td && by == td);
+  const bool special = ahead && bx == td && by == td;
   // SYMMETRY. With σ(i) = -1 for the indices already swept (i < k0) and +1 otherwise, the matrix between two block steps
   // satisfies M[j,i] = σ(i) σ(j) M[i,j] (the inverse pivot block and the trailing part are symmetric, the row panel P A_Kj
   // and the column panel -A_iK P are each other's negative transpose; induction over the steps, P symmetric). Only the
@@ -546,77 +381,30 @@ __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom
   // read any entry.
   if (bx > by) return;
   const int i0 = bx * GJ_T, j0 = by * GJ_T;
-#ifdef MI355_GJ_STAMPS
-  const bool dbg = step == 120 && kb == 2 && threadIdx.x == 0 && (special || ((bx * 7 + by * 3 + dz) % 29) == 0);
-  long long ts[6] = {0, 0, 0, 0, 0, 0};
-  if (dbg) ts[0] = wall_clock64();
-#define GJ_KSTAMP(i) do { if (dbg) ts[i] = wall_clock64(); } while (0)
-#else
-#define GJ_KSTAMP(i)
-#endif
-  // LDS: A[K, J] / R (GJ_B x 65) and A[I, K] (64 x (GJ_B + 1)): 33.4 KB with a 32-wide pivot block (three workgroups per CU),
-  // 66.6 KB with a 64-wide one (two). The pivot inverse P is NOT staged: every lane keeps the GJ_B / 4 entries it feeds to
-  // the matrix cores in registers (one request per entry, served by L2: every tile reads the same 32 KB).
-  // With a pivot block as wide as a tile A[I, K] is not staged either: every lane holds the 16 entries of its row that it
-  // feeds to the matrix cores (CC_REGS). The second buffer is then only the scratch of the look-ahead inversion: 50 KB per
-  // workgroup, THREE workgroups per CU — the 530-620 tiles of a config-3 launch are resident at once instead of running
-  // a second round for the last few (measured: the tile loop alone 44 -> see profiles/NOTES.md).
-  constexpr bool CC_REGS = GJ_B == GJ_T;
-  constexpr int LDS_R = GJ_B * (GJ_T + 1), LDS_CC = CC_REGS ? GJ_H * (GJ_T + 1) + 64 : GJ_T * (GJ_B + 1);
-  static_assert(LDS_R + LDS_CC >= GJ_T * (GJ_T + 1), "the mirror image of a tile is staged in the R and Cc buffers");
-  __shared__ double lds[LDS_R + LDS_CC];
+  // LDS: A[K, J] / R (GJ_B x 65) and the scratch of the look-ahead inversion: 50 KB per workgroup, THREE workgroups per CU
+  // — the 530-620 tiles of a config-3 launch are resident at once instead of running a second round for the last few
+  // (profiles/NOTES.md). Neither the pivot inverse P nor A[I, K] is staged: every lane keeps the GJ_B / 4 entries of each
+  // that it feeds to the matrix cores in registers (P: one request per entry, served by L2: every tile reads the same 32 KB).
+  constexpr int LDS_R = GJ_B * (GJ_T + 1);
+  static_assert(LDS_R >= GJ_T * (GJ_T + 1), "the mirror image of a tile is staged in the R buffer");
+  __shared__ double lds[LDS_R + GJ_SCRATCH];
   double (&R)[GJ_B][GJ_T + 1] = *reinterpret_cast<double (*)[GJ_B][GJ_T + 1]>(lds);           // A[K, J] first, then R = P * A[K, J], then (look-ahead tile) the next pivot block
-  double (&Cc)[GJ_T][GJ_B + 1] = *reinterpret_cast<double (*)[GJ_T][GJ_B + 1]>(lds + LDS_R);  // A[I, K]
   double (&Ak)[GJ_B][GJ_T + 1] = R;
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, lc = l & 15, lk = l >> 4;
   const double *Pcur = dm.P + (kb & 1) * (GJ_B * GJ_B);   // column-major, symmetric
-  // R = P A[K, J]: (GJ_B / 16) x 4 blocks of 16 x 16; wave wv owns t-block(s) and j-blocks as below
-  constexpr int TBW = GJ_B == 64 ? 1 : 1, NQ = GJ_B == 64 ? 4 : 2;      // blocks per wave: 4 (64: tb = wv, all j) or 2 (32: tb = wv & 1, j = 2 (wv >> 1) + q)
-  (void)TBW;
-  const int tb = GJ_B == 64 ? wv : (wv & 1), jb0 = GJ_B == 64 ? 0 : 2 * (wv >> 1);
-  double pa[GJ_B / 4];                                                   // P[16 tb + lc][kk + lk], kk = 0, 4, ...
-  if (HEAD && special) {
-    // the pivot block of this step: load, invert, publish (write-through stores, acknowledged, then the flag), and store
-    // this tile of the result — the inverse itself
-    for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) {
-      const int r = e % GJ_B, c = e / GJ_B;
-      R[r][c] = (r < bs && c < bs) ? A[(k0 + r) + (size_t)(k0 + c) * n] : (r == c ? 1.0 : 0.0);
-    }
-    __syncthreads();
-    GJ_KSTAMP(1);
-    gj_invert_block(&R[0][0], GJ_T + 1, lds + LDS_R, lds + LDS_R + (GJ_B == 32 ? 0 : GJ_H * (GJ_T + 1)), st.nb == 1);
-    GJ_KSTAMP(2);
-    double *Pw = dm.P + (kb & 1) * (GJ_B * GJ_B);
-    for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) __hip_atomic_store(&Pw[e], R[e % GJ_B][e / GJ_B], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(gj_ready_flag(dm), seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    GJ_KSTAMP(3);
-#ifdef MI355_GJ_STAMPS
-    if (dbg) printf("PIVOT tile %2d %2d dom %d: start %lld loaded +%lld inverted +%lld published +%lld (n = %d)\n", bx, by, dz, ts[0], ts[1] - ts[0], ts[2] - ts[0], ts[3] - ts[0], n);
-#endif
-    for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) {
-      const int r = e % GJ_B, c = e / GJ_B;
-      if (r < bs && c < bs) O[(k0 + r) + (size_t)(k0 + c) * n] = R[r][c];
-    }
-    return;
-  }
-  if (!HEAD) {
+  // R = P A[K, J]: 4 x 4 blocks of 16 x 16; wave wv owns t-block wv and all four j-blocks
+  double pa[GJ_B / 4];                                                   // P[16 wv + lc][kk + lk], kk = 0, 4, ...
 #pragma unroll
-    for (int q = 0; q < GJ_B / 4; ++q) pa[q] = Pcur[(16 * tb + lc) + (size_t)(4 * q + lk) * GJ_B];
-  }
+  for (int q = 0; q < GJ_B / 4; ++q) pa[q] = Pcur[(16 * wv + lc) + (size_t)(4 * q + lk) * GJ_B];
   for (int e = threadIdx.x; e < GJ_B * GJ_T; e += 256) {
     const int t = e % GJ_B, c = e / GJ_B;        // A[k0 + t, j0 + c]: consecutive threads walk down a column
     Ak[t][c] = (t < bs && j0 + c < n) ? A[(k0 + t) + (size_t)(j0 + c) * n] : 0.0;
   }
-  double cb[GJ_B / 4];                           // CC_REGS: A[i0 + 16 wv + lc, k0 + 4 q + lk]
-  if (CC_REGS) {
+  double cb[GJ_B / 4];                           // A[i0 + 16 wv + lc, k0 + 4 q + lk]
+  {
     const int ir = i0 + 16 * wv + lc;
 #pragma unroll
     for (int q = 0; q < GJ_B / 4; ++q) cb[q] = (4 * q + lk < bs && ir < n) ? A[ir + (size_t)(k0 + 4 * q + lk) * n] : 0.0;
-  } else {
-    for (int t = wv; t < GJ_B; t += 4)           // A[i0 + l, k0 + t]
-      Cc[l][t] = (t < bs && i0 + l < n) ? A[(i0 + l) + (size_t)(k0 + t) * n] : 0.0;
   }
   // the old entries this lane will update (D layout of the transposed product): i = i0 + 16 wv + lc, j = j0 + 16 jt + lk + 4 v
   const int i = i0 + 16 * wv + lc;
@@ -628,47 +416,25 @@ __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom
       const int j = j0 + 16 * jt + lk + 4 * v;
       acc[jt][v] = (i < n && j < n) ? A[i + (size_t)j * n] : 0.0;
     }
-  // With a pivot block as wide as a tile the tiles of block column K (by == kb, above the diagonal) hold only column-panel
-  // entries -(A_iK P): the SAME matrix-core loop as the trailing update with P in place of R and a zero start
+  // The tiles of block column K (by == kb, above the diagonal) hold only column-panel entries -(A_iK P): the SAME
+  // matrix-core loop as the trailing update with P in place of R and a zero start
   // (D[j][i] = Σ_u P[u][j] (-A[i][k0 + u])); the diagonal tile (kb, kb) becomes P itself.
-  const bool kcol = GJ_B == GJ_T && by == kb;
-  GJ_KSTAMP(4);   // operand loads issued
-  if (HEAD) {
-    // P of this step: wait for the pivot tile's flag (bounded: a tile that gives up poisons its results, the finite check
-    // of the run then fails), then fetch it past the caches it was written through
-    __shared__ int gave_up;
-    if (threadIdx.x == 0) {
-      const unsigned *fl = gj_ready_flag(dm);
-      long long spins = 0;
-      while (__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < seq && spins < (1ll << 22)) { __builtin_amdgcn_s_sleep(32); ++spins; }
-      gave_up = spins >= (1ll << 22);
-    }
-    __syncthreads();
-    // Plain loads: no L2 holds a line of this P yet — the launch began with the caches' acquire, nobody has read P since
-    // (every reader waits for the flag), and the pivot tile wrote it through to memory before the flag. (Loads that bypass
-    // the L2 instead — 600 tiles x 32 KB from the same few channels — made a launch 20 us longer.)
-    const double poison = gave_up ? __builtin_nan("") : 0.0;
-#pragma unroll
-    for (int q = 0; q < GJ_B / 4; ++q) pa[q] = Pcur[(16 * tb + lc) + (size_t)(4 * q + lk) * GJ_B] + poison;
-  }
+  const bool kcol = by == kb;
   __syncthreads();
-  GJ_KSTAMP(1);   // operands loaded
   if (!kcol) {
-    gj_d4 d[NQ];
+    gj_d4 d[4];
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int jbk = jb0 + q;
+    for (int q = 0; q < 4; ++q) {
       d[q] = gj_d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int kk = 0; kk < GJ_B; kk += 4)
-        d[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[kk / 4], Ak[kk + lk][16 * jbk + lc], d[q], 0, 0, 0);
+        d[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[kk / 4], Ak[kk + lk][16 * q + lc], d[q], 0, 0, 0);
     }
     __syncthreads();                             // every wave has read A[K, J]: the buffer becomes R
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int jbk = jb0 + q;
+    for (int q = 0; q < 4; ++q) {
 #pragma unroll
-      for (int v = 0; v < 4; ++v) R[16 * tb + lk + 4 * v][16 * jbk + lc] = d[q][v];
+      for (int v = 0; v < 4; ++v) R[16 * wv + lk + 4 * v][16 * q + lc] = d[q][v];
     }
   } else {
     __syncthreads();
@@ -678,10 +444,10 @@ __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom
     for (int jt = 0; jt < 4; ++jt) acc[jt] = gj_d4{0.0, 0.0, 0.0, 0.0};
   }
   __syncthreads();
-  // acc[jt] (rows j, cols i) -= R[K, J_jt]' * Cc[I, K]'  ==  (A_ij - A_iK (P A_Kj))'
+  // acc[jt] (rows j, cols i) -= R[K, J_jt]' * A[I, K]'  ==  (A_ij - A_iK (P A_Kj))'
 #pragma unroll
   for (int kk = 0; kk < GJ_B; kk += 4) {
-    const double bneg = CC_REGS ? -cb[kk / 4] : -Cc[16 * wv + lc][kk + lk];
+    const double bneg = -cb[kk / 4];
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) acc[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(R[kk + lk][16 * jt + lc], bneg, acc[jt], 0, 0, 0);
   }
@@ -697,20 +463,11 @@ __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom
       double val = acc[jt][v];                                                 // A_ij - A_iK (P A_Kj);  block column K: -(A_iK P)[i, j - k0]
       if (ik && jk) val = Pcur[(i - k0) + (size_t)(j - k0) * GJ_B];
       else if (ik) val = R[i - k0][jl];                                        // (P A_Kj)[i - k0, j]
-      else if (!CC_REGS && jk && !kcol) {                                      // -(A_iK P)[i, j - k0]   (32-wide pivot block inside a 64-wide tile)
-        double s2 = 0.0;
-        for (int u = 0; u < GJ_B; ++u) s2 += Cc[16 * wv + lc][u] * Pcur[u + (size_t)(j - k0) * GJ_B];
-        val = -s2;
-      }
       O[i + (size_t)j * n] = val;
       acc[jt][v] = val;
     }
-  GJ_KSTAMP(2);   // tile updated and stored
-#ifdef MI355_GJ_STAMPS
-  if (dbg && !special) printf("tile %2d %2d dom %d: start %lld loaded +%lld updated +%lld (loads issued +%lld)\n", bx, by, dz, ts[0], ts[1] - ts[0], ts[2] - ts[0], ts[4] - ts[0]);
-#endif
   if (bx != by) {                                // the mirror image: M[j,i] = σ'(i) σ'(j) M[i,j], σ' = -1 below k1 (swept after this step)
-    __syncthreads();                             // R, Cc are read for the last time above
+    __syncthreads();                             // R is read for the last time above
     double *T = lds;                             // [GJ_T][GJ_T + 1]
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt)
@@ -731,9 +488,9 @@ __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom
       }
     return;
   }
-  if (HEAD || !special) return;
+  if (!special) return;
   // Look-ahead: this diagonal tile holds the next pivot block (rows / columns k1 .. k1 + bs1 of the updated matrix); its inverse
-  // goes to the other half of P. R becomes the landing zone (row stride GJ_T + 1), Cc the scratch of the block inversion.
+  // goes to the other half of P. R becomes the landing zone (row stride GJ_T + 1), the rest of `lds` the inversion's scratch.
   __syncthreads();
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) { const int rr = e / GJ_B, cc = e % GJ_B; R[rr][cc] = rr == cc ? 1.0 : 0.0; }   // identity beyond the matrix' end
   __syncthreads();
@@ -745,14 +502,9 @@ __global__ __launch_bounds__(256, 3) void k_gj_update(int step, int kb, int ndom
       if (i >= k1 && i < k1 + bs1 && j >= k1 && j < k1 + bs1) R[i - k1][j - k1] = acc[jt][v];   // (trailing entries: K1 != K)
     }
   __syncthreads();
-  static_assert(LDS_CC >= GJ_H * (GJ_T + 1) + 64 || GJ_B == 32, "scratch of the block inversion lives in the Cc buffer");
-  gj_invert_block(&R[0][0], GJ_T + 1, lds + LDS_R, lds + LDS_R + (GJ_B == 32 ? 0 : GJ_H * (GJ_T + 1)), false);   // (block kb + 1 >= 1)
-  GJ_KSTAMP(3);   // pivot block inverted
+  gj_invert_block64(&R[0][0], GJ_T + 1, lds + LDS_R, false);   // (block kb + 1 >= 1: P feeds further block steps, not mirrored)
   double *Pn = dm.P + ((kb + 1) & 1) * (GJ_B * GJ_B);
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) Pn[e] = R[e % GJ_B][e / GJ_B];
-#ifdef MI355_GJ_STAMPS
-  if (dbg) printf("LOOK-AHEAD tile %2d %2d dom %d: start %lld loaded +%lld updated +%lld inverted +%lld (n = %d)\n", bx, by, dz, ts[0], ts[1] - ts[0], ts[2] - ts[0], ts[3] - ts[0], n);
-#endif
 }
 // ---- the end of a subdomain's chain: S (upper triangle mirrored) = A_ΓΓ - B' Z_0 B; w = B' (Z_0 g_0)
 __global__ __launch_bounds__(256) void k_gj_final_pick(int ndom, const GjDom *__restrict__ doms, const int *__restrict__ c_ptr,
@@ -920,7 +672,7 @@ inline void gj_build(mi_setup_s &P) {
     const size_t nm = (size_t)std::max(1, D.max_lev), nt = (size_t)std::max<int>(std::max(1, D.max_lev), D.n_g);
     auto take = [&](size_t cnt) { const size_t o = tot; tot += (cnt + 31) / 32 * 32; return o; };
     off_T[d] = take(nt * nt); off_Z0[d] = take(nm * nm); off_Z1[d] = take(nm * nm);
-    off_y[d] = take(nm); off_g0[d] = take(nm); off_g1[d] = take(nm); off_P[d] = take(2 * GJ_B * GJ_B + 16);   // (+ the step's ready flag)
+    off_y[d] = take(nm); off_g0[d] = take(nm); off_g1[d] = take(nm); off_P[d] = take(2 * GJ_B * GJ_B);
   }
   G->pool.alloc(tot + 32);
   memset_sync(G->pool.p, 0, sizeof(double) * (tot + 32));
@@ -958,6 +710,16 @@ inline void gj_build(mi_setup_s &P) {
   P.gj = std::move(G);
 }
 
+// The block steps of one level of `n` subdomains or blocks (grid.z), of which the longest takes nb_max steps and the widest
+// has n_max rows: the first pivot block in a launch of its own, every later one by look-ahead inside the update launches.
+inline void gj_block_steps(hipStream_t s, int step, int nb_max, int n_max, int n, const GjStep *steps, const GjDom *doms) {
+  const int tx = (n_max + GJ_T - 1) / GJ_T;
+  for (int kb = 0; kb < nb_max; ++kb) {
+    if (kb == 0) hipLaunchKernelGGL(k_gj_pivot, dim3(1, 1, n), dim3(256), 0, s, step, kb, n, steps, doms);
+    hipLaunchKernelGGL(k_gj_update, dim3(tx, tx, n), dim3(256), 0, s, step, kb, n, steps, doms);
+  }
+}
+
 // enqueue the whole elimination on `s` (plain launches: capturable)
 inline void gj_enqueue(mi_setup_s &P, hipStream_t s, const double *ii, const double *ig, const double *gg, const double *bI, double *Sd,
                        double *w) {
@@ -967,24 +729,14 @@ inline void gj_enqueue(mi_setup_s &P, hipStream_t s, const double *ii, const dou
   const GjDom *dm = G.doms.p;
   auto cdiv = [](int a, int b) { return (a + b - 1) / b; };
   int nm = std::max(1, G.nmax);
-  // levels of at most `head_maxn` nodes invert the step's pivot block at the head of the launch, larger ones look ahead
-  static const int head_maxn = GJ_B == GJ_T ? env_int("MI355_GJ_HEAD_MAXN", MI355_GJ_HEAD ? (1 << 30) : 0) : 0;
-  unsigned seq = 0;
   if (nd > GJ_MAX_DOM) raise(MI_ERR_BAD_ARG, "device set-up: more than %d subdomains in one plan", GJ_MAX_DOM);
-  hipLaunchKernelGGL(k_gj_reset, dim3(cdiv(nd, 1024)), dim3(1024), 0, s, nd, dm);
   for (int step = 0; step < G.nsteps; ++step) {
     nm = G.n_step[step];   // grids cover the largest level of this step only
     if (bI && step > 0) hipLaunchKernelGGL(k_gj_zg, dim3(cdiv(nm, 64), 1, nd), dim3(256), 0, s, step, nd, st, dm);
     hipLaunchKernelGGL(k_gj_pick, dim3(cdiv(nm, 16), cdiv(nm, 16), nd), dim3(256), 0, s, step, nd, st, dm, P.c_ptr.p, P.c_row.p, P.c_src.p, ii);
     hipLaunchKernelGGL(k_gj_scatter, dim3(8, 1, nd), dim3(256), 0, s, step, nd, st, dm, P.src.p, P.dst.p, ii);
     if (bI) hipLaunchKernelGGL(k_gj_g, dim3(cdiv(nm, 256), 1, nd), dim3(256), 0, s, step, nd, st, dm, P.c_ptr.p, P.c_row.p, P.c_src.p, ii, P.perm.p, bI);
-    const bool gj_head = nm <= head_maxn;
-    for (int kb = 0; kb < G.nb_step[step]; ++kb) {
-      if (kb == 0 && !gj_head) hipLaunchKernelGGL(k_gj_pivot, dim3(1, 1, nd), dim3(256), 0, s, step, kb, nd, st, dm);   // later pivots: look-ahead in the update
-      const int tx = cdiv(nm, GJ_T);
-      if (gj_head) hipLaunchKernelGGL(k_gj_update<true>, dim3(nd + tx * tx * nd), dim3(256), 0, s, step, kb, nd, st, dm, ++seq, tx);
-      else hipLaunchKernelGGL(k_gj_update<false>, dim3(tx, tx, nd), dim3(256), 0, s, step, kb, nd, st, dm, ++seq, tx);
-    }
+    gj_block_steps(s, step, G.nb_step[step], nm, nd, st, dm);
     if (G.keep) hipLaunchKernelGGL(k_gj_keep, dim3(std::min(1024, cdiv(nm * nm, 1024)), 1, nd), dim3(256), 0, s, step, nd, st, dm, G.zstore.p);
   }
   const int ngm = std::max(1, G.ngmax);
@@ -1098,30 +850,22 @@ inline void gj_run(mi_setup_s &P, const double *ii_val, const double *ig_val, co
   auto cp = [&](double *dst, const double *src, long long cnt) {
     if (cnt > 0) MI_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToDevice, s));
   };
-  if (G.graph_failed || env_int("MI355_SETUP_NO_GRAPH", 0)) {
+  hipGraphExec_t &ex = G.graph[rhs ? 1 : 0];
+  bool plain = G.graph_failed || env_int("MI355_SETUP_NO_GRAPH", 0);
+  if (!plain && !ex) {
+    try {
+      ex = capture_graph(s, "device set-up", [&] {
+        gj_enqueue(P, s, G.in_ii.p, G.in_ig.p, G.in_gg.p, rhs ? G.in_bi.p : nullptr, G.out_S.p, rhs ? G.out_w.p : nullptr);
+      });
+    } catch (const Error &) {                    // a failed capture: plain launches in this run and in every later one
+      (void)hipGetLastError();
+      G.graph_failed = plain = true;
+    }
+  }
+  if (plain) {
     if (G.keep) cp(G.in_ii.p, ii_val, P.n_ii);   // the level solves read the coupling values from the plan's copy
     gj_enqueue(P, s, ii_val, ig_val, gg_val, rhs ? bI : nullptr, Sd, w);
     return;
-  }
-  hipGraphExec_t &ex = G.graph[rhs ? 1 : 0];
-  if (!ex) {
-    hipGraph_t gr = nullptr;
-    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    if (ok) {
-      try {
-        gj_enqueue(P, s, G.in_ii.p, G.in_ig.p, G.in_gg.p, rhs ? G.in_bi.p : nullptr, G.out_S.p, rhs ? G.out_w.p : nullptr);
-      } catch (const Error &) { ok = false; }
-      if (hipStreamEndCapture(s, &gr) != hipSuccess) ok = false;
-    }
-    if (ok && gr) ok = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0) == hipSuccess;
-    if (gr) (void)hipGraphDestroy(gr);
-    if (!ok) {
-      (void)hipGetLastError();
-      ex = nullptr; G.graph_failed = true;
-      if (G.keep) cp(G.in_ii.p, ii_val, P.n_ii);
-      gj_enqueue(P, s, ii_val, ig_val, gg_val, rhs ? bI : nullptr, Sd, w);
-      return;
-    }
   }
   cp(G.in_ii.p, ii_val, P.n_ii); cp(G.in_ig.p, ig_val, P.n_ig); cp(G.in_gg.p, gg_val, P.n_gg);
   if (rhs) cp(G.in_bi.p, bI, P.n_bi);
@@ -1223,7 +967,7 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
     const size_t n = (size_t)n_gamma_d[d], nn = std::max<size_t>(1, n * n);
     off[d] = run; run += n * n; ov[d] = nsum; nsum += n;
     auto take = [&](size_t cnt) { const size_t o = tot; tot += (cnt + 31) / 32 * 32; return o; };
-    oT[d] = take(nn); o0[d] = take(nn); o1[d] = take(nn); oP[d] = take(2 * GJ_B * GJ_B + 16);
+    oT[d] = take(nn); o0[d] = take(nn); o1[d] = take(nn); oP[d] = take(2 * GJ_B * GJ_B);
   }
   DevBuf<double> pool(tot + 32), norms((size_t)5 * ndom * 8), probe(nsum + 32);
   for (int d = 0; d < ndom; ++d) {
@@ -1248,14 +992,8 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
     }
     std_.upload(sb, s); dmd.upload(db, s);
     const int nb_ = (int)ds.size();
-    constexpr bool gj_head = false;   // (pinv batches: look-ahead form)
     if (nb_ > GJ_MAX_DOM) raise(MI_ERR_BAD_ARG, "pinv: more than %d blocks in one batch", GJ_MAX_DOM);
-    hipLaunchKernelGGL(k_gj_reset, dim3(cdiv(nb_, 1024)), dim3(1024), 0, s, nb_, dmd.p);
-    for (int kb = 0; kb < nbmax; ++kb) {
-      if (kb == 0 && !gj_head) hipLaunchKernelGGL(k_gj_pivot, dim3(1, 1, nb_), dim3(256), 0, s, 0, kb, nb_, std_.p, dmd.p);   // later pivots: look-ahead in the update
-      const int tx = cdiv(nmax, GJ_T);
-      hipLaunchKernelGGL(k_gj_update<false>, dim3(tx, tx, nb_), dim3(256), 0, s, 0, kb, nb_, std_.p, dmd.p, (unsigned)(kb + 1), tx);
-    }
+    gj_block_steps(s, 0, nbmax, nmax, nb_, std_.p, dmd.p);
     for (size_t k = 0; k < ds.size(); ++k) {
       const int d = ds[k], n = (int)n_gamma_d[d];
       if (!n) continue;

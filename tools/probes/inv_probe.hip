@@ -1,8 +1,6 @@
-// How long do the pieces of the 64 x 64 pivot-block inversion of csrc/setup_gj.hpp take inside a kernel? (wall_clock64 stamps,
-// 100 MHz; one workgroup of 256 threads, as in k_gj_pivot / the look-ahead tile of k_gj_update)
+// How long does the 64 x 64 pivot-block inversion of csrc/setup_gj.hpp take inside a kernel? (wall_clock64 stamps, 100 MHz;
+// one workgroup of 256 threads, as in k_gj_pivot / the look-ahead tile of k_gj_update)
 #include <hip/hip_runtime.h>
-__device__ long long gj_stamps[16 * 8];
-#define GJ_STAMP(i) do { if (threadIdx.x == 0) gj_stamps[s * 8 + (i)] = wall_clock64(); } while (0)
 #include "../../julia-phd-krylov-spdes_amd/csrc/setup_gj.hpp"
 #include "../../julia-phd-krylov-spdes_amd/csrc/pinv_spectral.hpp"
 #include <cstdio>
@@ -10,23 +8,14 @@ using namespace mi;
 __global__ __launch_bounds__(256) void k_probe(const double *A, double *out, long long *stamps) {
   constexpr int LD = GJ_B + 1;
   __shared__ double Mb[GJ_B * LD];
-  __shared__ double Wb[GJ_H * LD + 64];
+  __shared__ double Wb[GJ_SCRATCH];
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) Mb[(e % GJ_B) * LD + e / GJ_B] = A[e];
   __syncthreads();
   long long t0 = wall_clock64();
-  gj_inv32(Mb, LD, 0, Wb + GJ_H * LD);
-  __syncthreads();
+  gj_invert_block64(Mb, LD, Wb, true);
   long long t1 = wall_clock64();
-  gj_inv32(Mb, LD, 32, Wb + GJ_H * LD);     // (not the algorithm: just a second timing of the same routine)
-  __syncthreads();
-  long long t2 = wall_clock64();
-  for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) Mb[(e % GJ_B) * LD + e / GJ_B] = A[e];
-  __syncthreads();
-  long long t3 = wall_clock64();
-  gj_invert_block(Mb, LD, Wb, Wb + GJ_H * LD, true);
-  long long t4 = wall_clock64();
   for (int e = threadIdx.x; e < GJ_B * GJ_B; e += 256) out[e] = Mb[(e % GJ_B) * LD + e / GJ_B];
-  if (threadIdx.x == 0) { stamps[0] = t1 - t0; stamps[1] = t2 - t1; stamps[2] = t4 - t3; }
+  if (threadIdx.x == 0) stamps[0] = t1 - t0;
 }
 int main() {
   const int n = GJ_B;
@@ -38,13 +27,9 @@ int main() {
   for (int rep = 0; rep < 3; ++rep) {
     hipLaunchKernelGGL(k_probe, dim3(1), dim3(256), 0, 0, A, out, st);
     hipDeviceSynchronize();
-    long long s[3]; hipMemcpy(s, st, 24, hipMemcpyDeviceToHost);
-    printf("gj_inv32: %.2f us, again %.2f us; gj_invert_block (64 x 64): %.2f us\n", s[0] / 100.0, s[1] / 100.0, s[2] / 100.0);
+    long long s; hipMemcpy(&s, st, 8, hipMemcpyDeviceToHost);
+    printf("gj_invert_block64 (64 x 64): %.2f us\n", s / 100.0);
   }
-  long long hs[16 * 8]; hipMemcpyFromSymbol(hs, HIP_SYMBOL(gj_stamps), sizeof hs);
-  for (int s = 0; s < 16; s += 5) printf("block step %2d: loads %.2f | inv4 %.2f | panel %.2f | barrier %.2f | mfma+stores %.2f | barrier %.2f us\n", s,
-      s ? (hs[s * 8] - hs[(s - 1) * 8 + 5]) / 100.0 : 0.0, (hs[s * 8 + 1] - hs[s * 8]) / 100.0, (hs[s * 8 + 2] - hs[s * 8 + 1]) / 100.0, (hs[s * 8 + 3] - hs[s * 8 + 2]) / 100.0,
-      (hs[s * 8 + 4] - hs[s * 8 + 3]) / 100.0, (hs[s * 8 + 5] - hs[s * 8 + 4]) / 100.0);
   std::vector<double> o(n * n); hipMemcpy(o.data(), out, n * n * 8, hipMemcpyDeviceToHost);
   double err = 0;   // A * inv - I
   for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { double s = 0; for (int k = 0; k < n; ++k) s += h[i + k * n] * o[k + j * n]; err = fmax(err, fabs(s - (i == j))); }
