@@ -387,6 +387,13 @@ int mi_op_apply_dominant(mi_op_t op, const double *x, int reps);
 /* Diagnostic: average duration (microseconds) of the dominant kernel over `reps` launches replayed from one
  * graph, measured with HIP events on the context's stream (what bench.py reports as roofline.us_per_launch). */
 int mi_op_time_dominant(mi_op_t op, const double *x, int reps, double *us_per_launch);
+/* Synchronises the context's stream, drops every solve graph and iteration prediction captured with the operator (as A or M,
+ * directly or inside a combined or LORASC M), then frees it: an operator created later may live at the same address, with
+ * device arrays at the same addresses, and is a new operator to every solver and plan. NULL is a no-op.
+ * MI_ERR_BAD_ARG, nothing changed, while another live operator borrows this one: a LORASC operator its A_ΓΓ solver ("... live
+ * LORASC operator(s) use this operator; destroy them first"), a combined operator its children ("this operator holds k
+ * place(s) among the children of live combined operator(s) (mi_op_combine); destroy them first"). Destroy the borrower
+ * first. An operator must be destroyed before its context. */
 int mi_op_destroy(mi_op_t op);
 
 /* ---------------------------------------------------------------- BLAS-1 on the device
@@ -529,7 +536,13 @@ int mi_schur_setup_run(mi_setup_t plan, const double *ii_val, const double *ig_v
  * down when the operator is given plan = NULL or another plan, or is destroyed. While the count is above 0
  * mi_schur_setup_destroy returns MI_ERR_BAD_ARG ("... live matrix-free Schur operator(s) solve with this plan; destroy them
  * first"). mi_schur_setup_keep_levels(plan, 0) is not refused for these users: their next interior solve raises
- * MI_ERR_BAD_ARG ("level solves need ...") until the levels are kept and run again. */
+ * MI_ERR_BAD_ARG ("level solves need ...") until the levels are kept and run again. That is safe because nothing of theirs is
+ * captured: a matrix-free Schur operator is never part of a solve graph (its solves run launch by launch), every level solve
+ * checks the plan's state before its first launch, and keep_levels(plan, 0) waits for the stream and destroys the plan's own
+ * level-solve graph before the level storage goes back to the pool.
+ * mi_schur_setup_keep_levels(plan, 0) IS refused (MI_ERR_BAD_ARG, plan unchanged) while a LORASC or a Neumann-Neumann induced
+ * operator is bound to the plan ("... live LORASC operator(s) solve with the kept levels", "... live Neumann-Neumann induced
+ * operator(s) solve with the kept levels"): their level solves are launches inside captured solve graphs. */
 int mi_schur_setup_keep_levels(mi_setup_t plan, int on);
 int mi_schur_setup_interior_solve(mi_setup_t plan, const double *f, double *u);
 int mi_schur_matfree_interior_levels(mi_op_t op, mi_setup_t plan);
@@ -807,8 +820,14 @@ int mi_kl_field_destroy(mi_kl_field_t field);
  *   NULL) describe the final state. A non-finite objective after the first assignment is MI_ERR_BAD_ARG and C is untouched.
  * mi_op_combine — z = Σ_i coef[i] (ops[i] applied to r), i ascending: `InterpolatingPreconditioner` / apply_local_interpolation
  *   (Ex14F:73-97; the coefficients of shepard_interpolating_precond, Ex14F:174-206). 1 <= k <= 16 operators of this context and
- *   of one size; coef: k finite HOST numbers. The children stay the caller's and must outlive the combination (destroying the
- *   combination leaves them usable). apply runs child i into the i-th temporary, then one kernel forms z = z + coef[i] * t_i
+ *   of one size; coef: k finite HOST numbers. The children stay the caller's and the combination borrows them: every place a
+ *   child holds in `ops` (of this and of any other live combination) is counted, and while the count is above 0
+ *   mi_op_destroy(child) returns MI_ERR_BAD_ARG ("... among the children of live combined operator(s) (mi_op_combine);
+ *   destroy them first") and changes nothing. Destroying the combination releases its places and leaves the children usable.
+ *   A refresh of a child that changes the arguments of its launches (mi_lorasc_set_correction, mi_nn_induced_set_coupling)
+ *   also drops the solve graphs captured with a combination that holds it, at any depth; refreshes into the same device
+ *   arrays (every *_set_values, mi_dense_set_blocks, a re-run of a bound plan) need not and do not.
+ *   apply runs child i into the i-th temporary, then one kernel forms z = z + coef[i] * t_i
  *   from z = +0 (product, then sum); it honours the solvers' `done` word, allocates nothing, and is captured into the solve
  *   graphs of mi_pcg, mi_defpcg and the eigCG family iff every child can be.
  * mi_op_combine_set_coefficients — new coefficients (k finite HOST numbers) into the same device array: a captured graph keeps

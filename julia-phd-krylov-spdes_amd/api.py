@@ -348,8 +348,11 @@ class Operator:
         return out.value
 
     def close(self) -> None:
+        """`mi_op_destroy`. The library refuses it while a live `LorascPreconditioner` or `InterpolatingPreconditioner`
+        borrows this operator: MiError, and the handle stays valid — close the borrower first. After `ctx.close()` nothing
+        is called: the handles of a closed context are abandoned, not destroyed."""
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx._L.mi_op_destroy(self._h)
+            check(self.ctx._L.mi_op_destroy(self._h))
         self._h = None
 
     def __del__(self):
@@ -2155,9 +2158,11 @@ def get_quantizer(ctx: Context, n: int, P: int, Λ, distance: str = "L2-full", r
 
 class InterpolatingPreconditioner(Operator):
     """`InterpolatingPreconditioner(coefficients, Πs)` (Ex14F:73-113): `Π \\ r` = Σ_i c_i (Πs[i] \\ r), on the device
-    (`mi_op_combine`), usable as the `M` of pcg and its relatives. 1 to 16 operators of one context and one size; they must
-    outlive this object (it keeps references to them). A non-finite coefficient — what `fem.shepard_coefficients` gives at
-    zero distance — raises ValueError."""
+    (`mi_op_combine`), usable as the `M` of pcg and its relatives. 1 to 16 operators of one context and one size. This
+    object keeps references to them, and the library counts them: `close()` of a child raises MiError until every
+    combination that holds it is closed. A child may be refreshed under a live combination (`set_values`, `set_correction`,
+    `set_coupling`, ...): the next solve uses its new state. A non-finite coefficient — what `fem.shepard_coefficients`
+    gives at zero distance — raises ValueError."""
 
     def __init__(self, ctx: Context, coefficients, Πs: Sequence[Operator]):
         coef = self._coef(coefficients)
@@ -2184,6 +2189,10 @@ class InterpolatingPreconditioner(Operator):
             raise ValueError(f"{coef.size} coefficients for {len(self.Πs)} operators")
         check(self.ctx._L.mi_op_combine_set_coefficients(self._h, coef.ctypes.data_as(f64p)))
         self.coefficients = coef
+
+    def close(self) -> None:
+        super().close()                 # before the children it borrows
+        self._keep, self.Πs = (), []
 
 
 def get_centroidal_preconds(ctx: Context, centroids, field: KLField, assemble: Callable, A0, **amg_kw):

@@ -74,5 +74,6 @@ struct mi_plan_s {
   mi::DevBuf<unsigned> inc_pos;
   mi::DevBuf<double> points, b_stage;
   std::vector<int> rowptr_h, colidx_h;   // the pattern, to compare an operator's with (mi_full_assembly_update)
-  const void *checked_op = nullptr;      // the operator's device column array that has been compared, and found equal
+  unsigned long long checked_serial = 0; // Operator::serial of the operator whose pattern has been compared, and found equal (0: none;
+                                         // not an address: a new operator may live where a closed one did, arrays included)
 };

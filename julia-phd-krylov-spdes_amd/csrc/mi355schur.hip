@@ -901,6 +901,8 @@ int mi_op_time_dominant(mi_op_t op, const double *x, int reps, double *us_per_la
 int mi_op_destroy(mi_op_t op) {
   if (!op) return MI_OK;
   if (op->bound > 0) return fail(MI_ERR_BAD_ARG, "mi_op_destroy: %d live LORASC operator(s) use this operator; destroy them first", op->bound);
+  if (op->bound_combine > 0)
+    return fail(MI_ERR_BAD_ARG, "mi_op_destroy: this operator holds %d place(s) among the children of live combined operator(s) (mi_op_combine); destroy them first", op->bound_combine);
   return guarded([&]() -> int {
     if (op->impl) {
       mi_ctx_s *c = op->impl->ctx;
@@ -1459,15 +1461,15 @@ int mi_op_combine(mi_ctx_t ctx, int64_t k, const mi_op_t *ops, const double *coe
   if (k < 1 || k > 16) return fail(MI_ERR_BAD_ARG, "%s: k = %lld operators (1 <= k <= 16)", me, (long long)k);
   if (!ops) return fail(MI_ERR_BAD_ARG, "%s: ops is NULL", me);
   if (int rc = combine_coef_check(me, k, coef)) return rc;
-  std::vector<Operator *> kids;
+  std::vector<mi_op_s *> kids;
   for (int64_t i = 0; i < k; ++i) {
     if (!ops[i] || !ops[i]->impl) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is NULL", me, (long long)i);
     Operator *o = ops[i]->impl.get();
     if (o->ctx != ctx) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] belongs to another context", me, (long long)i);
     if (o->n != ops[0]->impl->n) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is of size %lld, ops[0] of size %lld", me, (long long)i, (long long)o->n, (long long)ops[0]->impl->n);
-    kids.push_back(o);
+    kids.push_back(ops[i]);
   }
-  const int64_t n = kids[0]->n;
+  const int64_t n = kids[0]->impl->n;
   MI_NEW_OP(ctx, op, new CombineOp(ctx, n, kids, coef));
 }
 int mi_op_combine_set_coefficients(mi_op_t op, const double *coef) {
@@ -1615,13 +1617,13 @@ int mi_full_assembly_update(mi_plan_t plan, const double *a_nodal, mi_op_t A, do
                 (long long)op->A.nnz, plan->n, plan->n, (long long)plan->nnz);
   return guarded([&]() -> int {
     c->use();
-    if (plan->checked_op != (const void *)op->A.col.p) {   // once per operator: the whole pattern (synchronous)
+    if (plan->checked_serial != op->serial) {   // once per operator: the whole pattern (synchronous)
       std::vector<int> rp((size_t)plan->n + 1), ci((size_t)plan->nnz);
       MI_HIP(hipMemcpyAsync(rp.data(), op->A.rowptr.p, rp.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
       if (plan->nnz) MI_HIP(hipMemcpyAsync(ci.data(), op->A.col.p, ci.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
       MI_HIP(hipStreamSynchronize(c->stream));
       if (rp != plan->rowptr_h || ci != plan->colidx_h) return fail(MI_ERR_BAD_ARG, "%s: the pattern of A is not the plan's", me);
-      plan->checked_op = op->A.col.p;
+      plan->checked_serial = op->serial;
     }
     In ai(c, a_nodal, (size_t)plan->n_node, plan->a_stage);
     InOut bo(c, b, (size_t)plan->n, plan->b_stage, false);

@@ -33,9 +33,13 @@ inline int to_i32(int64_t v, int64_t lo, int64_t hi, const char *what) {
 // ------------------------------------------------------------------ base class
 inline std::atomic<long long> &folded_pcg_launches() { static std::atomic<long long> n{0}; return n; }   // k_gemv_pcg launches issued (mi_ctx_query)
 struct DenseBlockOp;
+inline unsigned long long next_operator_serial() { static std::atomic<unsigned long long> n{0}; return ++n; }
 struct Operator {
   mi_ctx_s *ctx;
   int64_t n;  // operator is n x n on the Γ (or full) vector space
+  // Who this operator is, for anything that remembers it beyond its life: unique in the process and never handed out again,
+  // which its address and the addresses of its device arrays are not (DevPool and malloc reuse both). Starts at 1.
+  const unsigned long long serial = next_operator_serial();
   // Set by a solver around the `A*x0` of its set-up: device flag "x0 is identically zero" (the result is then +0
   // without streaming A). Operators that cannot use it ignore it.
   const int *zero_hint = nullptr;
@@ -65,6 +69,9 @@ struct Operator {
   virtual DenseBlockOp *as_dense() { return nullptr; }
   virtual struct CsrDev *as_csr() { return nullptr; }  // a plain sparse matrix (config 2): rows, row blocks, values
   virtual bool graph_safe() const { return true; }  // false: apply synchronises with the host
+  // true: the launches of apply() include those of `o` — `o` is this operator or one it applies through a borrowed handle
+  // (CombineOp's children, LorascOp's A_ΓΓ solver). A graph captured with this operator holds o's launch arguments.
+  virtual bool uses(const Operator *o) const { return o == this; }
   // true: y is written exactly once, by the last kernel of apply(), and never read — it may then be pinned host memory
   virtual bool writes_y_once() const { return true; }
   virtual void bytes(int64_t *apply_b, int64_t *dominant_b) const = 0;
@@ -1174,5 +1181,6 @@ struct GlobalSchurOp : InteriorSchurOp {
 struct mi_op_s {
   std::unique_ptr<mi::Operator> impl;
   mi::DevBuf<double> hx, hy;  // staging for host-pointer mode
-  int bound = 0;              // operators that borrow this one (lorasc.hpp): mi_op_destroy is refused while > 0
+  int bound = 0;              // LORASC operators that borrow this one (lorasc.hpp): mi_op_destroy is refused while > 0
+  int bound_combine = 0;      // ... and the places it holds among the children of live combined operators (vq.hpp CombineOp)
 };

@@ -118,8 +118,11 @@ struct SolverWorkspace {
     for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
     graphs.clear();
   }
+  // Every graph, and every prediction, of a solve whose A or M is `op` or applies `op` (Operator::uses): a graph of a
+  // combined M holds the launch arguments of its children. The operators of the keys are alive: mi_op_destroy calls
+  // this before it deletes one, and refuses an operator that another one borrows.
   void drop_graphs_of(const Operator *op) {
-    auto of_op = [op](const GraphKey &k) { return k.A == op || k.M == op; };
+    auto of_op = [op](const GraphKey &k) { return (k.A && k.A->uses(op)) || (k.M && k.M->uses(op)); };
     for (auto &kv : graphs) if (of_op(kv.first)) (void)hipGraphExecDestroy(kv.second);
     auto erase_of = [&](auto &map) { for (auto it = map.begin(); it != map.end();) it = of_op(it->first) ? map.erase(it) : std::next(it); };
     erase_of(graphs); erase_of(predicted); erase_of(zero_x0);

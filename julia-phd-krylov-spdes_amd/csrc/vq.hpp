@@ -512,13 +512,28 @@ struct VqArg {
 // ------------------------------------------------------------------ z = Σ_i c_i (Π_i \ r)
 // `InterpolatingPreconditioner` (Example14_QuantizationAndShepardLocalInterpolation_Functions.jl:73-113). The children stay the
 // caller's; apply runs child i into the i-th temporary, then one k_lincomb. Nothing is allocated or synchronised in apply.
+// The children are borrowed through their handles: every place a handle holds among `kid_h` is counted in its
+// `bound_combine`, which refuses mi_op_destroy of a child while this operator lives (a child in two combinations, or twice
+// in one, is released when the last place is gone).
 struct CombineOp : Operator {
-  std::vector<Operator *> kids;
+  std::vector<mi_op_s *> kid_h;
+  std::vector<Operator *> kids;   // kid_h[i]->impl
   DevBuf<double> coef, tmp;   // k; k x n
-  CombineOp(mi_ctx_s *c, int64_t n_, std::vector<Operator *> kids_, const double *cf) : Operator(c, n_), kids(std::move(kids_)) {
+  CombineOp(mi_ctx_s *c, int64_t n_, std::vector<mi_op_s *> kid_h_, const double *cf) : Operator(c, n_), kid_h(std::move(kid_h_)) {
+    for (mi_op_s *h : kid_h) kids.push_back(h->impl.get());
     coef.alloc(kids.size());
     tmp.alloc(kids.size() * (size_t)n_);
     set_coefficients(cf);
+    for (mi_op_s *h : kid_h) ++h->bound_combine;   // last: nothing above may leave a count behind
+  }
+  ~CombineOp() override {
+    for (mi_op_s *h : kid_h) --h->bound_combine;
+  }
+  bool uses(const Operator *o) const override {
+    if (o == this) return true;
+    for (const Operator *k : kids)
+      if (k->uses(o)) return true;
+    return false;
   }
   // a blocking copy on the context's stream: it is ordered after the solves already enqueued, and a captured graph reads the
   // same device array afterwards
