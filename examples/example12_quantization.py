@@ -13,11 +13,15 @@ Example20_QuantizedPreconditioner.jl in one driver, at small default sizes, on t
 
 The iteration counts are printed beside those of the constant preconditioner of ξ = 0 (Example06's Π_amg_0).
 
+`--bank`: the same flow on ONE `api.AMGBank` (`api.get_centroidal_bank`): the P hierarchies share one plan and
+one set of index arrays, `view.select(p)` / `view.combine(near, coef)` stand for `Π[p]` / `InterpolatingPreconditioner`, and
+one captured solve graph serves every selection. The iteration counts are those of the default flow.
+
 `--device-assembly`: every system, the centroids' and the realizations', is assembled on the device
 (`api.FullAssemblyPlan`, bit-identical to the host assembly), and ONE `A_op` is refreshed in place per realization.
 
     python examples/example12_quantization.py [--N 60] [--ns 2000] [--P 8] [--nreals 5] [--distance L2-full] [--interpolate 4]
-                                              [--device-assembly]
+                                              [--device-assembly] [--bank]
 """
 import argparse
 import os
@@ -41,7 +45,10 @@ def main():
     ap.add_argument("--interpolate", type=int, default=0, help="k > 0: Shepard combination of the k nearest centroids' preconditioners")
     ap.add_argument("--seed", type=int, default=987654321)
     ap.add_argument("--device-assembly", action="store_true", help="assemble on the device and refresh one A_op in place")
+    ap.add_argument("--bank", action="store_true", help="hold the centroidal hierarchies in one AMGBank and select through a view")
     args = ap.parse_args()
+    if args.bank and min(args.interpolate, args.P) > 16:
+        ap.error(f"--bank: a view combines at most 16 members, --interpolate {args.interpolate} with --P {args.P} asks for {min(args.interpolate, args.P)}")
     pkg = graft.load_package()
     fem, api = pkg.fem, pkg.api
     mesh = fem.get_mesh(args.N)
@@ -65,8 +72,17 @@ def main():
         plan = api.FullAssemblyPlan(ctx, fem.make_full_assembly_plan(mesh.cells, mesh.points, dinds, mesh.point_marker, f, uexact))
         A_t = api.SparseMatrixCSC(ctx, A_0)
     t = time.perf_counter()
-    Π = api.get_centroidal_preconds(ctx, centroids, field, (lambda a: plan.run(a)[0]) if plan else (lambda a: system(a)[0]), A_0)
-    print(f"{args.P} centroidal AMG preconditioners (n = {A_0.shape[0]}) in {time.perf_counter() - t:.2f} s")
+    assemble = (lambda a: plan.run(a)[0]) if plan else (lambda a: system(a)[0])
+    bank = view = None
+    if args.bank:
+        bank = api.get_centroidal_bank(ctx, centroids, field, assemble, A_0)
+        view = bank.view(max(1, min(args.interpolate, args.P)))
+        st = bank.stats()
+        print(f"{args.P} centroidal AMG hierarchies (n = {A_0.shape[0]}) on one bank in {time.perf_counter() - t:.2f} s: "
+              f"{st['bytes_shared']} bytes shared, {st['bytes_per_member']} per member")
+    else:
+        Π = api.get_centroidal_preconds(ctx, centroids, field, assemble, A_0)
+        print(f"{args.P} centroidal AMG preconditioners (n = {A_0.shape[0]}) in {time.perf_counter() - t:.2f} s")
     Π_0 = api.AMGPreconditioner(ctx, A_0)
 
     scaled_centroids = fem.scale_data(centroids, kl.Λ, args.distance)
@@ -89,22 +105,32 @@ def main():
             full = np.zeros((kl.Λ.size, near.size))
             full[:rows] = centroids[:, near]
             coef = fem.shepard_coefficients(ξ, full, kl.Λ)
-            M = api.InterpolatingPreconditioner(ctx, coef, [Π[p] for p in near])
+            if bank:
+                view.combine(near, coef)
+                M = view
+            else:
+                M = api.InterpolatingPreconditioner(ctx, coef, [Π[p] for p in near])
             what = f"Shepard combination of centroids {near.tolist()} (nearest at squared distance {float(dist2[0]):.3e})"
         else:
             p = api.find_precond(ctx, η, scaled_centroids)
-            M = Π[p]
+            if bank:
+                view.select(p)
+                M = view
+            else:
+                M = Π[p]
             what = f"centroid {p}"
         u, it_q, _ = api.pcg(A_op, b, x0, M)
         _, it_0, _ = api.pcg(A_op, b, x0, Π_0)
         iters_q.append(int(it_q)); iters_0.append(int(it_0))
         print(f"realization {ireal}: {what}: pcg it = {it_q} (ξ = 0 preconditioner: {it_0}), |b - A u| / |b| = "
               f"{np.linalg.norm(b - A_op * u) / np.linalg.norm(b):.3e}")
-        if args.interpolate > 0:
+        if args.interpolate > 0 and not bank:
             M.close()
         if not plan:
             A_op.close()
     print(f"iters_quantized = {iters_q}\niters_xi_0 = {iters_0}")
+    if bank:
+        bank.close()
 
 
 if __name__ == "__main__":

@@ -113,6 +113,7 @@ int mi_ctx_set_exchange(mi_ctx_t ctx, int use_peer_exchange);
 #define MI_QUERY_EXPERIMENTAL 5    /* always 0: the EXPERIMENTAL build (persistent on-chip PCG, rocBLAS/rocSOLVER set-up route) was removed */
 #define MI_QUERY_SPECTRAL_PINV 4   /* blocks of mi_nn_pinv that went to the eigen-decomposition (rocSOLVER) so far, process-wide */
 #define MI_QUERY_FOLDED_PCG 6      /* launches of the folded PCG kernel issued (captured or direct) so far, process-wide */
+#define MI_QUERY_GRAPH_CAPTURES 7  /* graphs the solvers have captured on this context so far (a solve that replays a cached graph adds none) */
 int mi_ctx_query(mi_ctx_t ctx, int what, int64_t *out);
 /* Test facility: in-process ranks. `n_ranks` contexts of ONE process (one host thread each, typically all on the same
  * device) call mi_ctx_loopback_init with the same group and then behave like ranks of a multi-GPU job: operators built
@@ -253,6 +254,53 @@ int mi_amg_level_get(mi_op_t op, int64_t level, int64_t *a_rowptr, int64_t *a_co
                      int64_t *p_colidx, double *p_val, double *omega, double *omega_over_d);
 int mi_amg_coarse_inverse(mi_op_t op, double *coarse_inv);
 int mi_amg_refresh_profile(mi_op_t op, double *ms /* 6 */);
+
+/* mi_amg_bank_* — P hierarchies of mi_amg_plan_create on ONE plan (amg_bank.hpp): the constant preconditioners of the
+ * quantization studies, one per centroid on frozen aggregates (`get_centroidal_preconds`, Example12_…_Functions.jl:85-113;
+ * Examples 13, 14, 18, 20). The plan, the index arrays and row blocks of every A_l, P_l, R_l and the numeric set-up engine
+ * (candidate buffers, dense work) are held once; a member is numbers only, one slot of a value slab that is allocated at
+ * creation and never moves. Every handle is an mi_op_t; members are 0-based.
+ *   create     : as mi_amg_plan_create without `val` (HOST arrays, `index_base`-based), and `capacity` >= 1 slots. No member
+ *                is set yet. The bank is NOT applicable: mi_op_apply, mi_op_combine and every solver refuse it with
+ *                MI_ERR_BAD_ARG before any launch; mi_op_size gives n. mi_op_destroy is refused (MI_ERR_BAD_ARG, "... live
+ *                view(s) (mi_amg_bank_view) borrow this AMG bank; destroy them first") while a view lives. A slab that does
+ *                not fit is MI_ERR_HIP, the message naming the bytes asked for.
+ *   set_values : the numeric chain of mi_amg_set_values on `val` (host or device pointer per the context's pointer mode, on
+ *                the pattern of create), then — only on success — the result is copied into the member's slot. Synchronous.
+ *                MI_ERR_SINGULAR leaves the slot bit for bit as it was; a slot never set stays unset.
+ *   view       : an operator of size n that borrows the bank, usable wherever an AMG operator is (M of mi_pcg, mi_defpcg,
+ *                mi_eigpcg, mi_eigdefpcg, mi_initpcg; a child of mi_op_combine; mi_op_apply), with its own level vectors for
+ *                `max_terms` (1 .. 16) members. z = Σ_i coef[i] (Π_{members[i]} \ r), i ascending as mi_op_combine sums: the
+ *                V(1,1) cycles of all k members in ONE sequence of 4 (nlevels - 1) + 1 launches (the member is the grid's
+ *                second dimension) and one combination launch. A member's cycle has the bits of the operator of
+ *                mi_amg_plan_create / mi_amg_set_values on the same values. A new view selects k = 1, member 0, coefficient 1.
+ *   select     : k HOST member indices and k finite HOST coefficients into the view's device arrays, a blocking copy on the
+ *                context's stream. The kernels read k and the members on the device, so solve graphs captured with the view
+ *                stay valid and the next solve uses the new selection.
+ *   stats      : capacity; members set so far; bytes_shared (mi_amg_stats' bytes_kept of the engine: patterns, plan,
+ *                candidates, work and the buffers a member is staged in); views alive; and
+ *                  bytes_per_member = 8 (Σ_l nnz(A_l) + 2 Σ_{l<L-1} nnz(P_l) + Σ_{l<L-1} n_l + n_c² + 2 (L - 1)) + padding,
+ *                L = nlevels, for the values of every A_l (the coarsest as given, for the read-back), of P_l and R_l, ω_l/d, the
+ *                coarse inverse and the (ω_l, g_l) pairs. padding = 8 bytes for every one of the arrays A_l (L of them), P_l,
+ *                R_l, ω_l/d (L - 1 each) and the inverse whose count of doubles is odd: each array is padded to an even
+ *                count, so every array of every member starts on a 16-byte boundary (the cycle loads values in pairs).
+ *   level_sizes / level_get / coarse_inverse: the read-back of mi_amg_level_sizes / mi_amg_level_get /
+ *                mi_amg_coarse_inverse for one member (the sizes are those of every member).
+ * MI_ERR_BAD_ARG, the message naming the numbers: everything mi_amg_plan_create refuses; capacity < 1; a member outside
+ * 0 .. capacity - 1; a selected or read member that was never set — at select, and at apply or solve entry when the default
+ * member 0 is unset; k < 1 or k > max_terms; max_terms outside 1 .. 16; a coefficient that is not finite; a handle of the wrong
+ * kind; a context that is one rank of several. */
+int mi_amg_bank_create(mi_ctx_t ctx, int64_t n, const int64_t *rowptr, const int64_t *colidx, int64_t nlevels, const int64_t *n_l,
+                       const int64_t *const *agg /* [nlevels - 1] */, int64_t capacity, int index_base, mi_op_t *bank);
+int mi_amg_bank_set_values(mi_op_t bank, int64_t member, const double *val);
+int mi_amg_bank_view(mi_op_t bank, int64_t max_terms, mi_op_t *view);
+int mi_amg_bank_select(mi_op_t view, int64_t k, const int64_t *members, const double *coef);
+int mi_amg_bank_stats(mi_op_t bank, int64_t *capacity, int64_t *members_set, int64_t *bytes_shared, int64_t *bytes_per_member,
+                      int64_t *views);
+int mi_amg_bank_level_sizes(mi_op_t bank, int64_t level, int64_t *n_rows, int64_t *n_cols, int64_t *a_nnz, int64_t *p_nnz);
+int mi_amg_bank_level_get(mi_op_t bank, int64_t member, int64_t level, int64_t *a_rowptr, int64_t *a_colidx, double *a_val,
+                          int64_t *p_rowptr, int64_t *p_colidx, double *p_val, double *omega, double *omega_over_d);
+int mi_amg_bank_coarse_inverse(mi_op_t bank, int64_t member, double *coarse_inv);
 
 /* mi_schur_assembled_create — `apply_local_schurs(Sd, ind_Γd_Γ2l, node_Γ_cnt, x)`, EPDD.jl:761-785:
  * Sx = Σ_d R_d' S_d R_d x with dense local Schur complements.

@@ -63,6 +63,14 @@ SIGNATURES = {
     "mi_amg_level_get": [vp, i64, i64p, i64p, f64p, i64p, i64p, f64p, f64p, f64p],
     "mi_amg_coarse_inverse": [vp, f64p],
     "mi_amg_refresh_profile": [vp, f64p],
+    "mi_amg_bank_create": [vp, i64, i64p, i64p, i64, i64p, i64pp, i64, C.c_int, C.POINTER(vp)],
+    "mi_amg_bank_set_values": [vp, i64, vp],
+    "mi_amg_bank_view": [vp, i64, C.POINTER(vp)],
+    "mi_amg_bank_select": [vp, i64, i64p, f64p],
+    "mi_amg_bank_stats": [vp, i64p, i64p, i64p, i64p, i64p],
+    "mi_amg_bank_level_sizes": [vp, i64, i64p, i64p, i64p, i64p],
+    "mi_amg_bank_level_get": [vp, i64, i64, i64p, i64p, f64p, i64p, i64p, f64p, f64p, f64p],
+    "mi_amg_bank_coarse_inverse": [vp, i64, f64p],
     "mi_schur_assembled_create": [vp, i64, i64, i64p, i64pp, f64pp, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_nn_create": [vp, i64, i64, i64p, i64pp, f64pp, i64p, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_nn_create_stored": [vp, i64, i64, i64p, i64pp, f64pp, i64p, C.c_int, i64, i64, C.c_int, C.POINTER(vp)],

@@ -184,9 +184,10 @@ class Context:
         check(self._L.mi_ctx_set_exchange(self._h, C.c_int(int(mode))))
 
     def query(self, what: str) -> int:
-        """`mi_ctx_query`: "no_graph", "peer_exchange", "graph_replays", "exchanges", "spectral_pinv", "experimental", "folded_pcg"."""
+        """`mi_ctx_query`: "no_graph", "peer_exchange", "graph_replays", "exchanges", "spectral_pinv", "experimental", "folded_pcg",
+        "graph_captures"."""
         out = i64(0)
-        check(self._L.mi_ctx_query(self._h, C.c_int({"no_graph": 0, "peer_exchange": 1, "graph_replays": 2, "exchanges": 3, "spectral_pinv": 4, "experimental": 5, "folded_pcg": 6}[what]), C.byref(out)))
+        check(self._L.mi_ctx_query(self._h, C.c_int({"no_graph": 0, "peer_exchange": 1, "graph_replays": 2, "exchanges": 3, "spectral_pinv": 4, "experimental": 5, "folded_pcg": 6, "graph_captures": 7}[what]), C.byref(out)))
         return int(out.value)
 
     def peer_connect(self, rank: int, n_ranks: int, all_gather) -> None:
@@ -2211,3 +2212,203 @@ def get_centroidal_preconds(ctx: Context, centroids, field: KLField, assemble: C
         M.set_values(assemble(field.coefficient(ξ)))
         Π.append(M)
     return Π
+
+
+# ------------------------------------------------------------------ P hierarchies on one plan
+AMG_BANK_MAX_TERMS = 16
+
+
+def amg_bank_member_bytes(H) -> int:
+    """`bytes_per_member` of `mi_amg_bank_stats` for the level matrices `H.A`, `H.P` of a `fem.AmgHierarchy` on the structural
+    patterns (`fem.amg_refresh(aggregates, A)`, `AMGBank.device_hierarchy(p)`): 8 (Σ_l nnz(A_l) + 2 Σ_{l<L-1} nnz(P_l) +
+    Σ_{l<L-1} n_l + n_c² + 2 (L - 1)) plus 8 bytes for every array of an odd count of doubles."""
+    L = len(H.A)
+    counts = [int(a.indices.size) for a in H.A]
+    counts += [int(p.indices.size) for p in H.P] * 2
+    counts += [int(a.shape[0]) for a in H.A[:L - 1]]
+    counts.append(int(H.A[-1].shape[0]) ** 2)
+    return 8 * (sum(c + (c & 1) for c in counts) + 2 * (L - 1))
+
+
+def _csr_values(v):
+    if sp.issparse(v):
+        v = sp.csr_matrix(v)
+        v.sum_duplicates()
+        v.sort_indices()
+        v = _f64(v.data)
+    return v
+
+
+class AMGBank:
+    """`capacity` smoothed-aggregation hierarchies on the pattern and the frozen aggregates of `A0`, sharing ONE plan, one set
+    of index arrays and one set-up engine on the device (`mi_amg_bank_create`): the constant preconditioners of the
+    quantization studies (`get_centroidal_preconds`, Ex12F:85-113) at a P where separate `AMGPreconditioner` objects do not
+    fit. A member is numbers only. `aggregates=[agg_0, …]` (0-based, one array per smoothed level) come from
+    `fem.prepare_amg_precond(A0, **amg_kw)` unless given. The bank is not an operator: solve and apply with `.view()`.
+    Members are 0-based."""
+
+    def __init__(self, ctx: Context, A0, capacity: int, index_base: int = 0, aggregates=None, **amg_kw):
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError(f"capacity = {capacity}: a bank holds at least 1 member")
+        if index_base not in (0, 1):
+            raise ValueError(f"index_base = {index_base} (0 or 1)")
+        if not (sp.issparse(A0) or isinstance(A0, np.ndarray)):
+            raise TypeError("AMGBank takes the matrix whose pattern every member shares")
+        A = sp.csr_matrix(A0)
+        A.sum_duplicates()
+        A.sort_indices()
+        if A.shape[0] != A.shape[1]:
+            raise ValueError("square matrix expected")
+        if aggregates is not None:
+            if amg_kw:
+                raise TypeError(f"set-up options {sorted(amg_kw)} with aggregates that are already chosen")
+            agg0 = [_i64(a).ravel() for a in aggregates]
+            sizes = [A.shape[0]] + [int(a.max()) + 1 if a.size else 0 for a in agg0]
+        else:
+            from . import fem
+            H = fem.prepare_amg_precond(A, **amg_kw)
+            agg0, sizes = [_i64(a).ravel() for a in H.agg], list(H.sizes)
+        aggs = [a + index_base for a in agg0]
+        n_l = _i64(sizes)
+        ptr, idx = _i64(A.indptr) + index_base, _i64(A.indices) + index_base
+        h = vp()
+        check(ctx._L.mi_amg_bank_create(ctx._h, i64(A.shape[0]), ptr.ctypes.data_as(i64p), idx.ctypes.data_as(i64p), i64(len(sizes)),
+                                        n_l.ctypes.data_as(i64p), _ptrs(aggs, i64p) if aggs else None, i64(capacity),
+                                        C.c_int(index_base), C.byref(h)))
+        self.ctx, self._h = ctx, h
+        self.n, self.nnz, self.capacity, self.n_levels = int(A.shape[0]), int(A.indices.size), capacity, len(sizes)
+        self.aggregates = list(agg0)
+        self._views = []
+
+    def _member(self, p) -> int:
+        q = int(p)
+        if q != p or not 0 <= q < self.capacity:
+            raise IndexError(f"member {p} outside 0 .. {self.capacity - 1}")
+        return q
+
+    def set_values(self, p: int, A_or_nzval) -> None:
+        """The hierarchy of member `p` from a matrix on the pattern of `A0`: a scipy sparse matrix, or its CSR values as a numpy
+        array or a torch CUDA tensor (`mi_amg_bank_set_values`). Synchronous. MiError(MI_ERR_SINGULAR) leaves the member as
+        it was (unset, if it never was set)."""
+        p = self._member(p)
+        v = _csr_values(A_or_nzval)
+        count = v.numel() if _is_torch(v) else np.size(v)
+        if count != self.nnz:
+            raise ValueError(f"{count} values for the {self.nnz} stored entries of the bank's pattern")
+        self.ctx._mode_for(v)
+        k, ptr = self.ctx._ptr(v, self.nnz)
+        self.ctx._order((k,), after=False)
+        check(self.ctx._L.mi_amg_bank_set_values(self._h, i64(p), ptr))   # synchronous
+
+    def view(self, max_terms: int = 1) -> "AMGBankView":
+        """An operator on this bank for up to `max_terms` (1 .. 16) members at a time; it selects member 0 at first."""
+        v = AMGBankView(self, max_terms)
+        self._views.append(v)
+        return v
+
+    def stats(self) -> dict:
+        """dict(capacity, members_set, bytes_shared, bytes_per_member, views) (`mi_amg_bank_stats`)"""
+        a, b, c, d, e = i64(), i64(), i64(), i64(), i64()
+        check(self.ctx._L.mi_amg_bank_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)))
+        return dict(capacity=int(a.value), members_set=int(b.value), bytes_shared=int(c.value), bytes_per_member=int(d.value),
+                    views=int(e.value))
+
+    def device_hierarchy(self, p: int):
+        """Member `p` as the device holds it, a `fem.AmgHierarchy` (`mi_amg_bank_level_sizes`, `mi_amg_bank_level_get`,
+        `mi_amg_bank_coarse_inverse`)."""
+        from . import fem
+        p = self._member(p)
+        L = self.ctx._L
+        As, Ps, om, owd = [], [], [], []
+        for l in range(self.n_levels):
+            n, m, an, pn = i64(), i64(), i64(), i64()
+            check(L.mi_amg_bank_level_sizes(self._h, i64(l), C.byref(n), C.byref(m), C.byref(an), C.byref(pn)))
+            n, m, an, pn = int(n.value), int(m.value), int(an.value), int(pn.value)
+            ap, ai, av = np.zeros(n + 1, dtype=np.int64), np.zeros(an, dtype=np.int64), np.zeros(an)
+            pp, pi, pv = np.zeros(n + 1, dtype=np.int64), np.zeros(pn, dtype=np.int64), np.zeros(pn)
+            w, wd = C.c_double(0.0), np.zeros(n)
+            check(L.mi_amg_bank_level_get(self._h, i64(p), i64(l), ap.ctypes.data_as(i64p), ai.ctypes.data_as(i64p),
+                                          av.ctypes.data_as(f64p), pp.ctypes.data_as(i64p), pi.ctypes.data_as(i64p),
+                                          pv.ctypes.data_as(f64p), C.byref(w), wd.ctypes.data_as(f64p)))
+            As.append(sp.csr_matrix((av, ai, ap), shape=(n, n)))
+            if l < self.n_levels - 1:
+                Ps.append(sp.csr_matrix((pv, pi, pp), shape=(n, m)))
+                om.append(float(w.value)); owd.append(wd)
+        nc = As[-1].shape[0]
+        inv = np.zeros((nc, nc), order="F")
+        check(L.mi_amg_bank_coarse_inverse(self._h, i64(p), inv.ctypes.data_as(f64p)))
+        nnz = [a.indices.size for a in As]
+        return fem.AmgHierarchy(As, Ps, om, owd, inv, [a.shape[0] for a in As], float(sum(nnz)) / float(nnz[0]), self.aggregates)
+
+    def close(self) -> None:
+        """`mi_op_destroy` of the bank, after its views that are still open (the library refuses a bank under a live view)."""
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            for v in list(self._views):
+                v.close()
+            check(self.ctx._L.mi_op_destroy(self._h))
+        self._h, self._views = None, []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AMGBankView(Operator):
+    """`bank.view(max_terms)`: `Π \\ r` = Σ_i c_i (Π_{m_i} \\ r) over members of an `AMGBank` (`mi_amg_bank_view`), usable as the
+    `M` of pcg and its relatives, as a child of `InterpolatingPreconditioner` and through `.ldiv(r)`. `.select(p)` is the
+    `Πs[find_precond(ξ, hXt)]` of Example12, `.combine(members, coefficients)` the `InterpolatingPreconditioner` of
+    Example14 — both rewrite small device arrays, so the solve graphs captured with the view serve every selection."""
+
+    def __init__(self, bank: AMGBank, max_terms: int = 1):
+        kmax = int(max_terms)
+        if kmax != max_terms or not 1 <= kmax <= AMG_BANK_MAX_TERMS:
+            raise ValueError(f"max_terms = {max_terms} (1 <= max_terms <= {AMG_BANK_MAX_TERMS})")
+        if not getattr(bank, "_h", None):
+            raise ValueError("the bank is closed")
+        h = vp()
+        check(bank.ctx._L.mi_amg_bank_view(bank._h, i64(kmax), C.byref(h)))
+        super().__init__(bank.ctx, h, keep=(bank,))
+        self.bank, self.max_terms = bank, kmax
+        self.members, self.coefficients = np.zeros(1, dtype=np.int64), np.ones(1)
+
+    def select(self, p: int) -> None:
+        """One member, coefficient 1."""
+        self.combine([p], [1.0])
+
+    def combine(self, members, coefficients) -> None:
+        """k members (1 <= k <= max_terms, each set before; one may appear twice) and k finite coefficients
+        (`mi_amg_bank_select`)."""
+        mem = [self.bank._member(p) for p in np.asarray(members).ravel().tolist()]
+        coef = _f64(coefficients).ravel()
+        if not 1 <= len(mem) <= self.max_terms:
+            raise ValueError(f"k = {len(mem)} members (1 <= k <= max_terms = {self.max_terms})")
+        if coef.size != len(mem):
+            raise ValueError(f"{coef.size} coefficients for {len(mem)} members")
+        if not np.all(np.isfinite(coef)):
+            raise ValueError("a coefficient is not finite (Shepard weights at zero distance?)")
+        mem = _i64(mem)
+        check(self.ctx._L.mi_amg_bank_select(self._h, i64(mem.size), mem.ctypes.data_as(i64p), coef.ctypes.data_as(f64p)))
+        self.members, self.coefficients = mem, coef
+
+    def close(self) -> None:
+        super().close()
+        bank = getattr(self, "bank", None)
+        if bank is not None and self in bank._views:
+            bank._views.remove(self)
+        self._keep = ()
+
+
+def get_centroidal_bank(ctx: Context, centroids, field: KLField, assemble: Callable, A0, **amg_kw) -> AMGBank:
+    """`get_centroidal_preconds` on a bank: member p is the constant AMG preconditioner of centroid p (column p of
+    `centroids`, zero-padded to the field's modes), `assemble(a)` as there. One plan, one set of index arrays, P slots of
+    numbers: `bank.view().select(find_precond(ctx, ξ, hXt))` is the `Πs[p]` of Example12:106."""
+    centroids = np.asarray(centroids, dtype=np.float64)
+    bank = AMGBank(ctx, A0, centroids.shape[1], **amg_kw)
+    for p in range(centroids.shape[1]):
+        ξ = np.zeros(field.m)
+        ξ[:centroids.shape[0]] = centroids[:, p]
+        bank.set_values(p, assemble(field.coefficient(ξ)))
+    return bank

@@ -160,7 +160,8 @@ struct AmgPlanOp : AmgOp {
 
   AmgPlanOp(mi_ctx_s *c, int64_t n0, const int64_t *rowptr, const int64_t *colidx, const double *val, int64_t nlevels, const int64_t *n_l,
             const int64_t *const *agg, int base, const std::vector<int> *breaks0 = nullptr)
-      : AmgOp(c, n0) {   // breaks0 (interior_amg.hpp): rows the row blocks of A_0 do not cross
+      : AmgOp(c, n0) {   // breaks0 (interior_amg.hpp): rows the row blocks of A_0 do not cross; val == NULL (amg_bank.hpp): the
+                         // plan, the patterns and the work only — a set-up engine that is never applied
     std::string err;
     if (n0 < 1 || n0 >= INT32_MAX) raise(MI_ERR_BAD_ARG, "mi_amg_plan_create: n = %lld rows", (long long)n0);
     if (amgp::make_plan(n0, rowptr, colidx, nlevels, n_l, agg, base, c->rank, c->n_ranks, plan, err) != amgp::OK) raise(MI_ERR_BAD_ARG, "%s", err.c_str());
@@ -216,6 +217,7 @@ struct AmgPlanOp : AmgOp {
     extra = plan.bytes() + second;
     kept += extra;
     omega_h.assign((size_t)std::max(0, nlev - 1), 0.0);
+    if (!val) return;
     alloc_vectors();
     DevBuf<double> v;
     v.upload(val, (size_t)nnz0, s);

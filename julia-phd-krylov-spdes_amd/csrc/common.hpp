@@ -309,6 +309,7 @@ struct mi_ctx_s {
   bool use_peer() const { return peer != nullptr && peer_on; }
   bool no_graph = false;  // set when a captured collective could not be instantiated: eager launches from then on
   long long n_replays = 0;  // hipGraphLaunch calls of the solvers on this context (mi_ctx_query)
+  long long n_captures = 0; // graphs the solvers have captured on this context (mi_ctx_query)
   // scratch for BLAS-1 entry points and reductions
   mi::DevBuf<double> scratch_a, scratch_b, partials, scalar;
   mi::PinnedBuf pin_b, pin_x;  // host-pointer solves: b, x0 in / x out without stream copies

@@ -75,6 +75,7 @@ struct LorascOp : SplitOp {
   }
   ~LorascOp() override { --plan->bound; --gg_h->bound; }
   bool uses(const Operator *o) const override { return o == this || gg->uses(o); }
+  bool usable(std::string &why) const override { return gg->usable(why); }
 
   static void check_nev(int64_t k, const double *E_, const char *me) {
     if (k < 0 || k > LO_MAX_NEV) raise(MI_ERR_BAD_ARG, "%s: nev = %lld, the correction holds at most %d vectors", me, (long long)k, LO_MAX_NEV);

@@ -14,6 +14,7 @@
 #include "block_jacobi.hpp"
 #include "amg.hpp"
 #include "amg_setup.hpp"
+#include "amg_bank.hpp"
 #include "interior_amg.hpp"
 #include "kl.hpp"
 #include "kl_field.hpp"
@@ -112,6 +113,14 @@ void loop_allreduce(LoopGroup &g, int rank, const double *send, double *recv, si
   MI_HIP(hipStreamSynchronize(s));
 }
 
+// A handle that cannot be applied as it stands (an AMG bank; a view whose selection was never set): refused before any launch
+static int refuse_unusable(const char *me, std::initializer_list<mi_op_t> ops) {
+  std::string why;
+  for (mi_op_t o : ops)
+    if (o && o->impl && !o->impl->usable(why)) return fail(MI_ERR_BAD_ARG, "%s: %s", me, why.c_str());
+  return MI_OK;
+}
+
 static int run_solver(mi_op_t A, mi_op_t M, const double *b, double *x, const double *W, int64_t nvec, int64_t maxit,
                       double eps, double *res_norm, int64_t res_cap, int64_t *it, bool want_M, bool want_W) {
   if (!A || !A->impl || !b || !x || !it || res_cap < 0 || (res_cap > 0 && !res_norm) || maxit < 0)
@@ -120,6 +129,7 @@ static int run_solver(mi_op_t A, mi_op_t M, const double *b, double *x, const do
   if (want_W && (nvec < 0 || (nvec > 0 && !W) || nvec > 1024)) return fail(MI_ERR_BAD_ARG, "solver: bad W / nvec");
   Operator *a = A->impl.get(), *m = want_M ? M->impl.get() : nullptr;
   if (m && (m->n != a->n || m->ctx != a->ctx)) return fail(MI_ERR_BAD_ARG, "solver: A and M differ in size or context");
+  if (int rc = refuse_unusable("solver", {A, want_M ? M : nullptr})) return rc;
   mi_ctx_s *c = a->ctx;
   return guarded([&]() -> int {
     c->use();
@@ -152,6 +162,7 @@ static int run_eig_solver(EigKind kind, mi_op_t A, mi_op_t M, const double *b, d
                 (long long)spdim, (long long)(2 * nvec + 1));
   Operator *a = A->impl.get(), *m = want_M ? M->impl.get() : nullptr;
   if (m && (m->n != a->n || m->ctx != a->ctx)) return fail(MI_ERR_BAD_ARG, "solver: A and M differ in size or context");
+  if (int rc = refuse_unusable("solver", {A, want_M ? M : nullptr})) return rc;
   mi_ctx_s *c = a->ctx;
   return guarded([&]() -> int {
     c->use();
@@ -178,6 +189,7 @@ static int run_init_solver(mi_op_t A, mi_op_t M, const double *b, double *x, con
   if (nvec < 1 || !W || nvec > 1024) return fail(MI_ERR_BAD_ARG, "solver: bad W / nvec");
   Operator *a = A->impl.get(), *m = want_M ? M->impl.get() : nullptr;
   if (m && (m->n != a->n || m->ctx != a->ctx)) return fail(MI_ERR_BAD_ARG, "solver: A and M differ in size or context");
+  if (int rc = refuse_unusable("solver", {A, want_M ? M : nullptr})) return rc;
   mi_ctx_s *c = a->ctx;
   return guarded([&]() -> int {
     c->use();
@@ -445,6 +457,7 @@ int mi_ctx_query(mi_ctx_t ctx, int what, int64_t *out) {
       case MI_QUERY_NO_GRAPH: *out = ctx->no_graph ? 1 : 0; break;
       case MI_QUERY_PEER_EXCHANGE: *out = ctx->use_peer() ? (ctx->peer_inwait ? 3 : ctx->peer->fine_grained ? 2 : 1) : 0; break;
       case MI_QUERY_GRAPH_REPLAYS: *out = ctx->n_replays; break;
+      case MI_QUERY_GRAPH_CAPTURES: *out = ctx->n_captures; break;
       case MI_QUERY_SPECTRAL_PINV: *out = spectral_pinv_calls().load(); break;
       case MI_QUERY_FOLDED_PCG: *out = folded_pcg_launches().load(); break;
       case MI_QUERY_EXPERIMENTAL: *out = 0; break;   // the EXPERIMENTAL build was removed
@@ -678,6 +691,9 @@ int mi_lorasc_create(mi_ctx_t ctx, int64_t ndom, int64_t n, int64_t n_gamma, con
                      const int64_t *pos_gamma, const int64_t *const *ig_colptr, const int64_t *const *ig_rowval,
                      const double *const *ig_nzval, mi_setup_t interior, mi_op_t a_gg_solver, int64_t nev, const double *E,
                      const double *coef, int index_base, mi_op_t *op) {
+  if (op) *op = nullptr;
+  if (dynamic_cast<AmgBankOp *>(a_gg_solver && a_gg_solver->impl ? a_gg_solver->impl.get() : nullptr))
+    return fail(MI_ERR_BAD_ARG, "mi_lorasc_create: a_gg_solver is an AMG bank, which is not applicable itself; pass a view of it (mi_amg_bank_view)");
   MI_NEW_OP(ctx, op, new LorascOp(ctx, ndom, n, n_gamma, n_i, pos_I, pos_gamma, ig_colptr, ig_rowval, ig_nzval, interior, a_gg_solver,
                                   nev, E, coef, index_base));
 }
@@ -799,6 +815,7 @@ int mi_schur_global_device_create(mi_ctx_t ctx, int64_t ndom, int64_t n_gamma, c
                                        gg_nzval, nullptr, nullptr, index_base, ii_colptr, ii_rowval, ii_nzval, reltol));
 }
 
+static AmgBankOp *as_amg_bank(mi_op_t op);
 int mi_op_size(mi_op_t op, int64_t *n) {
   if (!op || !op->impl || !n) return fail(MI_ERR_BAD_ARG, "NULL argument");
   *n = op->impl->n;
@@ -807,6 +824,7 @@ int mi_op_size(mi_op_t op, int64_t *n) {
 
 int mi_op_apply(mi_op_t op, const double *x, double *y) {
   if (!op || !op->impl || !x || !y || x == y) return fail(MI_ERR_BAD_ARG, "mi_op_apply: NULL or aliased argument");
+  if (int rc = refuse_unusable("mi_op_apply", {op})) return rc;
   return guarded([&]() -> int {
     mi_ctx_s *c = op->impl->ctx;
     c->use();
@@ -859,6 +877,7 @@ int mi_op_bytes(mi_op_t op, int64_t *bytes_apply, int64_t *bytes_dominant_kernel
 // context's stream, after a warm-up replay; the average duration per launch is returned.
 static int dominant_impl(mi_op_t op, const double *x, int reps, double *us_per_launch) {
   if (!op || !op->impl || !x || reps < 0) return fail(MI_ERR_BAD_ARG, "bad argument");
+  if (int rc = refuse_unusable(us_per_launch ? "mi_op_time_dominant" : "mi_op_apply_dominant", {op})) return rc;
   return guarded([&]() -> int {
     mi_ctx_s *c = op->impl->ctx;
     c->use();
@@ -903,6 +922,8 @@ int mi_op_destroy(mi_op_t op) {
   if (op->bound > 0) return fail(MI_ERR_BAD_ARG, "mi_op_destroy: %d live LORASC operator(s) use this operator; destroy them first", op->bound);
   if (op->bound_combine > 0)
     return fail(MI_ERR_BAD_ARG, "mi_op_destroy: this operator holds %d place(s) among the children of live combined operator(s) (mi_op_combine); destroy them first", op->bound_combine);
+  if (AmgBankOp *bk = as_amg_bank(op))
+    if (bk->views > 0) return fail(MI_ERR_BAD_ARG, "mi_op_destroy: %d live view(s) (mi_amg_bank_view) borrow this AMG bank; destroy them first", bk->views);
   return guarded([&]() -> int {
     if (op->impl) {
       mi_ctx_s *c = op->impl->ctx;
@@ -1034,6 +1055,7 @@ int mi_eigsolve(mi_op_t A, mi_op_t B, mi_op_t Binv, int64_t nev, int which, int6
   mi_ctx_s *c = a->ctx;
   if (c->has_comm())
     return fail(MI_ERR_BAD_ARG, "mi_eigsolve: the context is one rank of several; sharded eigensolves are not provided");
+  if (int rc = refuse_unusable("mi_eigsolve", {A, B, Binv})) return rc;
   return guarded([&]() -> int {
     c->use();
     In vi(c, v0, v0 ? (size_t)n : 0, c->scratch_a);
@@ -1465,6 +1487,7 @@ int mi_op_combine(mi_ctx_t ctx, int64_t k, const mi_op_t *ops, const double *coe
   for (int64_t i = 0; i < k; ++i) {
     if (!ops[i] || !ops[i]->impl) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is NULL", me, (long long)i);
     Operator *o = ops[i]->impl.get();
+    if (dynamic_cast<AmgBankOp *>(o)) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is an AMG bank, which is not applicable itself; combine views of it (mi_amg_bank_view)", me, (long long)i);
     if (o->ctx != ctx) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] belongs to another context", me, (long long)i);
     if (o->n != ops[0]->impl->n) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is of size %lld, ops[0] of size %lld", me, (long long)i, (long long)o->n, (long long)ops[0]->impl->n);
     kids.push_back(ops[i]);
@@ -1480,6 +1503,110 @@ int mi_op_combine_set_coefficients(mi_op_t op, const double *coef) {
   return guarded([&]() -> int {
     c->ctx->use();
     c->set_coefficients(coef);
+    return MI_OK;
+  });
+}
+
+// ---------------------------------------------------------------- P hierarchies on one plan (amg_bank.hpp)
+static AmgBankOp *as_amg_bank(mi_op_t op) { return op && op->impl ? dynamic_cast<AmgBankOp *>(op->impl.get()) : nullptr; }
+static AmgBankView *as_amg_bank_view(mi_op_t op) { return op && op->impl ? dynamic_cast<AmgBankView *>(op->impl.get()) : nullptr; }
+static const char *bank_kind(mi_op_t op) {
+  return !op || !op->impl ? "a NULL handle" : as_amg_bank(op) ? "an AMG bank" : as_amg_bank_view(op) ? "a view of an AMG bank" : "another kind of operator";
+}
+static int bank_member_check(const char *me, AmgBankOp *m, int64_t member, bool need_set) {
+  if (member < 0 || member >= m->capacity)
+    return fail(MI_ERR_BAD_ARG, "%s: member = %lld outside 0 .. %lld (the capacity is %lld)", me, (long long)member, (long long)m->capacity - 1, (long long)m->capacity);
+  if (need_set && !m->is_set[(size_t)member])
+    return fail(MI_ERR_BAD_ARG, "%s: member %lld was never set (mi_amg_bank_set_values)", me, (long long)member);
+  return MI_OK;
+}
+int mi_amg_bank_create(mi_ctx_t ctx, int64_t n, const int64_t *rowptr, const int64_t *colidx, int64_t nlevels, const int64_t *n_l,
+                       const int64_t *const *agg, int64_t capacity, int index_base, mi_op_t *bank) {
+  if (bank) *bank = nullptr;
+  if (capacity < 1) return fail(MI_ERR_BAD_ARG, "mi_amg_bank_create: capacity = %lld (at least 1 member)", (long long)capacity);
+  MI_NEW_OP(ctx, bank, new AmgBankOp(ctx, n, rowptr, colidx, nlevels, n_l, agg, capacity, index_base));
+}
+int mi_amg_bank_set_values(mi_op_t bank, int64_t member, const double *val) {
+  const char *me = "mi_amg_bank_set_values";
+  AmgBankOp *m = as_amg_bank(bank);
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s: not an AMG bank (mi_amg_bank_create) but %s", me, bank_kind(bank));
+  if (int rc = bank_member_check(me, m, member, false)) return rc;
+  if (!val) return fail(MI_ERR_BAD_ARG, "%s: val is NULL", me);
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    In vi(c, val, (size_t)m->eng.nnz0, m->eng.stage);
+    m->set_values(member, vi.dev);   // synchronous
+    return MI_OK;
+  });
+}
+int mi_amg_bank_view(mi_op_t bank, int64_t max_terms, mi_op_t *view) {
+  const char *me = "mi_amg_bank_view";
+  if (view) *view = nullptr;
+  AmgBankOp *m = as_amg_bank(bank);
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s: not an AMG bank (mi_amg_bank_create) but %s", me, bank_kind(bank));
+  if (max_terms < 1 || max_terms > AMGB_MAX_TERMS)
+    return fail(MI_ERR_BAD_ARG, "%s: max_terms = %lld (1 <= max_terms <= %d)", me, (long long)max_terms, AMGB_MAX_TERMS);
+  mi_ctx_s *ctx = m->ctx;
+  MI_NEW_OP(ctx, view, new AmgBankView(ctx, m, (int)max_terms));
+}
+int mi_amg_bank_select(mi_op_t view, int64_t k, const int64_t *members, const double *coef) {
+  const char *me = "mi_amg_bank_select";
+  AmgBankView *v = as_amg_bank_view(view);
+  if (!v) return fail(MI_ERR_BAD_ARG, "%s: not a view of an AMG bank (mi_amg_bank_view) but %s", me, bank_kind(view));
+  if (k < 1 || k > v->kmax) return fail(MI_ERR_BAD_ARG, "%s: k = %lld members (1 <= k <= max_terms = %d)", me, (long long)k, v->kmax);
+  if (!members) return fail(MI_ERR_BAD_ARG, "%s: members is NULL", me);
+  if (int rc = combine_coef_check(me, k, coef)) return rc;
+  for (int64_t i = 0; i < k; ++i)
+    if (int rc = bank_member_check(me, v->bank, members[i], true)) return rc;
+  return guarded([&]() -> int {
+    v->ctx->use();
+    v->write_selection(k, members, coef);
+    return MI_OK;
+  });
+}
+int mi_amg_bank_stats(mi_op_t bank, int64_t *capacity, int64_t *members_set, int64_t *bytes_shared, int64_t *bytes_per_member, int64_t *views) {
+  AmgBankOp *m = as_amg_bank(bank);
+  if (!m) return fail(MI_ERR_BAD_ARG, "mi_amg_bank_stats: not an AMG bank (mi_amg_bank_create) but %s", bank_kind(bank));
+  if (capacity) *capacity = m->capacity;
+  if (members_set) *members_set = m->n_set;
+  if (bytes_shared) *bytes_shared = m->eng.kept;
+  if (bytes_per_member) *bytes_per_member = 8 * m->stride;
+  if (views) *views = m->views;
+  return MI_OK;
+}
+int mi_amg_bank_level_sizes(mi_op_t bank, int64_t level, int64_t *n_rows, int64_t *n_cols, int64_t *a_nnz, int64_t *p_nnz) {
+  AmgBankOp *m = as_amg_bank(bank);
+  if (!m) return fail(MI_ERR_BAD_ARG, "mi_amg_bank_level_sizes: not an AMG bank (mi_amg_bank_create) but %s", bank_kind(bank));
+  if (level < 0 || level >= m->nlev) return fail(MI_ERR_BAD_ARG, "mi_amg_bank_level_sizes: level = %lld of %d levels", (long long)level, m->nlev);
+  m->eng.level_sizes((int)level, n_rows, n_cols, a_nnz, p_nnz);
+  return MI_OK;
+}
+int mi_amg_bank_level_get(mi_op_t bank, int64_t member, int64_t level, int64_t *a_rowptr, int64_t *a_colidx, double *a_val, int64_t *p_rowptr,
+                          int64_t *p_colidx, double *p_val, double *omega, double *omega_over_d) {
+  const char *me = "mi_amg_bank_level_get";
+  AmgBankOp *m = as_amg_bank(bank);
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s: not an AMG bank (mi_amg_bank_create) but %s", me, bank_kind(bank));
+  if (int rc = bank_member_check(me, m, member, true)) return rc;
+  if (level < 0 || level >= m->nlev) return fail(MI_ERR_BAD_ARG, "%s: level = %lld of %d levels", me, (long long)level, m->nlev);
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    m->level_get(member, (int)level, a_rowptr, a_colidx, a_val, p_rowptr, p_colidx, p_val, omega, omega_over_d);
+    return MI_OK;
+  });
+}
+int mi_amg_bank_coarse_inverse(mi_op_t bank, int64_t member, double *coarse_inv) {
+  const char *me = "mi_amg_bank_coarse_inverse";
+  AmgBankOp *m = as_amg_bank(bank);
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s: not an AMG bank (mi_amg_bank_create) but %s", me, bank_kind(bank));
+  if (int rc = bank_member_check(me, m, member, true)) return rc;
+  if (!coarse_inv) return fail(MI_ERR_BAD_ARG, "%s: coarse_inv is NULL", me);
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    MI_HIP(hipMemcpyAsync(coarse_inv, m->slot(member) + m->off_z, sizeof(double) * (size_t)m->nc * m->nc, hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
     return MI_OK;
   });
 }

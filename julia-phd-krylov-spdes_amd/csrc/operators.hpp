@@ -72,6 +72,9 @@ struct Operator {
   // true: the launches of apply() include those of `o` — `o` is this operator or one it applies through a borrowed handle
   // (CombineOp's children, LorascOp's A_ΓΓ solver). A graph captured with this operator holds o's launch arguments.
   virtual bool uses(const Operator *o) const { return o == this; }
+  // false, with the reason in `why`: apply() would refuse — a handle that is no operator by itself, or a selection that holds
+  // nothing yet (amg_bank.hpp). Asked by mi_op_apply and the solvers before their first launch.
+  virtual bool usable(std::string &why) const { return true; }
   // true: y is written exactly once, by the last kernel of apply(), and never read — it may then be pinned host memory
   virtual bool writes_y_once() const { return true; }
   virtual void bytes(int64_t *apply_b, int64_t *dominant_b) const = 0;

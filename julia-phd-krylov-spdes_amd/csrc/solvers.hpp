@@ -523,6 +523,7 @@ struct Krylov {
       throw;
     }
     ws.graphs[key] = ex;
+    ++ctx->n_captures;
     return ex;
   }
 

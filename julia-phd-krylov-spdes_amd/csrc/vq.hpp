@@ -535,6 +535,11 @@ struct CombineOp : Operator {
       if (k->uses(o)) return true;
     return false;
   }
+  bool usable(std::string &why) const override {
+    for (const Operator *k : kids)
+      if (!k->usable(why)) return false;
+    return true;
+  }
   // a blocking copy on the context's stream: it is ordered after the solves already enqueued, and a captured graph reads the
   // same device array afterwards
   void set_coefficients(const double *cf) {

@@ -37,7 +37,8 @@ export MiContext, MiOperator, MiPrecond,
        keep_levels!, interior_solve, use_level_solver!, peer_handle!, peer_connect!, set_exchange!,
        SparseDirectPreconditioner, spd_direct_stats, bj_set_values!, MiLorasc, set_correction!, MiNNInduced, set_coupling!,
        mi_eigsolve, mi_geneigsolve, MiAMGPreconditioner, amg_stats,
-       MiKlField, MiMcmcSampler, coefficient!, klfield_stats, MiFullAssembly, jacobi_refresh!
+       MiKlField, MiMcmcSampler, coefficient!, klfield_stats, MiFullAssembly, jacobi_refresh!,
+       MiAMGBank, MiAMGBankView, select!, combine!, amg_bank_stats
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -893,6 +894,86 @@ eigpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditi
 eigdefpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditioner, W::Matrix{Float64}, spdim::Int; maxit=0) =
   eigsolve(:eigdefpcg, A, M.op, b, x, W, size(W, 2), spdim, maxit)
 initpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGPreconditioner, W::Matrix{Float64}; maxit=0) = initsolve(A, M.op, b, x, W, maxit)
+
+# ---------------------------------------------------------------- P hierarchies on one plan (Example12_…_Functions.jl:85-113)
+"""`MiAMGBank(ctx, A, agg, capacity)`: `capacity` smoothed-aggregation hierarchies on the pattern of `A` and the frozen
+aggregates `agg` (as for `MiAMGPreconditioner(ctx, A, agg)`), sharing one plan, one set of index arrays and one set-up engine
+on the device (`mi_amg_bank_create`) — the constant preconditioners of `get_centroidal_preconds`, one member per centroid, a
+member being numbers only. `set_values!(bank, p, A_p)` makes member `p` (1-based, as everything on the Julia side). The bank
+is not an operator: `MiAMGBankView(bank, max_terms)` is, `select!(Π, p)` is the `Πs[find_precond(ξ, hXt)]` of Example12:106
+and `combine!(Π, members, coefficients)` the `InterpolatingPreconditioner` of Example14 — both rewrite small device arrays,
+so the solve graphs captured with the view serve every selection. A view roots its bank; the bank's slab is freed at the
+first collection after its last view is gone."""
+mutable struct MiAMGBank
+  op::MiOperator
+  capacity::Int
+  n_levels::Int
+end
+function MiAMGBank(ctx::MiContext, A::SparseMatrixCSC{Float64,Int}, agg::Vector{Vector{Int}}, capacity::Int)
+  capacity >= 1 || throw(ArgumentError("capacity = $capacity: a bank holds at least 1 member"))
+  L = length(agg) + 1
+  n_l = Int64[A.n; [maximum(a) for a in agg]]
+  cp, rv = Vector{Int64}(A.colptr), Vector{Int64}(A.rowval)
+  ag = Vector{Int64}[Vector{Int64}(a) for a in agg]
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  GC.@preserve ag begin
+    check(ccall((:mi_amg_bank_create, lib), Cint,
+                (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Ptr{Int64}}, Int64, Cint, Ref{Ptr{Cvoid}}),
+                ctx.h, A.n, cp, rv, L, n_l, ptrs(ag), capacity, 1, r))
+  end
+  n = Ref{Int64}(0)
+  check(ccall((:mi_op_size, lib), Cint, (Ptr{Cvoid}, Ref{Int64}), r[], n))
+  MiAMGBank(finalizer(bank_release, MiOperator(r[], n[], n[], ctx, nothing)), capacity, L)
+end
+# The library refuses to destroy a bank under a live view and leaves the handle valid. A view that becomes garbage in the
+# same collection may be finalized after its bank: the bank then asks again at the next collection instead of leaking its slab.
+function bank_release(o::MiOperator)
+  rc = ccall((:mi_op_destroy, lib), Cint, (Ptr{Cvoid},), o.h)
+  rc == 0 || finalizer(bank_release, o)
+  return
+end
+member0(bank::MiAMGBank, p::Integer) = 1 <= p <= bank.capacity ? Int64(p - 1) : throw(BoundsError(1:bank.capacity, p))
+"""`set_values!(bank, p, A)`: member `p` from the values of `A` (the pattern of creation; `mi_amg_bank_set_values`). A matrix
+that is not positive definite throws and leaves the member as it was."""
+set_values!(bank::MiAMGBank, p::Integer, A::SparseMatrixCSC{Float64,Int}) =
+  check(ccall((:mi_amg_bank_set_values, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), bank.op.h, member0(bank, p), A.nzval))
+function amg_bank_stats(bank::MiAMGBank)
+  a, b, c, d, e = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+  check(ccall((:mi_amg_bank_stats, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), bank.op.h, a, b, c, d, e))
+  (capacity=Int(a[]), members_set=Int(b[]), bytes_shared=Int(c[]), bytes_per_member=Int(d[]), views=Int(e[]))
+end
+
+mutable struct MiAMGBankView
+  op::MiOperator
+  bank::MiAMGBank
+  max_terms::Int
+end
+function MiAMGBankView(bank::MiAMGBank, max_terms::Int=1)
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:mi_amg_bank_view, lib), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), bank.op.h, max_terms, r))
+  MiAMGBankView(wrap(bank.op.ctx, r, bank), bank, max_terms)
+end
+"""`combine!(Π, members, coefficients)`: Π \\ r = Σ_i coefficients[i] (Π_{members[i]} \\ r), 1-based members that were set before
+(`mi_amg_bank_select`)."""
+function combine!(Π::MiAMGBankView, members::Vector{Int}, coefficients::Vector{Float64})
+  length(members) == length(coefficients) || throw(ArgumentError("$(length(coefficients)) coefficients for $(length(members)) members"))
+  m0 = Int64[member0(Π.bank, p) for p in members]
+  check(ccall((:mi_amg_bank_select, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}), Π.op.h, length(m0), m0, coefficients))
+end
+"""`select!(Π, p)`: member `p` alone, coefficient 1."""
+select!(Π::MiAMGBankView, p::Integer) = combine!(Π, Int[p], [1.0])
+
+\(Π::MiAMGBankView, r::Vector{Float64}) = Π.op * r
+ldiv!(z::Vector{Float64}, Π::MiAMGBankView, r::Vector{Float64}) = mul!(z, Π.op, r)
+ldiv!(Π::MiAMGBankView, r::Vector{Float64}) = (r .= Π.op * copy(r))
+pcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGBankView; maxit=0) = solve(:pcg, A, M.op, b, x, nothing, maxit)   # Example12:106
+defpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, W::Matrix{Float64}, M::MiAMGBankView; maxit=0) =
+  solve(:defpcg, A, M.op, b, x, W, maxit)
+eigpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGBankView, nvec::Int, spdim::Int; maxit=0) =
+  eigsolve(:eigpcg, A, M.op, b, x, nothing, nvec, spdim, maxit)
+eigdefpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGBankView, W::Matrix{Float64}, spdim::Int; maxit=0) =
+  eigsolve(:eigdefpcg, A, M.op, b, x, W, size(W, 2), spdim, maxit)
+initpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGBankView, W::Matrix{Float64}; maxit=0) = initsolve(A, M.op, b, x, W, maxit)
 
 # ---------------------------------------------------------------- realization sampler (Example06:160, Example09 `draw!(sampler)`)
 """`MiKlField`: the step from a latent vector ξ to the field g = Σ_α sqrt(Λ_α) ξ_α Ψ[:, α] on the device (`mi_kl_field_t`).
