@@ -20,8 +20,12 @@ one captured solve graph serves every selection. The iteration counts are those 
 `--device-assembly`: every system, the centroids' and the realizations', is assembled on the device
 (`api.FullAssemblyPlan`, bit-identical to the host assembly), and ONE `A_op` is refreshed in place per realization.
 
+`--bank --batch k`: the realizations are solved k at a time in ONE Krylov loop. k values of ξ are drawn and their
+coefficients come from one `KLField` pass; k calls of `FullAssemblyPlan.update_batch` fill k slots of an `api.CsrBatch`, one
+`vq_assign` gives the k members, and one `api.pcg_batch` solves the k systems. `iters_quantized` is that of the unbatched flow.
+
     python examples/example12_quantization.py [--N 60] [--ns 2000] [--P 8] [--nreals 5] [--distance L2-full] [--interpolate 4]
-                                              [--device-assembly] [--bank]
+                                              [--device-assembly] [--bank] [--batch 4]
 """
 import argparse
 import os
@@ -46,7 +50,10 @@ def main():
     ap.add_argument("--seed", type=int, default=987654321)
     ap.add_argument("--device-assembly", action="store_true", help="assemble on the device and refresh one A_op in place")
     ap.add_argument("--bank", action="store_true", help="hold the centroidal hierarchies in one AMGBank and select through a view")
+    ap.add_argument("--batch", type=int, default=0, help="k > 0 (with --bank): solve the realizations k at a time with pcg_batch")
     args = ap.parse_args()
+    if args.batch and (not args.bank or args.interpolate > 0 or not 1 <= args.batch <= 16):
+        ap.error("--batch k: 1 <= k <= 16, with --bank and without --interpolate (one member per system)")
     if args.bank and min(args.interpolate, args.P) > 16:
         ap.error(f"--bank: a view combines at most 16 members, --interpolate {args.interpolate} with --P {args.P} asks for {min(args.interpolate, args.P)}")
     pkg = graft.load_package()
@@ -68,7 +75,7 @@ def main():
 
     A_0, _ = system(np.ones(mesh.points.shape[1]))
     plan = A_t = None
-    if args.device_assembly:
+    if args.device_assembly or args.batch:
         plan = api.FullAssemblyPlan(ctx, fem.make_full_assembly_plan(mesh.cells, mesh.points, dinds, mesh.point_marker, f, uexact))
         A_t = api.SparseMatrixCSC(ctx, A_0)
     t = time.perf_counter()
@@ -88,6 +95,10 @@ def main():
     scaled_centroids = fem.scale_data(centroids, kl.Λ, args.distance)
     rows = centroids.shape[0]
     iters_0, iters_q = [], []
+    if args.batch:
+        batched_flow(args, api, fem, ctx, rng, kl, field, plan, A_0, bank, scaled_centroids)
+        bank.close()
+        return
     for ireal in range(1, args.nreals + 1):
         ξ = rng.standard_normal(kl.Λ.size)
         if plan:
@@ -131,6 +142,34 @@ def main():
     print(f"iters_quantized = {iters_q}\niters_xi_0 = {iters_0}")
     if bank:
         bank.close()
+
+
+def batched_flow(args, api, fem, ctx, rng, kl, field, plan, A_0, bank, scaled_centroids):
+    """k realizations per Krylov loop: the draws, the members and the solves of the loop above, k at a time"""
+    kmax = args.batch
+    batch = api.CsrBatch(ctx, A_0, kmax)
+    view = bank.view(kmax)
+    padded = np.zeros((kl.Λ.size, scaled_centroids.shape[1]), order="F")     # as find_precond pads the centroids
+    padded[:scaled_centroids.shape[0]] = scaled_centroids
+    iters_q, done = [], 0
+    while done < args.nreals:
+        k = min(kmax, args.nreals - done)
+        Ξ = np.column_stack([rng.standard_normal(kl.Λ.size) for _ in range(k)])
+        a = field.coefficient(Ξ)                                             # one pass over the modes for the k coefficients
+        B = np.empty((plan.n, k), order="F")
+        for t in range(k):
+            B[:, t] = plan.update_batch(np.ascontiguousarray(a[:, t]), batch, t)
+        H = np.asfortranarray(np.column_stack([fem.scale_data(Ξ[:, t], kl.Λ, args.distance) for t in range(k)]))
+        members = np.asarray(api.vq_assign(ctx, H, padded, want_dist2=False, want_objv=False)[0], dtype=np.int64)
+        t0 = time.perf_counter()
+        X, its, _ = api.pcg_batch(batch, np.arange(k), B, np.zeros((plan.n, k), order="F"), view, members)
+        dt = time.perf_counter() - t0
+        print(f"realizations {done + 1} .. {done + k}: centroids {members.tolist()}: pcg_batch it = {its.tolist()} in {dt * 1e3:.2f} ms")
+        iters_q += [int(i) for i in its]
+        done += k
+    print(f"iters_quantized = {iters_q}")
+    view.close()
+    batch.close()
 
 
 if __name__ == "__main__":

@@ -302,6 +302,51 @@ int mi_amg_bank_level_get(mi_op_t bank, int64_t member, int64_t level, int64_t *
                           int64_t *p_rowptr, int64_t *p_colidx, double *p_val, double *omega, double *omega_over_d);
 int mi_amg_bank_coarse_inverse(mi_op_t bank, int64_t member, double *coarse_inv);
 
+/* mi_csr_batch_* / mi_pcg_batch — k realizations in ONE Krylov loop (csr_batch.hpp, batch_solvers.hpp): the Monte-Carlo loops
+ * `for ireal in 1:nreals … pcg(A_t, b_t, 0, Π[p(ξ_t)])` of Examples 06, 12, 14, 19, 20, whose systems are independent, share
+ * every launch. Slots and members are 0-based; every handle is an mi_op_t.
+ *   create     : the pattern (HOST arrays, `index_base`-based, as mi_csr_create without values; n >= 1, square) and `capacity`
+ *                >= 1 value slots. rowptr, col, the row blocks and their XCD ranges are held once; the value slab is allocated
+ *                here and never moves. No slot is set yet. The batch is NOT applicable: mi_op_apply, mi_op_combine and the
+ *                single-system solvers refuse it with MI_ERR_BAD_ARG before any launch; mi_op_size gives n.
+ *   set_values : nnz values on the pattern into slot `slot` (host or device pointer per the context's pointer mode; a device
+ *                pointer is copied asynchronously on the context's stream).
+ *   get_values : the read-back of a slot that was set (pointer mode as set_values; synchronous).
+ *   stats      : capacity; slots set so far; bytes_shared (the index arrays and row blocks); and
+ *                  bytes_per_slot = 8 (nnz + nnz mod 2):
+ *                the slot stride is padded to an even count of doubles, so every slot starts on a 16-byte boundary (the
+ *                SpMV loads values in pairs at the even offsets of the row blocks). mi_csr_batch_stride(nnz, &doubles) is
+ *                that stride in doubles, host arithmetic only.
+ *   mi_full_assembly_update_batch: mi_full_assembly_update with the values written straight into slot `slot` — the same
+ *                kernel, the same bits; b as there. The pattern is compared in full the first time a plan meets a batch.
+ *   mi_pcg_batch: for t < k, X[:, t] = pcg(A_t, B[:, t], X[:, t], Π_{members[t]}) with A_t = slot slots[t] of the batch and
+ *                Π_m = member m of the bank under the view `M_view` (M_view == NULL: cg, `members` is not read). B (n x k,
+ *                ldb) and X (n x k, ldx; X0 in, the iterates out) are column-major and follow the context's pointer mode;
+ *                slots, members, it[k] and res_norm (ldres x k, column-major: res_norm[0 .. it[t]) of system t in column t)
+ *                are HOST arrays. A slot or a member may appear several times. maxit, eps: as mi_pcg, for every system.
+ *                One form: the arithmetic of the multi-workgroup loop of mi_pcg on a sparse matrix with a non-diagonal M,
+ *                system t as the grid's second dimension and every partial sum in the single solve's order — x, it and
+ *                res_norm of system t carry the bits of the single solve of that system with the view selecting members[t].
+ *                A system whose stop rule has fired is frozen; the loop ends when none is active. The view's own selection
+ *                (mi_amg_bank_select) is not touched. k, slots and members are read on the device, so the graphs captured
+ *                for (batch, view) serve every later selection; MI_QUERY_GRAPH_REPLAYS / _CAPTURES count them, and
+ *                mi_op_destroy of the batch or the view drops them. Replay policy: as mi_pcg (the first graph holds the set-up
+ *                and the iterations the longest system of the previous batch on this (batch, view) took).
+ *                MI_ERR_RES_CAPACITY after the solve has completed if some it[t] > ldres: it is filled and X is valid.
+ * MI_ERR_BAD_ARG, the message naming the numbers: everything mi_csr_create refuses of a pattern; n < 1; capacity < 1; a slot
+ * outside 0 .. capacity - 1; a solved or read slot, or a member, that was never set; k < 1, k > 16 or k above the view's
+ * max_terms; ldb or ldx below n; a handle of the wrong kind; A and M of different size or context; a pattern that is not the
+ * plan's; a context that is one rank of several. */
+int mi_csr_batch_create(mi_ctx_t ctx, int64_t n, const int64_t *rowptr, const int64_t *colidx, int64_t capacity, int index_base,
+                        mi_op_t *batch);
+int mi_csr_batch_set_values(mi_op_t batch, int64_t slot, const double *val);
+int mi_csr_batch_get_values(mi_op_t batch, int64_t slot, double *val);
+int mi_csr_batch_stats(mi_op_t batch, int64_t *capacity, int64_t *slots_set, int64_t *bytes_shared, int64_t *bytes_per_slot);
+int mi_csr_batch_stride(int64_t nnz, int64_t *doubles);
+int mi_pcg_batch(mi_op_t A_batch, int64_t k, const int64_t *slots, mi_op_t M_view /* NULL: cg */, const int64_t *members,
+                 const double *B, int64_t ldb, double *X, int64_t ldx, int64_t maxit, double eps, double *res_norm, int64_t ldres,
+                 int64_t *it /* [k] */);
+
 /* mi_schur_assembled_create — `apply_local_schurs(Sd, ind_Γd_Γ2l, node_Γ_cnt, x)`, EPDD.jl:761-785:
  * Sx = Σ_d R_d' S_d R_d x with dense local Schur complements.
  *   Sd[d]          n_gamma_d[d]^2 doubles, column-major (Julia `Array(Sd[d])`)
@@ -526,6 +571,7 @@ int mi_full_assembly_plan_create(mi_ctx_t ctx, int64_t nel, int64_t n_node, cons
                                  const int64_t *colidx, const double *ue, const double *be, mi_plan_t *plan);
 int mi_full_assembly_run(mi_plan_t plan, const double *a_nodal, double *values, double *b);
 int mi_full_assembly_update(mi_plan_t plan, const double *a_nodal, mi_op_t A, double *b);
+int mi_full_assembly_update_batch(mi_plan_t plan, const double *a_nodal, mi_op_t batch, int64_t slot, double *b);   /* see mi_csr_batch_* */
 int mi_full_assembly_stats(mi_plan_t plan, int64_t *row_blocks, int64_t *incidences, int64_t *bytes_kept);
 int mi_csr_set_values(mi_op_t op, const double *val);
 int mi_diag_set_from_csr(mi_op_t M, mi_op_t A);

@@ -1201,6 +1201,18 @@ class FullAssemblyPlan:
         self.ctx._record(ka, b)
         return b
 
+    def update_batch(self, a_nodal, batch: "CsrBatch", slot: int):
+        """b; the values of A(a) go into slot `slot` of a `CsrBatch` of that pattern (`mi_full_assembly_update_batch`): the
+        kernel and the bits of `update`."""
+        self.ctx._mode_for(a_nodal)
+        ka, pa = self.ctx._ptr(a_nodal, self.plan.n_node)
+        b = self._b_like(ka)
+        _, pb = self.ctx._ptr(b, writable=True)
+        self.ctx._order((ka,), after=False)
+        check(self.ctx._L.mi_full_assembly_update_batch(self._h, pa, getattr(batch, "_h", None), i64(int(slot)), pb))
+        self.ctx._record(ka, b)
+        return b
+
     def stats(self) -> dict:
         """dict(row_blocks, incidences, bytes_kept) (`mi_full_assembly_stats`)"""
         a, b, c = i64(), i64(), i64()
@@ -2412,3 +2424,143 @@ def get_centroidal_bank(ctx: Context, centroids, field: KLField, assemble: Calla
         ξ[:centroids.shape[0]] = centroids[:, p]
         bank.set_values(p, assemble(field.coefficient(ξ)))
     return bank
+
+
+# ------------------------------------------------------------------ k realizations in one Krylov loop
+CSR_BATCH_MAX = 16   # systems of one `pcg_batch` (= AMG_BANK_MAX_TERMS: one term of a bank view each)
+
+
+def csr_batch_slot_bytes(nnz: int) -> int:
+    """`bytes_per_slot` of `mi_csr_batch_stats` for `nnz` stored entries: 8 (nnz + nnz mod 2) (`mi_csr_batch_stride`; no device)."""
+    d = i64()
+    check(_lib.load().mi_csr_batch_stride(i64(int(nnz)), C.byref(d)))
+    return 8 * int(d.value)
+
+
+class CsrBatch:
+    """`capacity` sparse matrices on the pattern of `A0`, sharing one set of index arrays and row blocks on the device
+    (`mi_csr_batch_create`): the systems A_t of a Monte-Carlo loop over realizations. A slot is numbers only. The batch is
+    not an operator: `pcg_batch` solves k of its slots in one Krylov loop. Slots are 0-based."""
+
+    def __init__(self, ctx: Context, A0, capacity: int, index_base: int = 0):
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError(f"capacity = {capacity}: a batch holds at least 1 slot")
+        if index_base not in (0, 1):
+            raise ValueError(f"index_base = {index_base} (0 or 1)")
+        if not (sp.issparse(A0) or isinstance(A0, np.ndarray)):
+            raise TypeError("CsrBatch takes the matrix whose pattern every slot shares")
+        A = sp.csr_matrix(A0)
+        A.sum_duplicates()
+        A.sort_indices()
+        if A.shape[0] != A.shape[1]:
+            raise ValueError("square matrix expected")
+        ptr, idx = _i64(A.indptr) + index_base, _i64(A.indices) + index_base
+        h = vp()
+        check(ctx._L.mi_csr_batch_create(ctx._h, i64(A.shape[0]), ptr.ctypes.data_as(i64p), idx.ctypes.data_as(i64p), i64(capacity),
+                                         C.c_int(index_base), C.byref(h)))
+        self.ctx, self._h = ctx, h
+        self.n, self.nnz, self.capacity = int(A.shape[0]), int(A.indices.size), capacity
+
+    def _slot(self, s) -> int:
+        q = int(s)
+        if q != s or not 0 <= q < self.capacity:
+            raise IndexError(f"slot {s} outside 0 .. {self.capacity - 1}")
+        return q
+
+    def set_values(self, slot: int, A_or_nzval) -> None:
+        """Slot `slot` from a matrix on the pattern of `A0`: a scipy sparse matrix, or its CSR values as a numpy array or a
+        torch CUDA tensor (`mi_csr_batch_set_values`; a tensor is copied asynchronously on the context's stream)."""
+        slot = self._slot(slot)
+        v = _csr_values(A_or_nzval)
+        count = v.numel() if _is_torch(v) else np.size(v)
+        if count != self.nnz:
+            raise ValueError(f"{count} values for the {self.nnz} stored entries of the batch's pattern")
+        self.ctx._mode_for(v)
+        k, ptr = self.ctx._ptr(v, self.nnz)
+        self.ctx._order((k,), after=False)
+        check(self.ctx._L.mi_csr_batch_set_values(self._h, i64(slot), ptr))
+        self.ctx._record(k)
+
+    def get_values(self, slot: int):
+        """The CSR values of slot `slot` as the device holds them, a numpy array (`mi_csr_batch_get_values`)."""
+        slot = self._slot(slot)
+        out = np.empty(self.nnz)
+        self.ctx._mode_for(out)
+        check(self.ctx._L.mi_csr_batch_get_values(self._h, i64(slot), vp(out.ctypes.data)))
+        return out
+
+    def stats(self) -> dict:
+        """dict(capacity, slots_set, bytes_shared, bytes_per_slot) (`mi_csr_batch_stats`)"""
+        a, b, c, d = i64(), i64(), i64(), i64()
+        check(self.ctx._L.mi_csr_batch_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(capacity=int(a.value), slots_set=int(b.value), bytes_shared=int(c.value), bytes_per_slot=int(d.value))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            check(self.ctx._L.mi_op_destroy(self._h))
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _batch_matrix(ctx: Context, V, n: int, k: int, what: str, copy: bool):
+    """(keepalive, void*, ld) of an n x k column-major block: a torch CUDA tensor with unit row stride (used in place, its
+    column stride is the leading dimension) or a numpy array (a Fortran-ordered view with a column stride >= n is used as it
+    is unless `copy`)."""
+    if _is_torch(V):
+        import torch
+        if V.dtype != torch.float64 or not V.is_cuda or V.dim() != 2 or tuple(V.shape) != (n, k) or V.stride(0) != 1 or (k > 1 and V.stride(1) < n):
+            raise TypeError(f"{what} must be an {n} x {k} column-major float64 CUDA tensor (e.g. torch.empty(k, n).T)")
+        return V, vp(V.data_ptr()), int(V.stride(1)) if k > 1 else n
+    a = np.asarray(V)
+    if a.ndim == 1 and k == 1:
+        a = a.reshape(n, 1)
+    if a.shape != (n, k):
+        raise ValueError(f"{what} must be {n} x {k}, got {a.shape}")
+    direct = (not copy and a.dtype == np.float64 and a.strides[0] == 8 and (k == 1 or (a.strides[1] % 8 == 0 and a.strides[1] >= 8 * n)))
+    if not direct:
+        a = np.array(a, dtype=np.float64, order="F", copy=True)
+    return a, vp(a.ctypes.data), (a.strides[1] // 8 if k > 1 else n)
+
+
+def pcg_batch(A_batch: CsrBatch, slots, B, X0, M_view: Optional["AMGBankView"], members=None, maxit: int = 0, eps: float = EPS,
+              ldres: Optional[int] = None):
+    """k solves in one Krylov loop (`mi_pcg_batch`): for t < k, `pcg(A[slots[t]], B[:, t], X0[:, t], Π[members[t]])` with the
+    matrices of a `CsrBatch` and the members of the bank under `M_view` (`M_view=None`: cg). Returns `(X, its, [res_norm_t])`;
+    x, it and res_norm of system t carry the bits of its separate solve with `M_view.select(members[t])`. numpy in -> a new
+    Fortran-ordered X out; torch CUDA tensors (column-major) -> X0 is mutated in place. `ldres`: the capacity of every residual
+    history (default: as the single solvers); BoundsError carries `.X` and `.its` when a system needed more."""
+    ctx, n = A_batch.ctx, A_batch.n
+    sl = _i64(slots).ravel()
+    k = int(sl.size)
+    if M_view is not None:
+        if members is None:
+            raise ValueError("members is required with a preconditioner view")
+        mem = _i64(members).ravel()
+        if mem.size != k:
+            raise ValueError(f"{mem.size} members for {k} slots")
+        pm = mem.ctypes.data_as(i64p)
+    else:
+        mem, pm = None, None
+    ctx._mode_for(B, X0)
+    kB, pB, ldb = _batch_matrix(ctx, B, n, k, "B", copy=False)
+    kX, pX, ldx = _batch_matrix(ctx, X0, n, k, "X0", copy=not _is_torch(X0))
+    cap = int(ldres) if ldres is not None else int(min(maxit if maxit else n, n)) + 1
+    res = np.empty((max(cap, 1), max(k, 1)), order="F")
+    its = np.zeros(max(k, 1), dtype=np.int64)
+    ctx._order((kB, kX), after=False)
+    rc = ctx._L.mi_pcg_batch(A_batch._h, i64(k), sl.ctypes.data_as(i64p), getattr(M_view, "_h", None), pm, pB, i64(ldb), pX, i64(ldx),
+                             i64(maxit), C.c_double(eps), res.ctypes.data_as(f64p), i64(cap), its.ctypes.data_as(i64p))
+    ctx._order((kB, kX), after=True)
+    its = its[:k]
+    try:
+        check(rc)
+    except BoundsError as e:
+        e.X, e.its = kX, its.copy()
+        raise
+    return kX, its.copy(), [res[:int(its[t]), t].copy() for t in range(k)]

@@ -18,6 +18,9 @@
 // pointers as slab + member * stride + offset, so a captured solve graph serves every later selection; the grid's second
 // dimension is max_terms, terms t >= k return at once. The row sums are amg_block_rows and the coarse GEMV order of
 // k_amg_coarse, unchanged: a member's cycle has the bits of k_amg_*. No atomics, nothing allocated or synchronised in apply.
+//
+// apply_batch is the same cycle for k independent right-hand sides, one member each (mi_pcg_batch, batch_solvers.hpp): term t
+// reads column t of R and writes column t of Z, and stops under its own flag. Its selection is a device array of its own.
 #pragma once
 #include "amg_setup.hpp"
 #include "vq.hpp"
@@ -69,7 +72,68 @@ __global__ __launch_bounds__(NT) void k_amgb_post(MI_AMGB_ARGS, long long off_a,
                  [&](int i, double s) { y[i] = x[i] + wd[i] * (b[i] - s); });
 }
 #undef MI_AMGB_TERM
+// The batched cycle (AmgBankView::apply_batch): term t is system t of a batched solve, Z[:, t] = Π_{member t} \ R[:, t]. The same
+// row sums; `sel` is the view's BATCH selection, the stop flag is per term (done[t * ds], ds in ints), and the level-0
+// right-hand side has a stride of its own. The last launch stores 0.0 + 1.0 * z, the arithmetic of k_amgb_combine for one term
+// with coefficient 1: a system's cycle has the bits of view.select(member) applied to its column.
+#define MI_AMGBB_TERM                                            \
+  const int t = (int)blockIdx.y;                                 \
+  if (t >= sel[0]) return;                                       \
+  if (done && done[(size_t)t * (size_t)ds]) return;              \
+  const double *slot = slab + (size_t)sel[1 + t] * (size_t)stride; \
+  __shared__ __attribute__((aligned(16))) double prod[SPMV_TILE]
+__global__ __launch_bounds__(NT) void k_amgbb_down(MI_AMGB_ARGS, long long off_a, long long off_wd, const double *__restrict__ b0, long long bs,
+                                                   double *__restrict__ x0, double *__restrict__ r0, long long vs, const int *done, long long ds) {
+  MI_AMGBB_TERM;
+  const double *val = slot + off_a, *wd = slot + off_wd, *b = b0 + (size_t)t * bs;
+  double *x = x0 + (size_t)t * vs, *r = r0 + (size_t)t * vs;
+  amg_block_rows(nblocks, blk, rowptr, col, val, prod, [&](int c) { return wd[c] * b[c]; },
+                 [&](int i, double s) { const double bi = b[i]; x[i] = wd[i] * bi; r[i] = bi - s; });
+}
+__global__ __launch_bounds__(NT) void k_amgbb_restrict(MI_AMGB_ARGS, long long off_r, const double *__restrict__ v0, long long vs,
+                                                       double *__restrict__ y0, long long ys, const int *done, long long ds) {
+  MI_AMGBB_TERM;
+  const double *val = slot + off_r, *v = v0 + (size_t)t * vs;
+  double *y = y0 + (size_t)t * ys;
+  amg_block_rows(nblocks, blk, rowptr, col, val, prod, [&](int c) { return v[c]; }, [&](int i, double s) { y[i] = s; });
+}
+__global__ __launch_bounds__(NT) void k_amgbb_prolong(MI_AMGB_ARGS, long long off_p, const double *__restrict__ e0, long long es, double *x0,
+                                                      long long vs, const int *done, long long ds) {
+  MI_AMGBB_TERM;
+  const double *val = slot + off_p, *e = e0 + (size_t)t * es;
+  double *x = x0 + (size_t)t * vs;
+  amg_block_rows(nblocks, blk, rowptr, col, val, prod, [&](int c) { return e[c]; }, [&](int i, double s) { x[i] = x[i] + s; });
+}
+// fin: this is the cycle's last launch (level 0)
+__global__ __launch_bounds__(NT) void k_amgbb_post(MI_AMGB_ARGS, long long off_a, long long off_wd, const double *__restrict__ b0, long long bs,
+                                                   const double *__restrict__ x0, long long vs, double *__restrict__ y0, long long ys, int fin,
+                                                   const int *done, long long ds) {
+  MI_AMGBB_TERM;
+  const double *val = slot + off_a, *wd = slot + off_wd, *b = b0 + (size_t)t * bs, *x = x0 + (size_t)t * vs;
+  double *y = y0 + (size_t)t * ys;
+  amg_block_rows(nblocks, blk, rowptr, col, val, prod, [&](int c) { return x[c]; }, [&](int i, double s) {
+    const double v = x[i] + wd[i] * (b[i] - s);
+    y[i] = fin ? 0.0 + 1.0 * v : v;
+  });
+}
+#undef MI_AMGBB_TERM
 #undef MI_AMGB_ARGS
+// y_t = Z_{m_t} b_t, the order of k_amg_coarse; fin: a coarse-only cycle, this is its last launch
+__global__ __launch_bounds__(NT) void k_amgbb_coarse(int n, const double *__restrict__ slab, long long stride, const int *__restrict__ sel,
+                                                     long long off_z, const double *__restrict__ b0, long long bs, double *__restrict__ y0,
+                                                     long long ys, int fin, const int *done, long long ds) {
+  const int t = (int)blockIdx.y;
+  if (t >= sel[0]) return;
+  if (done && done[(size_t)t * (size_t)ds]) return;
+  const int row = (int)blockIdx.x * (NT / 64) + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= n) return;
+  const double *z = slab + (size_t)sel[1 + t] * (size_t)stride + off_z + (size_t)row * n;
+  const double *b = b0 + (size_t)t * bs;
+  double s = 0.0;
+  for (int j = lane; j < n; j += 64) s += z[j] * b[j];
+  s = wave_sum(s);
+  if (lane == 0) y0[(size_t)t * ys + row] = fin ? 0.0 + 1.0 * s : s;
+}
 // y_t = Z_{m_t} b_t: one wave per row, the order of k_amg_coarse
 __global__ __launch_bounds__(NT) void k_amgb_coarse(int n, const double *__restrict__ slab, long long stride, const int *__restrict__ sel,
                                                     long long off_z, const double *__restrict__ b0, long long bs, double *__restrict__ y0,
@@ -213,9 +277,12 @@ struct AmgBankView : Operator {
   std::vector<Vec> lv;
   DevBuf<double> tmp;              // kmax x n: the terms' results
   std::vector<int64_t> sel_h;      // the selection, on the host
+  DevBuf<int> bsel;                // apply_batch: k, then kmax member indices; written by the batched solve's entry kernel
 
   AmgBankView(mi_ctx_s *c, AmgBankOp *b, int max_terms) : Operator(c, b->n), bank(b), kmax(max_terms) {
     sel.alloc((size_t)kmax + 1); coef.alloc((size_t)kmax);
+    bsel.alloc((size_t)kmax + 1);
+    memset_sync(bsel.p, 0, ((size_t)kmax + 1) * sizeof(int));
     const int L = bank->nlev;
     lv.resize((size_t)L);
     for (int l = 0; l < L; ++l) {
@@ -300,6 +367,47 @@ struct AmgBankView : Operator {
                          l ? (long long)V.vs : (long long)n, done);
     }
     combine(z, done);
+  }
+  // Z[:, t] = Π_{bsel[1 + t]} \ R[:, t] for t < bsel[0] (column strides ldr, ldz): the launches of apply() with the term as the
+  // system, no combination launch, every term under its own stop flag done[t * ds] (done == NULL: none). The caller has
+  // checked that the members are set and has written bsel on this stream; select / combine state is not touched.
+  void apply_batch(const double *R, long long ldr, double *Z, long long ldz, const int *done, long long ds) {
+    hipStream_t s = ctx->stream;
+    const int L = bank->nlev;
+    const unsigned ky = (unsigned)kmax;
+    const int nc = bank->nc;
+    auto coarse_b = [&](const double *b, long long bs, double *y, long long ys, int fin) {
+      hipLaunchKernelGGL(k_amgbb_coarse, dim3((nc + NT / 64 - 1) / (NT / 64), ky), dim3(NT), 0, s, nc, (const double *)bank->slab.p,
+                         (long long)bank->stride, (const int *)bsel.p, (long long)bank->off_z, b, bs, y, ys, fin, done, ds);
+    };
+#define MI_AMGBB_CSR(M) (M).nblocks, (const SpmvBlock *)(M).blk.p, (const int *)(M).rowptr.p, (const int *)(M).col.p, (const double *)bank->slab.p, \
+                        (long long)bank->stride, (const int *)bsel.p
+    if (L == 1) { coarse_b(R, ldr, Z, ldz, 1); MI_HIP(hipGetLastError()); return; }
+    for (int l = 0; l < L - 1; ++l) {
+      AmgOp::Level &E = bank->eng.lv[(size_t)l];
+      Vec &V = lv[(size_t)l], &N = lv[(size_t)l + 1];
+      const double *b = l ? V.b.p : R;
+      const long long bs = l ? V.vs : ldr;
+      hipLaunchKernelGGL(k_amgbb_down, dim3(grid_of(E.A), ky), dim3(NT), 0, s, MI_AMGBB_CSR(E.A), (long long)bank->off_a[(size_t)l],
+                         (long long)bank->off_wd[(size_t)l], b, bs, V.x.p, V.r.p, (long long)V.vs, done, ds);
+      hipLaunchKernelGGL(k_amgbb_restrict, dim3(grid_of(E.R), ky), dim3(NT), 0, s, MI_AMGBB_CSR(E.R), (long long)bank->off_r[(size_t)l],
+                         (const double *)V.r.p, (long long)V.vs, N.b.p, (long long)N.vs, done, ds);
+    }
+    Vec &C = lv[(size_t)L - 1];
+    coarse_b(C.b.p, C.vs, C.y.p, C.vs, 0);
+    for (int l = L - 2; l >= 0; --l) {
+      AmgOp::Level &E = bank->eng.lv[(size_t)l];
+      Vec &V = lv[(size_t)l], &N = lv[(size_t)l + 1];
+      const double *b = l ? V.b.p : R;
+      const long long bs = l ? V.vs : ldr;
+      hipLaunchKernelGGL(k_amgbb_prolong, dim3(grid_of(E.P), ky), dim3(NT), 0, s, MI_AMGBB_CSR(E.P), (long long)bank->off_p[(size_t)l],
+                         (const double *)N.y.p, (long long)N.vs, V.x.p, (long long)V.vs, done, ds);
+      hipLaunchKernelGGL(k_amgbb_post, dim3(grid_of(E.A), ky), dim3(NT), 0, s, MI_AMGBB_CSR(E.A), (long long)bank->off_a[(size_t)l],
+                         (long long)bank->off_wd[(size_t)l], b, bs, (const double *)V.x.p, (long long)V.vs, l ? V.y.p : Z,
+                         l ? (long long)V.vs : ldz, l ? 0 : 1, done, ds);
+    }
+#undef MI_AMGBB_CSR
+    MI_HIP(hipGetLastError());
   }
   // k cycles (AmgOp::bytes each) and the combination; dominant: the fine-level k_amgb_down of the terms selected
   void bytes(int64_t *a, int64_t *d) const override {

@@ -15,6 +15,7 @@
 #include "amg.hpp"
 #include "amg_setup.hpp"
 #include "amg_bank.hpp"
+#include "batch_solvers.hpp"
 #include "interior_amg.hpp"
 #include "kl.hpp"
 #include "kl_field.hpp"
@@ -1488,6 +1489,7 @@ int mi_op_combine(mi_ctx_t ctx, int64_t k, const mi_op_t *ops, const double *coe
     if (!ops[i] || !ops[i]->impl) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is NULL", me, (long long)i);
     Operator *o = ops[i]->impl.get();
     if (dynamic_cast<AmgBankOp *>(o)) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is an AMG bank, which is not applicable itself; combine views of it (mi_amg_bank_view)", me, (long long)i);
+    if (dynamic_cast<CsrBatchOp *>(o)) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is a batch of sparse matrices (mi_csr_batch_create), which is not applicable itself", me, (long long)i);
     if (o->ctx != ctx) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] belongs to another context", me, (long long)i);
     if (o->n != ops[0]->impl->n) return fail(MI_ERR_BAD_ARG, "%s: ops[%lld] is of size %lld, ops[0] of size %lld", me, (long long)i, (long long)o->n, (long long)ops[0]->impl->n);
     kids.push_back(ops[i]);
@@ -1757,6 +1759,150 @@ int mi_full_assembly_update(mi_plan_t plan, const double *a_nodal, mi_op_t A, do
     full_assembly_launch(plan, ai.dev, op->A.val.p, bo.dev);
     bo.finish();
     return MI_OK;
+  });
+}
+// ---------------------------------------------------------------- k matrices on one pattern, k solves in one loop (csr_batch.hpp, batch_solvers.hpp)
+static CsrBatchOp *as_csr_batch(mi_op_t op) { return op && op->impl ? dynamic_cast<CsrBatchOp *>(op->impl.get()) : nullptr; }
+static const char *batch_kind(mi_op_t op) {
+  return !op || !op->impl ? "a NULL handle" : as_csr_batch(op) ? "a batch of sparse matrices" : bank_kind(op);
+}
+static int batch_slot_check(const char *me, CsrBatchOp *m, int64_t slot, bool need_set) {
+  if (slot < 0 || slot >= m->capacity)
+    return fail(MI_ERR_BAD_ARG, "%s: slot = %lld outside 0 .. %lld (the capacity is %lld)", me, (long long)slot, (long long)m->capacity - 1, (long long)m->capacity);
+  if (need_set && !m->is_set[(size_t)slot])
+    return fail(MI_ERR_BAD_ARG, "%s: slot %lld was never set (mi_csr_batch_set_values, mi_full_assembly_update_batch)", me, (long long)slot);
+  return MI_OK;
+}
+int mi_csr_batch_create(mi_ctx_t ctx, int64_t n, const int64_t *rowptr, const int64_t *colidx, int64_t capacity, int index_base, mi_op_t *batch) {
+  const char *me = "mi_csr_batch_create";
+  if (batch) *batch = nullptr;
+  if (!ctx || !batch) return fail(MI_ERR_BAD_ARG, "%s: ctx/batch is NULL", me);
+  if (n < 1 || !rowptr || !colidx) return fail(MI_ERR_BAD_ARG, "%s: n = %lld (at least 1), rowptr or colidx is NULL", me, (long long)n);
+  if (capacity < 1) return fail(MI_ERR_BAD_ARG, "%s: capacity = %lld (at least 1 slot)", me, (long long)capacity);
+  if (index_base != 0 && index_base != 1) return fail(MI_ERR_BAD_ARG, "%s: index_base = %d (0 or 1)", me, index_base);
+  return guarded([&]() -> int {
+    ctx->use();
+    const int64_t nnz = rowptr[n] - index_base;
+    if (nnz < 0 || nnz >= INT32_MAX) raise(MI_ERR_BAD_ARG, "%s: bad rowptr[n]", me);
+    std::vector<double> none((size_t)nnz, 0.0);
+    HostCsr h = host_csr(n, n, rowptr, colidx, none.data(), index_base);
+    std::unique_ptr<mi_op_s> hd(new mi_op_s);
+    hd->impl.reset(new CsrBatchOp(ctx, h, capacity));
+    MI_HIP(hipStreamSynchronize(ctx->stream));
+    *batch = hd.release();
+    return MI_OK;
+  });
+}
+int mi_csr_batch_set_values(mi_op_t batch, int64_t slot, const double *val) {
+  const char *me = "mi_csr_batch_set_values";
+  CsrBatchOp *m = as_csr_batch(batch);
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s: not a batch of sparse matrices (mi_csr_batch_create) but %s", me, batch_kind(batch));
+  if (int rc = batch_slot_check(me, m, slot, false)) return rc;
+  if (m->nnz && !val) return fail(MI_ERR_BAD_ARG, "%s: val is NULL", me);
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    const bool dev = c->ptr_mode == MI_PTR_DEVICE;
+    if (m->nnz) MI_HIP(hipMemcpyAsync(m->slot(slot), val, (size_t)m->nnz * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if (!dev) MI_HIP(hipStreamSynchronize(c->stream));   // the caller's array may change right after
+    m->mark_set(slot);
+    return MI_OK;
+  });
+}
+int mi_csr_batch_get_values(mi_op_t batch, int64_t slot, double *val) {
+  const char *me = "mi_csr_batch_get_values";
+  CsrBatchOp *m = as_csr_batch(batch);
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s: not a batch of sparse matrices (mi_csr_batch_create) but %s", me, batch_kind(batch));
+  if (int rc = batch_slot_check(me, m, slot, true)) return rc;
+  if (m->nnz && !val) return fail(MI_ERR_BAD_ARG, "%s: val is NULL", me);
+  mi_ctx_s *c = m->ctx;
+  return guarded([&]() -> int {
+    c->use();
+    const bool dev = c->ptr_mode == MI_PTR_DEVICE;
+    if (m->nnz) MI_HIP(hipMemcpyAsync(val, m->slot(slot), (size_t)m->nnz * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    MI_HIP(hipStreamSynchronize(c->stream));
+    return MI_OK;
+  });
+}
+int mi_csr_batch_stats(mi_op_t batch, int64_t *capacity, int64_t *slots_set, int64_t *bytes_shared, int64_t *bytes_per_slot) {
+  CsrBatchOp *m = as_csr_batch(batch);
+  if (!m) return fail(MI_ERR_BAD_ARG, "mi_csr_batch_stats: not a batch of sparse matrices (mi_csr_batch_create) but %s", batch_kind(batch));
+  if (capacity) *capacity = m->capacity;
+  if (slots_set) *slots_set = m->n_set;
+  if (bytes_shared) *bytes_shared = m->bytes_shared();
+  if (bytes_per_slot) *bytes_per_slot = 8 * m->stride;
+  return MI_OK;
+}
+int mi_csr_batch_stride(int64_t nnz, int64_t *doubles) {
+  if (nnz < 0 || !doubles) return fail(MI_ERR_BAD_ARG, "mi_csr_batch_stride: nnz = %lld or doubles is NULL", (long long)nnz);
+  *doubles = csr_batch_stride(nnz);
+  return MI_OK;
+}
+int mi_full_assembly_update_batch(mi_plan_t plan, const double *a_nodal, mi_op_t batch, int64_t slot, double *b) {
+  const char *me = "mi_full_assembly_update_batch";
+  if (!plan || !a_nodal) return fail(MI_ERR_BAD_ARG, "%s: NULL argument", me);
+  if (!plan->full) return fail(MI_ERR_BAD_ARG, "%s: this is a plan of mi_assembly_plan_create", me);
+  CsrBatchOp *m = as_csr_batch(batch);
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s: not a batch of sparse matrices (mi_csr_batch_create) but %s", me, batch_kind(batch));
+  if (int rc = batch_slot_check(me, m, slot, false)) return rc;
+  if (plan->n && !b) return fail(MI_ERR_BAD_ARG, "%s: b is NULL", me);
+  mi_ctx_s *c = plan->ctx;
+  if (m->ctx != c) return fail(MI_ERR_BAD_ARG, "%s: the batch belongs to another context", me);
+  if (m->n != plan->n || m->nnz != plan->nnz)
+    return fail(MI_ERR_BAD_ARG, "%s: the batch is %lld x %lld with %lld stored entries, the plan's system %d x %d with %lld", me, (long long)m->n, (long long)m->n,
+                (long long)m->nnz, plan->n, plan->n, (long long)plan->nnz);
+  return guarded([&]() -> int {
+    c->use();
+    if (plan->checked_serial != m->serial) {   // the first time this plan meets this batch: the whole pattern
+      if (m->rowptr_h != plan->rowptr_h || m->col_h != plan->colidx_h) return fail(MI_ERR_BAD_ARG, "%s: the pattern of the batch is not the plan's", me);
+      plan->checked_serial = m->serial;
+    }
+    In ai(c, a_nodal, (size_t)plan->n_node, plan->a_stage);
+    InOut bo(c, b, (size_t)plan->n, plan->b_stage, false);
+    full_assembly_launch(plan, ai.dev, m->slot(slot), bo.dev);
+    bo.finish();
+    m->mark_set(slot);
+    return MI_OK;
+  });
+}
+int mi_pcg_batch(mi_op_t A_batch, int64_t k, const int64_t *slots, mi_op_t M_view, const int64_t *members, const double *B, int64_t ldb, double *X,
+                 int64_t ldx, int64_t maxit, double eps, double *res_norm, int64_t ldres, int64_t *it) {
+  const char *me = "mi_pcg_batch";
+  CsrBatchOp *a = as_csr_batch(A_batch);
+  if (!a) return fail(MI_ERR_BAD_ARG, "%s: A is not a batch of sparse matrices (mi_csr_batch_create) but %s", me, batch_kind(A_batch));
+  AmgBankView *v = nullptr;
+  if (M_view) {
+    v = as_amg_bank_view(M_view);
+    if (!v) return fail(MI_ERR_BAD_ARG, "%s: M is not a view of an AMG bank (mi_amg_bank_view) but %s", me, batch_kind(M_view));
+  }
+  if (k < 1 || k > BATCH_MAX) return fail(MI_ERR_BAD_ARG, "%s: k = %lld systems (1 <= k <= %d)", me, (long long)k, BATCH_MAX);
+  if (v && k > v->kmax) return fail(MI_ERR_BAD_ARG, "%s: k = %lld systems on a view of max_terms = %d", me, (long long)k, v->kmax);
+  if (!slots || !B || !X || !it || (v && !members) || ldres < 0 || (ldres > 0 && !res_norm) || maxit < 0)
+    return fail(MI_ERR_BAD_ARG, "%s: NULL or negative argument", me);
+  mi_ctx_s *c = a->ctx;
+  if (v && (v->n != a->n || v->ctx != c))
+    return fail(MI_ERR_BAD_ARG, "%s: A and M differ in size or context (A is of size %lld, M of size %lld)", me, (long long)a->n, (long long)v->n);
+  if (c->n_ranks > 1) return fail(MI_ERR_BAD_ARG, "%s: this context is rank %d of %d; a batched solve runs on a context of its own", me, c->rank, c->n_ranks);
+  if (ldb < a->n || ldx < a->n) return fail(MI_ERR_BAD_ARG, "%s: ldb = %lld, ldx = %lld below n = %lld", me, (long long)ldb, (long long)ldx, (long long)a->n);
+  for (int64_t t = 0; t < k; ++t) {
+    if (int rc = batch_slot_check(me, a, slots[t], true)) return rc;
+    if (v)
+      if (int rc = bank_member_check(me, v->bank, members[t], true)) return rc;
+  }
+  return guarded([&]() -> int {
+    c->use();
+    const size_t n = (size_t)a->n;
+    BatchKrylov kr(c, a, v);
+    if (c->ptr_mode == MI_PTR_DEVICE) return kr.solve((int)k, slots, members, B, ldb, X, ldx, maxit, eps, res_norm, ldres, it);
+    // Host pointers: the columns go through pinned buffers that the entry kernel reads and the exit kernel writes
+    c->pin_b.ensure(n * (size_t)k); c->pin_x.ensure(n * (size_t)k);
+    for (int64_t t = 0; t < k; ++t) {
+      std::memcpy(c->pin_b.p + (size_t)t * n, B + (size_t)t * (size_t)ldb, n * sizeof(double));
+      std::memcpy(c->pin_x.p + (size_t)t * n, X + (size_t)t * (size_t)ldx, n * sizeof(double));
+    }
+    const int rc = kr.solve((int)k, slots, members, c->pin_b.p, (int64_t)n, c->pin_x.p, (int64_t)n, maxit, eps, res_norm, ldres, it);  // synchronises before returning
+    for (int64_t t = 0; t < k; ++t) std::memcpy(X + (size_t)t * (size_t)ldx, c->pin_x.p + (size_t)t * n, n * sizeof(double));
+    return rc;
   });
 }
 int mi_full_assembly_stats(mi_plan_t plan, int64_t *row_blocks, int64_t *incidences, int64_t *bytes_kept) {

@@ -38,7 +38,8 @@ export MiContext, MiOperator, MiPrecond,
        SparseDirectPreconditioner, spd_direct_stats, bj_set_values!, MiLorasc, set_correction!, MiNNInduced, set_coupling!,
        mi_eigsolve, mi_geneigsolve, MiAMGPreconditioner, amg_stats,
        MiKlField, MiMcmcSampler, coefficient!, klfield_stats, MiFullAssembly, jacobi_refresh!,
-       MiAMGBank, MiAMGBankView, select!, combine!, amg_bank_stats
+       MiAMGBank, MiAMGBankView, select!, combine!, amg_bank_stats,
+       MiCsrBatch, pcg_batch, csr_batch_stats
 
 const lib = get(ENV, "MI355SCHUR_LIB", "libmi355schur")
 const MI_ERR_SINGULAR = Cint(-3)
@@ -974,6 +975,50 @@ eigpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGBankView, 
 eigdefpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGBankView, W::Matrix{Float64}, spdim::Int; maxit=0) =
   eigsolve(:eigdefpcg, A, M.op, b, x, W, size(W, 2), spdim, maxit)
 initpcg(A::MiOperator, b::Vector{Float64}, x::Vector{Float64}, M::MiAMGBankView, W::Matrix{Float64}; maxit=0) = initsolve(A, M.op, b, x, W, maxit)
+
+# ---------------------------------------------------------------- k realizations in one Krylov loop (Examples 06, 12, 14, 19, 20: `for ireal in 1:nreals`)
+"""`MiCsrBatch(ctx, A, capacity)`: `capacity` sparse matrices on the pattern of `A`, sharing one set of index arrays and row
+blocks on the device (`mi_csr_batch_create`) — the systems `A_t` of a Monte-Carlo loop over realizations, a slot being numbers
+only. `set_values!(batch, s, A_s)` fills slot `s` (1-based, as everything on the Julia side). The batch is not an operator:
+`pcg_batch(batch, slots, B, X, Π, members)` solves `length(slots)` of its slots in one Krylov loop on the device, system `t`
+under member `members[t]` of the bank view `Π`, and returns `(X, its, res_norms)`: column `t` of `X`, `its[t]` and
+`res_norms[t]` are those of `pcg(A_t, B[:, t], X[:, t], Π)` after `select!(Π, members[t])`."""
+mutable struct MiCsrBatch
+  op::MiOperator
+  capacity::Int
+  nnz::Int
+end
+function MiCsrBatch(ctx::MiContext, A::SparseMatrixCSC{Float64,Int}, capacity::Int)
+  capacity >= 1 || throw(ArgumentError("capacity = $capacity: a batch holds at least 1 slot"))
+  cp, rv = Vector{Int64}(A.colptr), Vector{Int64}(A.rowval)
+  r = Ref{Ptr{Cvoid}}(C_NULL)
+  check(ccall((:mi_csr_batch_create, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Cint, Ref{Ptr{Cvoid}}),
+              ctx.h, A.n, cp, rv, capacity, 1, r))
+  MiCsrBatch(wrap(ctx, r), capacity, length(A.nzval))
+end
+slot0(batch::MiCsrBatch, s::Integer) = 1 <= s <= batch.capacity ? Int64(s - 1) : throw(BoundsError(1:batch.capacity, s))
+function set_values!(batch::MiCsrBatch, s::Integer, A::SparseMatrixCSC{Float64,Int})
+  length(A.nzval) == batch.nnz || throw(ArgumentError("$(length(A.nzval)) values for the $(batch.nnz) stored entries of the batch's pattern"))
+  check(ccall((:mi_csr_batch_set_values, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), batch.op.h, slot0(batch, s), A.nzval))
+end
+function csr_batch_stats(batch::MiCsrBatch)
+  a, b, c, d = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+  check(ccall((:mi_csr_batch_stats, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), batch.op.h, a, b, c, d))
+  (capacity=Int(a[]), slots_set=Int(b[]), bytes_shared=Int(c[]), bytes_per_slot=Int(d[]))
+end
+function pcg_batch(A::MiCsrBatch, slots::Vector{Int}, B::Matrix{Float64}, X::Matrix{Float64}, M::MiAMGBankView, members::Vector{Int}; maxit=0)
+  n, k = A.op.n, length(slots)
+  length(members) == k || throw(ArgumentError("$(length(members)) members for $k slots"))
+  size(B) == (n, k) && size(X) == (n, k) || throw(DimensionMismatch("B and X must be $n x $k"))
+  s0 = Int64[slot0(A, s) for s in slots]
+  m0 = Int64[member0(M.bank, p) for p in members]
+  res = Matrix{Float64}(undef, n, k)                   # cg.jl:23 `res_norm = Array{T,1}(undef, n)`, one column per system
+  its = zeros(Int64, k)
+  check(ccall((:mi_pcg_batch, lib), Cint,
+              (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Float64, Ptr{Float64}, Int64, Ptr{Int64}),
+              A.op.h, k, s0, M.op.h, m0, B, n, X, n, maxit, 1e-7, res, n, its))
+  return X, Vector{Int}(its), [res[1:its[t], t] for t in 1:k]
+end
 
 # ---------------------------------------------------------------- realization sampler (Example06:160, Example09 `draw!(sampler)`)
 """`MiKlField`: the step from a latent vector ξ to the field g = Σ_α sqrt(Λ_α) ξ_α Ψ[:, α] on the device (`mi_kl_field_t`).
