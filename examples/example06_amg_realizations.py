@@ -16,7 +16,13 @@ set-up it replaces (`--host-setup` measures that too).
 assembly (`update_isotropic_elliptic_assembly!`, EllipticPde.jl:291-377) of the same coefficient, so the iteration counts
 are those of the default path; its time is printed beside the host assembly's.
 
-    python examples/example06_amg_realizations.py [--N 100] [--nreals 3] [--host-setup] [--device-assembly]
+`--device-assembly --batch k` then runs the same k = `--nreals` realizations as ONE batch: the k values of ξ go
+through one `KLField` pass, k `FullAssemblyPlan.update_batch` calls fill k slots of a `CsrBatch`, one
+`AMGBank.set_values_batch` builds the k hierarchies into the members 0 .. k - 1 of a bank on the same aggregates, and one
+`pcg_batch` solves every system under its own member. Its iteration counts are printed beside those of the loop above; they
+must be equal.
+
+    python examples/example06_amg_realizations.py [--N 100] [--nreals 3] [--host-setup] [--device-assembly [--batch 3]]
 """
 import argparse
 import os
@@ -36,7 +42,13 @@ def main():
     ap.add_argument("--seed", type=int, default=481456)
     ap.add_argument("--host-setup", action="store_true", help="also time fem.prepare_amg_precond(A_t) per realization")
     ap.add_argument("--device-assembly", action="store_true", help="assemble A_t, b_t on the device and refresh one A_op in place")
+    ap.add_argument("--batch", type=int, default=0, metavar="k",
+                    help="with --device-assembly: also run k realizations (1 .. 16; --nreals is set to k) as one batch")
     args = ap.parse_args()
+    if args.batch:
+        if not args.device_assembly or not 1 <= args.batch <= 16:
+            ap.error("--batch k needs --device-assembly and 1 <= k <= 16")
+        args.nreals = args.batch
     pkg = graft.load_package()
     fem, api = pkg.fem, pkg.api
     mesh = fem.get_mesh(args.N)
@@ -116,7 +128,35 @@ def device_loop(args, fem, api, ctx, mesh, dinds, f, uexact, kl, ξs, assemble, 
         print(f"realization {ireal}: assembly {1e3 * dt_dev:.3f} ms on the device (host: {dt_host:.2f} s), set_values {1e3 * dt:.2f} ms; "
               f"pcg it = {it_0} with Π_amg_0, {it_t} with Π_amg_t, |b - A u| / |b| = {float(torch.linalg.norm(r) / torch.linalg.norm(b)):.3e}")
     print(f"iters_0 = {iters_0}\niters_t = {iters_t}")
+    if args.batch:
+        batched(args.batch, api, ctx, plan, field, ξs, A_0, Π_amg_t.aggregates, iters_t)
     A_op.close(); plan.close()
+
+
+def batched(k, api, ctx, plan, field, ξs, A_0, aggregates, iters_t):
+    """the k realizations of the loop above as one batch: every system under the hierarchy of its own matrix"""
+    import torch
+    n = A_0.shape[0]
+    batch, bank = api.CsrBatch(ctx, A_0, k), api.AMGBank(ctx, A_0, k, aggregates=aggregates)
+    view = bank.view(k)
+    ctx.synchronize()
+    t = time.perf_counter()
+    a = field.coefficient(torch.from_numpy(np.column_stack(ξs)).cuda())                   # one pass: column t is exp.(g_t)
+    B = torch.stack([plan.update_batch(a[:, s].contiguous(), batch, s) for s in range(k)]).T
+    ctx.synchronize()
+    dt_asm = time.perf_counter() - t
+    t = time.perf_counter()
+    bank.set_values_batch(np.arange(k), batch, np.arange(k))                              # :182, k at a time
+    dt_set = time.perf_counter() - t
+    t = time.perf_counter()
+    X = torch.zeros((k, n), dtype=torch.float64, device="cuda").T
+    _, its, _ = api.pcg_batch(batch, np.arange(k), B, X, view, np.arange(k))
+    ctx.synchronize()
+    dt_solve = time.perf_counter() - t
+    print(f"batch of {k}: field + assembly {1e3 * dt_asm:.3f} ms, set_values_batch {1e3 * dt_set:.2f} ms, pcg_batch {1e3 * dt_solve:.2f} ms")
+    print(f"iters_t = {iters_t} (one realization at a time)\niters_b = {[int(i) for i in its]} (one batch)")
+    assert [int(i) for i in its] == iters_t, "the batched flow and the loop disagree"
+    batch.close(); bank.close()
 
 
 if __name__ == "__main__":

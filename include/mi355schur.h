@@ -347,6 +347,25 @@ int mi_pcg_batch(mi_op_t A_batch, int64_t k, const int64_t *slots, mi_op_t M_vie
                  const double *B, int64_t ldb, double *X, int64_t ldx, int64_t maxit, double eps, double *res_norm, int64_t ldres,
                  int64_t *it /* [k] */);
 
+/* mi_amg_bank_set_values_batch — the numeric set-up of k <= 16 bank members in ONE sequence of launches
+ * (csrc/amg_bank_setup.hpp): term t builds member members[t] from the values in slot slots[t] of `A_batch`, read on the
+ * device where they lie (no staging copy of A_0, no host round trip of values); the term is the grid's second dimension.
+ * members, slots and status are HOST arrays, 0-based. A member built here carries the bits of mi_amg_bank_set_values on the
+ * same values. Every term is committed separately: a term whose chain fails (a value that is not finite, a diagonal entry of a
+ * level missing or not positive, a coarse inverse without its certificate) leaves its member bit for bit as it was (unset, if
+ * it never was set); the healthy terms of the same call are committed. status[t] = MI_OK or MI_ERR_SINGULAR. Returns MI_OK when
+ * every term succeeded, and when `status` is given and only terms failed; with status == NULL a failed term makes the call
+ * return MI_ERR_SINGULAR after the healthy terms are committed, the message naming the failed terms and their reasons.
+ * Synchronous. Slot addresses never move: solve graphs captured on views of the bank stay valid. The workspace (k candidate
+ * slots and the per-term work) is allocated at the first call, grows only when a call has more terms than any before, and is
+ * counted in mi_amg_bank_stats' bytes_shared from then on.
+ * MI_ERR_BAD_ARG before any launch, the message naming the numbers: k < 1 or k > 16; a member or slot out of range; a slot
+ * never set; the same member twice (the same slot twice is allowed); a handle of the wrong kind; bank and batch of different
+ * contexts or sizes; a batch whose pattern is not the bank's (compared in full the first time this bank meets this batch); a
+ * context that is one rank of several. */
+int mi_amg_bank_set_values_batch(mi_op_t bank, int64_t k, const int64_t *members, mi_op_t A_batch, const int64_t *slots,
+                                 int *status /* [k], may be NULL */);
+
 /* mi_schur_assembled_create — `apply_local_schurs(Sd, ind_Γd_Γ2l, node_Γ_cnt, x)`, EPDD.jl:761-785:
  * Sx = Σ_d R_d' S_d R_d x with dense local Schur complements.
  *   Sd[d]          n_gamma_d[d]^2 doubles, column-major (Julia `Array(Sd[d])`)

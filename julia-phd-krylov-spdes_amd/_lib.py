@@ -78,6 +78,7 @@ SIGNATURES = {
     "mi_csr_batch_stride": [i64, i64p],
     "mi_full_assembly_update_batch": [vp, vp, vp, i64, vp],
     "mi_pcg_batch": [vp, i64, i64p, vp, i64p, vp, i64, vp, i64, i64, C.c_double, f64p, i64, i64p],
+    "mi_amg_bank_set_values_batch": [vp, i64, i64p, vp, i64p, C.POINTER(C.c_int)],
     "mi_schur_assembled_create": [vp, i64, i64, i64p, i64pp, f64pp, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_nn_create": [vp, i64, i64, i64p, i64pp, f64pp, i64p, C.c_int, i64, i64, C.POINTER(vp)],
     "mi_nn_create_stored": [vp, i64, i64, i64p, i64pp, f64pp, i64p, C.c_int, i64, i64, C.c_int, C.POINTER(vp)],

@@ -2313,6 +2313,27 @@ class AMGBank:
         self.ctx._order((k,), after=False)
         check(self.ctx._L.mi_amg_bank_set_values(self._h, i64(p), ptr))   # synchronous
 
+    def set_values_batch(self, members, batch: "CsrBatch", slots, strict: bool = True) -> np.ndarray:
+        """The hierarchies of k <= 16 members in one sequence of launches (`mi_amg_bank_set_values_batch`): member
+        `members[t]` from the values in slot `slots[t]` of a `CsrBatch` on the bank's pattern, read on the device where they
+        lie. A member carries the bits of `set_values(members[t], values)`. Synchronous. Returns a boolean array of per-term
+        success; a failed term leaves its member as it was, the healthy terms are committed. With `strict` a failed term
+        raises MiError(MI_ERR_SINGULAR) after that commit (the array is the exception's `.ok`)."""
+        mem, sl = _i64(members).ravel(), _i64(slots).ravel()
+        if mem.size != sl.size:
+            raise ValueError(f"{mem.size} members for {sl.size} slots")
+        status = (C.c_int * max(int(mem.size), 1))()
+        check(self.ctx._L.mi_amg_bank_set_values_batch(self._h, i64(int(mem.size)), mem.ctypes.data_as(i64p), getattr(batch, "_h", None),
+                                                       sl.ctypes.data_as(i64p), status))
+        ok = np.array([status[t] == _lib.MI_OK for t in range(mem.size)], dtype=bool)
+        if strict and not ok.all():
+            try:
+                check(_lib.MI_ERR_SINGULAR)   # the library's message names the failed terms and their reasons
+            except MiError as e:
+                e.ok = ok
+                raise
+        return ok
+
     def view(self, max_terms: int = 1) -> "AMGBankView":
         """An operator on this bank for up to `max_terms` (1 .. 16) members at a time; it selects member 0 at first."""
         v = AMGBankView(self, max_terms)
@@ -2413,16 +2434,44 @@ class AMGBankView(Operator):
         self._keep = ()
 
 
-def get_centroidal_bank(ctx: Context, centroids, field: KLField, assemble: Callable, A0, **amg_kw) -> AMGBank:
+def get_centroidal_bank(ctx: Context, centroids, field: KLField, assemble, A0, batch: int = 0, **amg_kw) -> AMGBank:
     """`get_centroidal_preconds` on a bank: member p is the constant AMG preconditioner of centroid p (column p of
     `centroids`, zero-padded to the field's modes), `assemble(a)` as there. One plan, one set of index arrays, P slots of
-    numbers: `bank.view().select(find_precond(ctx, ξ, hXt))` is the `Πs[p]` of Example12:106."""
+    numbers: `bank.view().select(find_precond(ctx, ξ, hXt))` is the `Πs[p]` of Example12:106.
+
+    `batch = k` (1 .. 16): `assemble` is a `FullAssemblyPlan` on the pattern of `A0`; the centroids' matrices are assembled k
+    at a time into a `CsrBatch` (`update_batch`) and k members are refreshed per call (`AMGBank.set_values_batch`; the last
+    call is short when k does not divide P). The members carry the bits of the default path on the same matrices."""
     centroids = np.asarray(centroids, dtype=np.float64)
-    bank = AMGBank(ctx, A0, centroids.shape[1], **amg_kw)
-    for p in range(centroids.shape[1]):
+    P = centroids.shape[1]
+    k = int(batch)
+    if k != batch or not 0 <= k <= AMG_BANK_MAX_TERMS:
+        raise ValueError(f"batch = {batch} (0: one member per call; 1 <= batch <= {AMG_BANK_MAX_TERMS})")
+    if k and not hasattr(assemble, "update_batch"):
+        raise TypeError("with batch > 0, `assemble` is the FullAssemblyPlan whose update_batch fills the slots")
+
+    def coefficient(p):
         ξ = np.zeros(field.m)
         ξ[:centroids.shape[0]] = centroids[:, p]
-        bank.set_values(p, assemble(field.coefficient(ξ)))
+        return field.coefficient(ξ)
+
+    bank = AMGBank(ctx, A0, P, **amg_kw)
+    if not k:
+        for p in range(P):
+            bank.set_values(p, assemble(coefficient(p)))
+        return bank
+    slab = CsrBatch(ctx, A0, k)
+    try:
+        for p0 in range(0, P, k):
+            members = np.arange(p0, min(p0 + k, P))
+            for s, p in enumerate(members):
+                assemble.update_batch(coefficient(p), slab, s)
+            bank.set_values_batch(members, slab, np.arange(members.size))
+    except Exception:
+        bank.close()
+        raise
+    finally:
+        slab.close()
     return bank
 
 

@@ -11,6 +11,8 @@
 //
 // set_values(p, val) runs the engine's refresh (the arithmetic of mi_amg_set_values, its kernels unchanged) and only then
 // copies the engine's committed buffers into slot p; a refresh that raises MI_ERR_SINGULAR leaves every slot as it was.
+// set_values_batch builds k members at once from k slots of a CsrBatch, with the member-indexed kernels and the candidate
+// slots of amg_bank_setup.hpp: the same bits, every term committed or kept by itself.
 //
 // A view (AmgBankView) is the operator: z = Σ_i c_i (Π_{m_i} \ r) for k <= max_terms members, the V(1,1) cycle of amg.hpp for
 // all terms in ONE sequence of 4 (L - 1) + 1 launches with the term as the grid's second dimension, then one combination
@@ -22,7 +24,7 @@
 // apply_batch is the same cycle for k independent right-hand sides, one member each (mi_pcg_batch, batch_solvers.hpp): term t
 // reads column t of R and writes column t of Z, and stops under its own flag. Its selection is a device array of its own.
 #pragma once
-#include "amg_setup.hpp"
+#include "amg_bank_setup.hpp"
 #include "vq.hpp"
 
 namespace mi {
@@ -227,6 +229,35 @@ struct AmgBankOp : Operator {
     MI_HIP(hipStreamSynchronize(s));
     for (int l = 0; l + 1 < nlev; ++l) omega_h[(size_t)m * (size_t)(nlev - 1) + (size_t)l] = eng.omega_h[(size_t)l];
     if (!is_set[(size_t)m]) { is_set[(size_t)m] = 1; ++n_set; }
+  }
+
+  // Members members[t] from the device values a_slab + slots[t] * a_stride, t < k, in one sequence of launches
+  // (amg_bank_setup.hpp). Every healthy term is committed — A_0 from where it lies, then one copy of its candidate slot —
+  // and a failed one leaves its member as it was; term[t] says which. Synchronous. The caller has checked k, the members
+  // (distinct, in range) and the slots.
+  AmgBankSetupWs bws;
+  unsigned long long batch_serial = 0; // Operator::serial of the CsrBatch whose pattern was compared with this bank's in full (0: none)
+  void set_values_batch(int k, const int64_t *members, const int64_t *slots, const double *a_slab, int64_t a_stride, std::vector<AsbTerm> &term) {
+    const int64_t a0_len = nlev > 1 ? off_a[1] : off_z;
+    amg_bank_setup_batch(eng, bws, k, members, slots, a_slab, a_stride, off_a, off_p, off_r, off_wd, off_z, off_om, stride, a0_len, term);
+    hipStream_t s = ctx->stream;
+    const size_t nom = 2 * (size_t)(nlev - 1);
+    std::vector<double> oh((size_t)k * std::max<size_t>(1, nom));
+    for (int t = 0; t < k; ++t) {
+      if (!term[(size_t)t].ok) continue;
+      double *d = slot(members[t]);
+      const double *c = bws.cand.p + (size_t)t * (size_t)bws.cs;
+      if (eng.nnz0) MI_HIP(hipMemcpyAsync(d, a_slab + (size_t)slots[t] * (size_t)a_stride, (size_t)eng.nnz0 * sizeof(double), hipMemcpyDeviceToDevice, s));
+      MI_HIP(hipMemcpyAsync(d + a0_len, c, (size_t)bws.cs * sizeof(double), hipMemcpyDeviceToDevice, s));
+      if (nom) MI_HIP(hipMemcpyAsync(oh.data() + (size_t)t * nom, c + (off_om - a0_len), nom * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    MI_HIP(hipStreamSynchronize(s));
+    for (int t = 0; t < k; ++t) {
+      if (!term[(size_t)t].ok) continue;
+      const size_t m = (size_t)members[t];
+      for (int l = 0; l + 1 < nlev; ++l) omega_h[m * (size_t)(nlev - 1) + (size_t)l] = oh[(size_t)t * nom + (size_t)2 * l];
+      if (!is_set[m]) { is_set[m] = 1; ++n_set; }
+    }
   }
 
   // read-back of one level of member `m`, as AmgOp::level_get (HOST arrays, 0-based, any pointer may be NULL)

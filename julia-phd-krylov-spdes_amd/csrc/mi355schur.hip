@@ -1572,7 +1572,7 @@ int mi_amg_bank_stats(mi_op_t bank, int64_t *capacity, int64_t *members_set, int
   if (!m) return fail(MI_ERR_BAD_ARG, "mi_amg_bank_stats: not an AMG bank (mi_amg_bank_create) but %s", bank_kind(bank));
   if (capacity) *capacity = m->capacity;
   if (members_set) *members_set = m->n_set;
-  if (bytes_shared) *bytes_shared = m->eng.kept;
+  if (bytes_shared) *bytes_shared = m->eng.kept + m->bws.bytes();   // (the batched set-up's workspace from its first call on)
   if (bytes_per_member) *bytes_per_member = 8 * m->stride;
   if (views) *views = m->views;
   return MI_OK;
@@ -1903,6 +1903,54 @@ int mi_pcg_batch(mi_op_t A_batch, int64_t k, const int64_t *slots, mi_op_t M_vie
     const int rc = kr.solve((int)k, slots, members, c->pin_b.p, (int64_t)n, c->pin_x.p, (int64_t)n, maxit, eps, res_norm, ldres, it);  // synchronises before returning
     for (int64_t t = 0; t < k; ++t) std::memcpy(X + (size_t)t * (size_t)ldx, c->pin_x.p + (size_t)t * n, n * sizeof(double));
     return rc;
+  });
+}
+int mi_amg_bank_set_values_batch(mi_op_t bank, int64_t k, const int64_t *members, mi_op_t A_batch, const int64_t *slots, int *status) {
+  const char *me = "mi_amg_bank_set_values_batch";
+  if (k < 1 || k > AMGB_MAX_TERMS) return fail(MI_ERR_BAD_ARG, "%s: k = %lld members (1 <= k <= %d)", me, (long long)k, AMGB_MAX_TERMS);
+  AmgBankOp *m = as_amg_bank(bank);
+  if (!m) return fail(MI_ERR_BAD_ARG, "%s: not an AMG bank (mi_amg_bank_create) but %s", me, batch_kind(bank));
+  CsrBatchOp *a = as_csr_batch(A_batch);
+  if (!a) return fail(MI_ERR_BAD_ARG, "%s: A is not a batch of sparse matrices (mi_csr_batch_create) but %s", me, batch_kind(A_batch));
+  if (!members || !slots) return fail(MI_ERR_BAD_ARG, "%s: members or slots is NULL", me);
+  mi_ctx_s *c = m->ctx;
+  if (a->ctx != c) return fail(MI_ERR_BAD_ARG, "%s: the bank and the batch belong to different contexts", me);
+  if (a->n != m->n || a->nnz != m->eng.nnz0)
+    return fail(MI_ERR_BAD_ARG, "%s: the batch is %lld x %lld with %lld stored entries, the bank's matrix %lld x %lld with %lld", me, (long long)a->n,
+                (long long)a->n, (long long)a->nnz, (long long)m->n, (long long)m->n, (long long)m->eng.nnz0);
+  if (c->n_ranks > 1) return fail(MI_ERR_BAD_ARG, "%s: this context is rank %d of %d; a batched set-up runs on a context of its own", me, c->rank, c->n_ranks);
+  for (int64_t t = 0; t < k; ++t) {
+    if (int rc = bank_member_check(me, m, members[t], false)) return rc;
+    if (int rc = batch_slot_check(me, a, slots[t], true)) return rc;
+    for (int64_t u = 0; u < t; ++u)
+      if (members[u] == members[t])
+        return fail(MI_ERR_BAD_ARG, "%s: member %lld is given twice (terms %lld and %lld); a member is built once per call", me, (long long)members[t],
+                    (long long)u, (long long)t);
+  }
+  if (m->batch_serial != a->serial) {   // the first time this bank meets this batch: the whole pattern
+    const amgp::Level &H = m->eng.plan.lv[0];
+    if (a->rowptr_h != H.a_ptr || a->col_h != H.a_col) return fail(MI_ERR_BAD_ARG, "%s: the pattern of the batch is not the bank's", me);
+    m->batch_serial = a->serial;
+  }
+  return guarded([&]() -> int {
+    c->use();
+    std::vector<AsbTerm> term;
+    m->set_values_batch((int)k, members, slots, a->slab.p, a->stride, term);   // synchronous
+    std::string why;
+    int bad = 0;
+    for (int64_t t = 0; t < k; ++t) {
+      const AsbTerm &T = term[(size_t)t];
+      if (status) status[t] = T.ok ? MI_OK : MI_ERR_SINGULAR;
+      if (T.ok) continue;
+      char buf[400];
+      std::snprintf(buf, sizeof buf, "%sterm %lld (member %lld, slot %lld): %s", bad ? "; " : "", (long long)t, (long long)members[t], (long long)slots[t],
+                    T.why.c_str());
+      why += buf;
+      ++bad;
+    }
+    if (!bad) return MI_OK;
+    const int rc = fail(MI_ERR_SINGULAR, "%s: %d of %lld terms failed; their members are kept as they were: %s", me, bad, (long long)k, why.c_str());
+    return status ? MI_OK : rc;
   });
 }
 int mi_full_assembly_stats(mi_plan_t plan, int64_t *row_blocks, int64_t *incidences, int64_t *bytes_kept) {

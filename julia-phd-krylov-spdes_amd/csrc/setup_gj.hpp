@@ -954,9 +954,19 @@ inline void pinv_blocks(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, const d
 inline std::atomic<long long> &spectral_pinv_calls() { static std::atomic<long long> n{0}; return n; }   // blocks sent to the eigen-decomposition (mi_ctx_query)
 
 // `spd_only` (block_jacobi.hpp: the Schur complements of an SPD matrix are SPD): the plain inverse with its certificate or
-// MI_ERR_SINGULAR; the floating and the spectral route are never taken.
-inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, const double *Sd, double rtol, double *Pi, bool spd_only = false) {
+// MI_ERR_SINGULAR; the floating and the spectral route are never taken. `failed` (amg_bank_setup.hpp; with spd_only): a block
+// that is not finite or misses its certificate does not raise; (*failed)[d] gets the words of the raise, the block's part
+// of Pi is left as it was, and the other blocks are finished. Without it the first bad block raises, as before.
+inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, const double *Sd, double rtol, double *Pi, bool spd_only = false,
+                             std::vector<std::string> *failed = nullptr) {
   hipStream_t s = c->stream;
+  if (failed) failed->assign((size_t)ndom, std::string());
+  auto bad_block = [&](int d, const char *fmt, auto... a) {   // raise, or note the words and go on
+    if (!failed) raise(MI_ERR_SINGULAR, fmt, a...);
+    char buf[512];
+    std::snprintf(buf, sizeof buf, fmt, a...);
+    (*failed)[(size_t)d] = buf;
+  };
   if (!spd_only && env_int("MI355_PINV_EIG", 0)) { spectral_pinv_calls() += ndom; pinv_blocks(c, ndom, n_gamma_d, Sd, rtol, Pi); return; }
   std::vector<GjStep> st(ndom);
   std::vector<GjDom> dm(ndom);
@@ -1035,14 +1045,17 @@ inline void pinv_blocks_fast(mi_ctx_s *c, int ndom, const int64_t *n_gamma_d, co
   for (int d = 0; d < ndom; ++d) {
     const int n = (int)n_gamma_d[d];
     if (!n) continue;
-    if (!std::isfinite(nS[d])) raise(MI_ERR_SINGULAR, "mi_nn_pinv: block %d is not finite (mi_schur_setup_run met a singular or indefinite interior block)", d);
+    if (!std::isfinite(nS[d])) {
+      bad_block(d, "mi_nn_pinv: block %d is not finite (mi_schur_setup_run met a singular or indefinite interior block)", d);
+      continue;
+    }
     const bool inv_ok = std::isfinite(nS[d]) && std::isfinite(nZ[d]) && nZ[d] > 0.0 && 1.0 / nZ[d] > rtol * nS[d] &&
                         probe_ok(n, nS[d], nZ[d], nR[d]);
     if (inv_ok) MI_HIP(hipMemcpyAsync(Pi + off[d], dm[d].Z[st[d].nb & 1], sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, s));
     else if (spd_only) {
-      MI_HIP(hipStreamSynchronize(s));             // the copies out of Z above
-      raise(MI_ERR_SINGULAR, "block %d (%d x %d) is singular or its inverse fails the certificate (probe residual %.3e, bar %.3e)", d, n, n, nR[d],
-            PROBE_C * n * eps * nS[d] * nZ[d]);
+      if (!failed) MI_HIP(hipStreamSynchronize(s));   // the copies out of Z above
+      bad_block(d, "block %d (%d x %d) is singular or its inverse fails the certificate (probe residual %.3e, bar %.3e)", d, n, n, nR[d],
+                PROBE_C * n * eps * nS[d] * nZ[d]);
     }
     // (max |S_ii| and ||S||_inf / sqrt(n) are both <= σ_max: an S 1 this small means pinv drops at least one eigenvalue)
     else if (std::isfinite(nS[d]) && nS[d] > 0.0 && nS1[d] <= rtol * std::max(nD[d], nS[d] / std::sqrt((double)n)) &&

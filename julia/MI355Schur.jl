@@ -1019,6 +1019,23 @@ function pcg_batch(A::MiCsrBatch, slots::Vector{Int}, B::Matrix{Float64}, X::Mat
               A.op.h, k, s0, M.op.h, m0, B, n, X, n, maxit, 1e-7, res, n, its))
   return X, Vector{Int}(its), [res[1:its[t], t] for t in 1:k]
 end
+"""`set_values!(bank, members, batch, slots)`: the hierarchies of `length(members)` (at most 16) bank members in one sequence of
+launches (`mi_amg_bank_set_values_batch`), member `members[t]` from the values in slot `slots[t]` of the batch, read on the
+device where they lie; 1-based members and slots. A member carries the bits of `set_values!(bank, members[t], A_t)`. Returns
+the per-term success; a term that fails leaves its member as it was, the healthy terms are committed, and with `strict` (the
+default) the call then throws as `set_values!(bank, p, A)` does."""
+function set_values!(bank::MiAMGBank, members::Vector{Int}, batch::MiCsrBatch, slots::Vector{Int}; strict::Bool=true)
+  k = length(members)
+  length(slots) == k || throw(ArgumentError("$(length(slots)) slots for $k members"))
+  m0 = Int64[member0(bank, p) for p in members]
+  s0 = Int64[slot0(batch, s) for s in slots]
+  status = zeros(Cint, k)
+  check(ccall((:mi_amg_bank_set_values_batch, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cint}),
+              bank.op.h, k, m0, batch.op.h, s0, status))
+  ok = status .== 0
+  strict && !all(ok) && check(MI_ERR_SINGULAR)         # the library's message names the failed terms
+  return ok
+end
 
 # ---------------------------------------------------------------- realization sampler (Example06:160, Example09 `draw!(sampler)`)
 """`MiKlField`: the step from a latent vector ξ to the field g = Σ_α sqrt(Λ_α) ξ_α Ψ[:, α] on the device (`mi_kl_field_t`).
